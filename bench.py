@@ -359,8 +359,29 @@ def conv_roofline(bank, B, per, precision, overlap, traffic):
     return r
 
 
+DUMP_SAMPLE = 1 << 22        # --dump-outputs: larger arrays are written as a fixed, seeded sample of this many elements
+
+
+def step_outputs(bank, ws):
+    """{name: float32 numpy array} of what one train step hands its caller: losses, per-cube scores, the updated parameters and
+    BatchNorm buffers of every UNet (arrays above DUMP_SAMPLE elements: the same seeded sample of distinct positions in every run)."""
+    l_raw, l_of = bank.losses(ws)
+    s_raw, s_of = bank.cube_scores(ws)
+    out = {'loss_raw': l_raw.reshape(1), 'cube_scores_raw': s_raw, 'params': bank.params, 'bn_buffers': bank.bufs}
+    if l_of is not None:
+        out.update({'loss_of': l_of.reshape(1), 'cube_scores_of': s_of})
+    res = {}
+    for name, t in out.items():
+        t = t.detach().float().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        res[name] = t.cpu().numpy()
+    return res
+
+
 def run_unet(model, precision, B, steps, warmup, dev, rank, world, dist, overlap='none', breakdown=False, pool=4096,
-             measure_forward=True, graph=True, ev_steps=1, small_batch_diag=False, ev_extra=4):
+             measure_forward=True, graph=True, ev_steps=1, small_batch_diag=False, ev_extra=4, dump=None):
     """W untimed + exactly K timed train steps; returns the record (rank 0) -- value is the whole-job rate.
 
     graph=True (default): the train step is replayed from a hipGraph (FusedTrainer, captured during the warm-up).  The first
@@ -368,7 +389,8 @@ def run_unet(model, precision, B, steps, warmup, dev, rank, world, dist, overlap
     (the roofline's live per-launch durations); the remaining steps replay the captured step.  ``ev_extra`` further eager event
     steps run right AFTER the timed region (same trainer, next batches) so that the roofline rests on (ev_steps + ev_extra) x 27
     launches instead of one sample per layer -- the record says how many were inside and how many after.  graph=False /
-    --breakdown / a side-stream schedule: every timed step is eager with events (the round-2 behaviour)."""
+    --breakdown / a side-stream schedule: every timed step is eager with events (the round-2 behaviour).
+    ``dump``: a dict that receives step_outputs() of the last timed step, taken after the timed region and before any later step."""
     from vec_vad_amd.trainer import FusedTrainer
     net, tot_of = build_net(model, precision, dev)
     # VV_FORCE_DIST=1 (a one-rank group under torch.distributed.run --nproc-per-node 1): the bucketed exchange runs anyway -- the
@@ -409,13 +431,15 @@ def run_unet(model, precision, B, steps, warmup, dev, rank, world, dist, overlap
     for it in range(steps):
         if it == n_ev:
             trainer.event_hook = None          # from here on: hipGraph replay
-        trainer.step_cubes(raw, flow, perm[warmup + it])
+        ws_last = trainer.step_cubes(raw, flow, perm[warmup + it])
     t_host = time.perf_counter() - t0          # the host has enqueued everything (no sync yet)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dt_local = dt
+    if dump is not None:
+        dump.update(step_outputs(bank, ws_last))
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -721,7 +745,10 @@ def main():
     ap.add_argument('--overlap', nargs='?', const='free', default='none', choices=('none', 'free', 'paired'),
                     help="side stream for the weight-gradient kernels: 'free' = under everything that follows (conv launches "
                          "are then contended), 'paired' = only under the next layer's BatchNorm backward (conv launches run alone)")
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed (rank 0) as DIR/<name>.npy, float32')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.cpu_child:
         cpu_child(args.cpu_child, args.batch if args.batch != 256 else 32, 3, 10, args.cpu_child_limit)
         return
@@ -750,9 +777,15 @@ def main():
 
     if dist is not None and dist.get_world_size() != args.gpus:
         raise SystemExit('process group has %d ranks, --gpus %d' % (dist.get_world_size(), args.gpus))
+    dump = {} if (args.dump_outputs and rank == 0) else None
     rec = run_unet(args.model, args.precision, args.batch, args.steps, args.warmup, dev, rank, world, dist, args.overlap,
                    args.breakdown, args.pool, graph=not args.no_graph, measure_forward=not args.no_forward_timing,
-                   ev_extra=0 if args.no_forward_timing else 4)
+                   ev_extra=0 if args.no_forward_timing else 4, dump=dump)
+    if dump is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
     # N > 1: the second record SURVEY 8(d) asks for beside the weak-scaling headline -- the reference's own split (train.py:373-375:
     # nn.DataParallel scatters ONE 256-cube batch over the GPUs => 256 / N cubes per rank and step, per-rank BatchNorm statistics)
     rec_dp = None
