@@ -30,9 +30,10 @@ def pair_of(frame_range):
     return 1, 2
 
 
-def load_flownet2(path=CHECKPOINT, device='cuda'):
-    """calc_optical_flow.py:15-22: keep the checkpoint entries whose key exists in the model."""
-    net = FlowNet2()
+def load_flownet2(path=CHECKPOINT, device='cuda', fp16=False):
+    """calc_optical_flow.py:15-22: keep the checkpoint entries whose key exists in the model.  fp16=True: FlowNet2(fp16=True),
+    fp16 activations on fp16 MFMA (the parameters and the written .npy files stay float32)."""
+    net = FlowNet2(fp16=fp16)
     pretrained = torch.load(path, map_location='cpu', weights_only=False)['state_dict']
     own = net.state_dict()
     own.update({k: v for k, v in pretrained.items() if k in own})
@@ -129,7 +130,12 @@ def calc_optical_flow(dataset, flownet2=None, of_root_dir='./optical_flow', log=
 
 if __name__ == '__main__':
     # Same example as the reference (calc_optical_flow.py:105-112); change dataset_name for the other datasets.
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--fp16', action='store_true', help='FlowNet2(fp16=True): fp16 activations, fp32 arithmetic')
+    args = ap.parse_args()
     dataset_name = 'UCSDped2'
+    net = load_flownet2(fp16=args.fp16)
     for mode in ('train', 'test'):
         calc_optical_flow(unified_dataset_interface(dataset_name=dataset_name, dir=os.path.join('raw_datasets', dataset_name),
-                                                    context_frame_num=1, mode=mode, border_mode='hard'))
+                                                    context_frame_num=1, mode=mode, border_mode='hard'), flownet2=net)

@@ -519,6 +519,43 @@ int vv_num_cus(void);
  * (cgo / ctypes) checks its own mirror of the struct against it once at load: vv_conv_params grew at its end in round 4. */
 int vv_abi_sizeof(int32_t which);
 
+/* ---- FlowNet2 fp16 mode (FlowNet2(fp16=True); FlowNet2_src/main.py:123-125 "fp16 storage fp32 math") ----
+ * The exception to "all tensors are fp32": activations and weight panels below are IEEE fp16 (uint16_t bit patterns), NHWC with
+ * channel strides in halves that are multiples of 8 (16 B).  Arithmetic is fp32; a result is rounded to fp16 where the module graph
+ * after .half() materialises a tensor: a conv / deconv output is (acc + bias) rounded, LeakyReLU'd and rounded again; bias and the
+ * fp32 weights of the two-channel heads hold fp16-rounded values.
+ *  vv_conv2d_f16        : vv_conv2d_mfma's layer forms (kinds 0 / 1 / 2, ksplit) on v_mfma_f32_32x32x16_f16 (16x16x32 for Cout <= 16).
+ *                         `p` is the vv_conv2d_params of vv_conv2d_mfma with src.ptr / out.ptr pointing at fp16 data (cstride / coff in
+ *                         halves, src cstride % 8 == 0), w = a vv_pack_conv2d_f16 panel; CinP % 32 == 0 (kind 2: the flattened (kx, c)
+ *                         run of an 8-half pixel, CinP = 64 for 7x7 s2 or 32 for 3x3 s1).  With ksplit > 1, out is an fp32 workspace
+ *                         [ksplit][B*OH*OW][CoutP] finished by vv_conv2d_splitk_finish_f16.
+ *  vv_pack_conv2d_f16   : fp32 Conv2d [N][K][taps] / ConvTranspose2d [K][N][taps] weight -> fp16 panel [taps][KP/8][NP][8] (KP % 16,
+ *                         NP % 32 == 0; zero padding).
+ *  vv_conv3x3_n2_f16 / vv_deconv4x4_c2_f16 / vv_correlation_nhwc_f16 / vv_flownet_prep_f16 / vv_warp_pack12_f16 /
+ *  vv_fusion_pack11_f16 : the fp32 entry points above on fp16 maps (images and flows of 8-half pixels, packed outputs of 16).
+ *  vv_out8_to_nchw_f16  : vv_out4_to_nchw from an 8-half pixel map to NCHW fp16 (dst_f16 = 1) or fp32 (dst_f16 = 0). */
+int vv_conv2d_f16(const vv_conv2d_params* p, vv_stream stream);
+int vv_pack_conv2d_f16(const float* w, uint16_t* packed, int32_t taps, int32_t K, int32_t KP, int32_t N, int32_t NP,
+                       int32_t transposed, vv_stream stream);
+int vv_conv2d_splitk_finish_f16(const float* ws, int32_t ksplit, int64_t M, int32_t Cout, int32_t CoutP, const float* bias,
+                                float slope, uint16_t* out, int32_t out_cstride, int32_t out_coff, vv_stream stream);
+int vv_conv3x3_n2_f16(const uint16_t* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* wq,
+                      int32_t C4P, const float* bias, float slope, uint16_t* out, int32_t out_cstride, int32_t out_coff,
+                      vv_stream stream);
+int vv_deconv4x4_c2_f16(const uint16_t* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, const float* w, const float* bias,
+                        float slope, uint16_t* out, int32_t out_cstride, int32_t out_coff, vv_stream stream);
+int vv_correlation_nhwc_f16(const uint16_t* f1, const uint16_t* f2, int32_t cstride, int32_t B, int32_t C, int32_t H, int32_t W,
+                            uint16_t* out, int32_t out_cstride, int32_t out_coff, float slope, vv_stream stream);
+int vv_flownet_prep_f16(const float* inputs, int32_t B, int32_t H, int32_t W, float rgb_max, void* workspace,
+                        int64_t workspace_bytes, uint16_t* x6, uint16_t* img0, uint16_t* img1, vv_stream stream);
+int vv_warp_pack12_f16(const uint16_t* x6, const uint16_t* img1, const uint16_t* flow2, int32_t flow_cstride, int32_t B, int32_t H,
+                       int32_t W, int32_t mode, float scale, float div_flow, uint16_t* out16, vv_stream stream);
+int vv_fusion_pack11_f16(const uint16_t* x6, const uint16_t* img1, const uint16_t* s2_flow2, int32_t s2_cstride,
+                         const uint16_t* sd_flow2, int32_t sd_cstride, int32_t B, int32_t H, int32_t W, float div_flow,
+                         uint16_t* out16, vv_stream stream);
+int vv_out8_to_nchw_f16(int32_t B, int32_t HW, int32_t oc, const uint16_t* out8, void* dst, int32_t dst_f16, int32_t Ctot,
+                        int32_t choff, vv_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,16 @@ _SIGS = {
     'vv_frame_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double, C.c_double, C.c_double, c_i32, c_vp,
                                 c_vp]),
     'vv_roc_auc_counts': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
+    'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),
+    'vv_conv3x3_n2_f16': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),
+    'vv_deconv4x4_c2_f16': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),
+    'vv_correlation_nhwc_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_f32, c_vp]),
+    'vv_flownet_prep_f16': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    'vv_warp_pack12_f16': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp]),
+    'vv_fusion_pack11_f16': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    'vv_out8_to_nchw_f16': (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     'vv_version': (C.c_char_p, []),
     'vv_abi_sizeof': (c_i32, [c_i32]),
     'vv_status_string': (C.c_char_p, [c_i32]),

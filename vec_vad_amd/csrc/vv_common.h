@@ -140,6 +140,53 @@ __device__ __forceinline__ uint4 vv_pack_bf16x8(const vv_f8& f) {
   return make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
 
+// ---- element type of the FlowNet2 activations: float (the fp32 forward) or _Float16 (fp16 storage, fp32 arithmetic).
+// Loads widen to float, vv_rnd<T> is the rounding a half tensor applies when it is materialised (identity for float), and
+// vv_act_out<T> is "bias-added value -> [LeakyReLU] -> stored element" in the order of conv -> LeakyReLU on tensors of type T:
+// for half the pre-activation is rounded, the activation runs on the rounded value and its result is rounded again.
+typedef _Float16 vv_h;
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+typedef _Float16 v4h __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ float vv_rnd(const float v) {
+  if constexpr (std::is_same<T, float>::value) return v;
+  else return (float)(vv_h)v;
+}
+template <typename T>
+__device__ __forceinline__ T vv_act_out(const float v, const float slope) {
+  if constexpr (std::is_same<T, float>::value) {
+    return v > 0.f ? v : v * slope;
+  } else {
+    const float r = (float)(vv_h)v;
+    return (vv_h)(r > 0.f ? r : r * slope);
+  }
+}
+template <typename T>
+__device__ __forceinline__ float4 vv_ld4(const T* p) {
+  if constexpr (std::is_same<T, float>::value) {
+    return *reinterpret_cast<const float4*>(p);
+  } else {
+    const v4h h = *reinterpret_cast<const v4h*>(p);
+    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+  }
+}
+template <typename T>
+__device__ __forceinline__ float2 vv_ld2(const T* p) {
+  if constexpr (std::is_same<T, float>::value) {
+    return *reinterpret_cast<const float2*>(p);
+  } else {
+    return make_float2((float)p[0], (float)p[1]);
+  }
+}
+template <typename T>
+__device__ __forceinline__ void vv_st4(T* p, const float4 v) {
+  if constexpr (std::is_same<T, float>::value) {
+    *reinterpret_cast<float4*>(p) = v;
+  } else {
+    *reinterpret_cast<v4h*>(p) = v4h{(vv_h)v.x, (vv_h)v.y, (vv_h)v.z, (vv_h)v.w};
+  }
+}
+
 // Resolved (per group) description of how a convolution reads its input.
 struct VVSrc {
   const float* p0; int cs0, co0;

@@ -378,17 +378,17 @@ conv2d_mfma_kernel(const vv_conv2d_params p, const int tilesX, const int tilesY,
     }
 }
 
+template <typename T>
 __global__ void __launch_bounds__(VV_WG)
 splitk_finish_kernel(const float* __restrict__ ws, const int KS, const int64_t M, const int Cout, const int CoutP,
-                     const float* __restrict__ bias, const float slope, float* __restrict__ out, const int ocs) {
+                     const float* __restrict__ bias, const float slope, T* __restrict__ out, const int ocs) {
   const int64_t e = (int64_t)blockIdx.x * VV_WG + threadIdx.x;
   if (e >= M * Cout) return;
   const int co = (int)(e % Cout);
   const int64_t pix = e / Cout;
   float v = bias ? bias[co] : 0.f;
   for (int k = 0; k < KS; ++k) v += ws[((int64_t)k * M + pix) * CoutP + co];      // fixed order: deterministic
-  v = v > 0.f ? v : v * slope;
-  out[pix * ocs + co] = v;
+  out[pix * ocs + co] = vv_act_out<T>(v, slope);
 }
 
 __global__ void __launch_bounds__(VV_WG)
@@ -497,11 +497,11 @@ conv3x3_n2_kernel(const float* __restrict__ src, const int scs, const int B, con
 // Same layer when the image is small and the channel count large (the H/8 ... H/64 pyramid levels: 112 .. 28k pixels x up
 // to 1026 channels): LPP lanes share one output pixel, each takes every LPP-th group of 4 input channels straight from
 // global memory (the 9x re-read of the small map is served by L2), partial sums meet in a shuffle tree.
-template <int LPP>
+template <int LPP, typename T = float>
 __global__ void __launch_bounds__(VV_WG)
-conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
+conv3x3_n2_split_kernel(const T* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
                         const float* __restrict__ wq, const int C4P, const float* __restrict__ bias, const float slope,
-                        float* __restrict__ out, const int ocs) {
+                        T* __restrict__ out, const int ocs) {
   const int64_t pix = ((int64_t)blockIdx.x * VV_WG + threadIdx.x) / LPP;
   const int sub = threadIdx.x % LPP;
   const int64_t npix = (int64_t)B * H * W;
@@ -515,7 +515,7 @@ conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int 
     for (int t = 0; t < 9; ++t) {
       const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
       if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
-      const float4* pa = reinterpret_cast<const float4*>(src + ((int64_t)(img * H + yy) * W + xx) * scs);
+      const T* pa = src + ((int64_t)(img * H + yy) * W + xx) * scs;
       const float4* pw = wq4 + (int64_t)t * C4P * 2;
       // four channel groups per trip, their 12 loads issued before the first multiply-add: the loop is a chain of L2 round trips
       // (the map is small), one load in flight per lane made it 4x slower
@@ -524,7 +524,7 @@ conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int 
         float4 v[4], w0[4], w1[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          v[u] = pa[k + u * LPP];
+          v[u] = vv_ld4(pa + 4 * (k + u * LPP));
           w0[u] = pw[2 * (k + u * LPP)];
           w1[u] = pw[2 * (k + u * LPP) + 1];
         }
@@ -535,7 +535,7 @@ conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int 
         }
       }
       for (; k < C4; k += LPP) {
-        const float4 v = pa[k], w0 = pw[2 * k], w1 = pw[2 * k + 1];
+        const float4 v = vv_ld4(pa + 4 * k), w0 = pw[2 * k], w1 = pw[2 * k + 1];
         a0 = fmaf(v.w, w0.w, fmaf(v.z, w0.z, fmaf(v.y, w0.y, fmaf(v.x, w0.x, a0))));
         a1 = fmaf(v.w, w1.w, fmaf(v.z, w1.z, fmaf(v.y, w1.y, fmaf(v.x, w1.x, a1))));
       }
@@ -548,9 +548,9 @@ conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int 
   }
   if (live && sub == 0) {
     float v0 = a0 + (bias ? bias[0] : 0.f), v1 = a1 + (bias ? bias[1] : 0.f);
-    float* o = out + pix * ocs;
-    o[0] = v0 > 0.f ? v0 : v0 * slope;
-    o[1] = v1 > 0.f ? v1 : v1 * slope;
+    T* o = out + pix * ocs;
+    o[0] = vv_act_out<T>(v0, slope);
+    o[1] = vv_act_out<T>(v1, slope);
   }
 }
 
@@ -558,11 +558,11 @@ conv3x3_n2_split_kernel(const float* __restrict__ src, const int scs, const int 
 // channel slice v of the halo tile in LDS (its weights stay wave-uniform: scalar loads), the four slice sums meet in LDS in wave
 // order.  Four times the workgroups of the 8 x 32 form and no zero-padded channels: 29 -> 20 us (16 channels, 448 x 1024), 18 -> 11 us
 // (32 channels, 224 x 512).  With 64-channel chunks on the quarter-resolution maps it measured slower than the split form below.
-template <int CK>
+template <int CK, typename T = float>
 __global__ void __launch_bounds__(VV_WG)
-conv3x3_n2_tile_kernel(const float* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
+conv3x3_n2_tile_kernel(const T* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
                        const float* __restrict__ wq, const int C4P, const float* __restrict__ bias, const float slope,
-                       float* __restrict__ out, const int ocs, const int tilesX, const int tilesY) {
+                       T* __restrict__ out, const int ocs, const int tilesX, const int tilesY) {
   constexpr int TH = 4, TW = 16, HH = TH + 2, HW = TW + 2, S4 = CK / 4 + 1, Q = CK / 4, QW = Q / 4;
   static_assert(QW >= 1, "a float4 group per wave");
   __shared__ float4 lds4[HH * HW * S4];
@@ -589,7 +589,7 @@ conv3x3_n2_tile_kernel(const float* __restrict__ src, const int scs, const int B
       const int y = ty * TH - 1 + hp / HW, x = tx * TW - 1 + hp % HW;
       stg[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (it < HH * HW * Q && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && (c0 >> 2) + q < C4)
-        stg[k] = *reinterpret_cast<const float4*>(src + ((int64_t)(img * H + y) * W + x) * scs + c0 + q * 4);
+        stg[k] = vv_ld4(src + ((int64_t)(img * H + y) * W + x) * scs + c0 + q * 4);
     }
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
@@ -618,9 +618,9 @@ conv3x3_n2_tile_kernel(const float* __restrict__ src, const int scs, const int B
   if (wave == 0 && oy < H && ox < W) {
     float v0 = ((part[0][lane].x + part[1][lane].x) + part[2][lane].x) + part[3][lane].x + (bias ? bias[0] : 0.f);
     float v1 = ((part[0][lane].y + part[1][lane].y) + part[2][lane].y) + part[3][lane].y + (bias ? bias[1] : 0.f);
-    float* o = out + ((int64_t)(img * H + oy) * W + ox) * ocs;
-    o[0] = v0 > 0.f ? v0 : v0 * slope;
-    o[1] = v1 > 0.f ? v1 : v1 * slope;
+    T* o = out + ((int64_t)(img * H + oy) * W + ox) * ocs;
+    o[0] = vv_act_out<T>(v0, slope);
+    o[1] = vv_act_out<T>(v1, slope);
   }
 }
 
@@ -628,11 +628,11 @@ conv3x3_n2_tile_kernel(const float* __restrict__ src, const int scs, const int B
 // WAVE PER FILTER TAP -- a workgroup of nine waves owns 64 / LPT pixels, wave t multiplies tap t for all of them, LPT lanes share a
 // pixel and split its channel groups (all their loads in flight together), a shuffle tree sums the lanes, and the nine tap sums meet
 // in LDS in tap order (fixed order: bitwise reproducible).  Nine times the workgroups' worth of loads in flight of the form above.
-template <int LPT>
+template <int LPT, typename T = float>
 __global__ void __launch_bounds__(576)
-conv3x3_n2_tap_kernel(const float* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
+conv3x3_n2_tap_kernel(const T* __restrict__ src, const int scs, const int B, const int H, const int W, const int Cin,
                       const float* __restrict__ wq, const int C4P, const float* __restrict__ bias, const float slope,
-                      float* __restrict__ out, const int ocs) {
+                      T* __restrict__ out, const int ocs) {
   constexpr int PP = 64 / LPT;                // pixels per workgroup
   __shared__ float2 part[9][PP];
   const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
@@ -645,14 +645,14 @@ conv3x3_n2_tap_kernel(const float* __restrict__ src, const int scs, const int B,
   const int C4 = (Cin + 3) >> 2;
   float a0 = 0.f, a1 = 0.f;
   if (live) {
-    const float4* pa = reinterpret_cast<const float4*>(src + ((int64_t)(img * H + yy) * W + xx) * scs);
+    const T* pa = src + ((int64_t)(img * H + yy) * W + xx) * scs;
     const float4* pw = reinterpret_cast<const float4*>(wq) + (int64_t)t * C4P * 2;
     int k = sub;
     for (; k + 3 * LPT < C4; k += 4 * LPT) {
       float4 v[4], w0[4], w1[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        v[u] = pa[k + u * LPT];
+        v[u] = vv_ld4(pa + 4 * (k + u * LPT));
         w0[u] = pw[2 * (k + u * LPT)];
         w1[u] = pw[2 * (k + u * LPT) + 1];
       }
@@ -663,7 +663,7 @@ conv3x3_n2_tap_kernel(const float* __restrict__ src, const int scs, const int B,
       }
     }
     for (; k < C4; k += LPT) {
-      const float4 v = pa[k], w0 = pw[2 * k], w1 = pw[2 * k + 1];
+      const float4 v = vv_ld4(pa + 4 * k), w0 = pw[2 * k], w1 = pw[2 * k + 1];
       a0 = fmaf(v.w, w0.w, fmaf(v.z, w0.z, fmaf(v.y, w0.y, fmaf(v.x, w0.x, a0))));
       a1 = fmaf(v.w, w1.w, fmaf(v.z, w1.z, fmaf(v.y, w1.y, fmaf(v.x, w1.x, a1))));
     }
@@ -686,19 +686,20 @@ conv3x3_n2_tap_kernel(const float* __restrict__ src, const int scs, const int B,
       }
       v0 += bias ? bias[0] : 0.f;
       v1 += bias ? bias[1] : 0.f;
-      float* o = out + q * ocs;
-      o[0] = v0 > 0.f ? v0 : v0 * slope;
-      o[1] = v1 > 0.f ? v1 : v1 * slope;
+      T* o = out + q * ocs;
+      o[0] = vv_act_out<T>(v0, slope);
+      o[1] = vv_act_out<T>(v1, slope);
     }
   }
 }
 
 // upsampled_flow*: nn.ConvTranspose2d(2, 2, 4, 2, 1[, bias]) (FlowNetC.py:53-60, FlowNetS.py:40-47, FlowNetSD.py:45-52,
 // FlowNetFusion.py:35-36): 2x2 taps x 2 channels per output -- one thread per output pixel.
+template <typename T>
 __global__ void __launch_bounds__(VV_WG)
-deconv4x4_c2_kernel(const float* __restrict__ src, const int scs, const int B, const int H, const int W,
+deconv4x4_c2_kernel(const T* __restrict__ src, const int scs, const int B, const int H, const int W,
                     const float* __restrict__ wt, const float* __restrict__ bias, const float slope,
-                    float* __restrict__ out, const int ocs) {
+                    T* __restrict__ out, const int ocs) {
   const int OH = 2 * H, OW = 2 * W;
   const int64_t e = (int64_t)blockIdx.x * VV_WG + threadIdx.x;
   if (e >= (int64_t)B * OH * OW) return;
@@ -713,7 +714,7 @@ deconv4x4_c2_kernel(const float* __restrict__ src, const int scs, const int B, c
     for (int b = 0; b < 2; ++b) {
       const int kx = ((ox + 1) & 1) + 2 * b, ix = (ox + 1 - kx) >> 1;
       if ((unsigned)ix >= (unsigned)W) continue;
-      const float* p = src + ((int64_t)(img * H + iy) * W + ix) * scs;
+      const T* p = src + ((int64_t)(img * H + iy) * W + ix) * scs;
       const float x0 = p[0], x1 = p[1];
       // weight [Cin][Cout][4][4]
       v0 = fmaf(x0, wt[(0 * 2 + 0) * 16 + ky * 4 + kx], v0);
@@ -722,9 +723,9 @@ deconv4x4_c2_kernel(const float* __restrict__ src, const int scs, const int B, c
       v1 = fmaf(x1, wt[(1 * 2 + 1) * 16 + ky * 4 + kx], v1);
     }
   }
-  float* o = out + e * ocs;
-  o[0] = v0 > 0.f ? v0 : v0 * slope;
-  o[1] = v1 > 0.f ? v1 : v1 * slope;
+  T* o = out + e * ocs;
+  o[0] = vv_act_out<T>(v0, slope);
+  o[1] = vv_act_out<T>(v1, slope);
 }
 
 template <int R, int STRIDE, int DECONV, int CK, int CP = 0>
@@ -784,48 +785,62 @@ extern "C" int vv_conv2d_mfma(const vv_conv2d_params* p, vv_stream stream) {
   return VV_ERR_UNSUPPORTED;
 }
 
-extern "C" int vv_conv3x3_n2(const float* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin,
-                             const float* wq, int32_t C4P, const float* bias, float slope, float* out, int32_t out_cstride,
-                             int32_t out_coff, vv_stream stream) {
+namespace {
+
+// T = float: the fp32 forward; T = _Float16: fp16 activations (wq / bias hold fp16-rounded values in fp32), fp32 arithmetic.  The fp16
+// form has no staged 8 x 32 variant: full-resolution maps of more than 32 channels take the 8-lane split form.
+template <typename T>
+int launch_n2(const T* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* wq, int32_t C4P,
+              const float* bias, float slope, T* out, int32_t out_cstride, int32_t out_coff, hipStream_t st) {
   if (!src || !wq || !out || src_cstride % 4 || C4P * 4 < ((Cin + 31) & ~31)) return VV_ERR_BAD_ARG;
   if ((int64_t)B * H * W * src_cstride >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
   const int64_t npix = (int64_t)B * H * W;
-  hipStream_t st = (hipStream_t)stream;
+  constexpr bool F32 = std::is_same<T, float>::value;
   if (npix >= 20000 && Cin <= 32) {
     // the 16 / 32-channel heads at full / half resolution: 4 x 16 tiles, the four waves split the channels
     const int tilesY = (H + 3) / 4, tilesX = (W + 15) / 16;
     const dim3 grid(B * tilesY * tilesX);
     if (Cin <= 16)
-      VV_LAUNCH(conv3x3_n2_tile_kernel<16>, grid, dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,
+      VV_LAUNCH((conv3x3_n2_tile_kernel<16, T>), grid, dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,
                 out + out_coff, out_cstride, tilesX, tilesY);
     else
-      VV_LAUNCH(conv3x3_n2_tile_kernel<32>, grid, dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,
+      VV_LAUNCH((conv3x3_n2_tile_kernel<32, T>), grid, dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,
                 out + out_coff, out_cstride, tilesX, tilesY);
-  } else if (npix >= 100000) {              // full / half resolution, more channels: 8 x 32 tiles, one thread per pixel
-    const int tilesY = (H + 7) / 8, tilesX = (W + 31) / 32;
-    VV_LAUNCH(conv3x3_n2_kernel, dim3(B * tilesY * tilesX), dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias,
-              slope, out + out_coff, out_cstride, tilesX, tilesY);
+  } else if (F32 && npix >= 100000) {       // full / half resolution, more channels: 8 x 32 tiles, one thread per pixel
+    if constexpr (F32) {
+      const int tilesY = (H + 7) / 8, tilesX = (W + 31) / 32;
+      VV_LAUNCH(conv3x3_n2_kernel, dim3(B * tilesY * tilesX), dim3(VV_WG), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias,
+                slope, out + out_coff, out_cstride, tilesX, tilesY);
+    }
   } else if (npix >= 20000) {               // quarter resolution: 8 lanes per pixel, the 9x re-read served by L2
-    VV_LAUNCH(conv3x3_n2_split_kernel<8>, dim3((unsigned)((npix * 8 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
+    VV_LAUNCH((conv3x3_n2_split_kernel<8, T>), dim3((unsigned)((npix * 8 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
               src_cstride, B, H, W, Cin, wq, C4P, bias, slope, out + out_coff, out_cstride);
   } else if (Cin >= 320) {
     // many channels on a small map: one wave per filter tap (fewer channels leave its lanes idle: the split form below)
     const int lpt = npix >= 4096 ? 16 : (npix >= 1024 ? 32 : 64);
     const dim3 grid((unsigned)((npix * lpt + 63) / 64));
 #define VV_N2_TAP(L_)                                                                                                        \
-    VV_LAUNCH(conv3x3_n2_tap_kernel<L_>, grid, dim3(576), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,       \
+    VV_LAUNCH((conv3x3_n2_tap_kernel<L_, T>), grid, dim3(576), 0, st, src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope,  \
               out + out_coff, out_cstride)
     if (lpt == 16) VV_N2_TAP(16); else if (lpt == 32) VV_N2_TAP(32); else VV_N2_TAP(64);
 #undef VV_N2_TAP
   } else if (npix >= 4096) {                // H/8: 7168 pixels x up to 386 channels -- 32 lanes per pixel fill the chip
-    VV_LAUNCH(conv3x3_n2_split_kernel<32>, dim3((unsigned)((npix * 32 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
+    VV_LAUNCH((conv3x3_n2_split_kernel<32, T>), dim3((unsigned)((npix * 32 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
               src_cstride, B, H, W, Cin, wq, C4P, bias, slope, out + out_coff, out_cstride);
   } else {
-    VV_LAUNCH(conv3x3_n2_split_kernel<64>, dim3((unsigned)((npix * 64 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
+    VV_LAUNCH((conv3x3_n2_split_kernel<64, T>), dim3((unsigned)((npix * 64 + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, st, src,
               src_cstride, B, H, W, Cin, wq, C4P, bias, slope, out + out_coff, out_cstride);
   }
   VV_CHECK_LAUNCH();
   return VV_OK;
+}
+
+}  // namespace
+
+extern "C" int vv_conv3x3_n2(const float* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                             const float* wq, int32_t C4P, const float* bias, float slope, float* out, int32_t out_cstride,
+                             int32_t out_coff, vv_stream stream) {
+  return launch_n2<float>(src, src_cstride, B, H, W, Cin, wq, C4P, bias, slope, out, out_cstride, out_coff, (hipStream_t)stream);
 }
 
 extern "C" int vv_deconv4x4_c2(const float* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, const float* w,
@@ -833,7 +848,7 @@ extern "C" int vv_deconv4x4_c2(const float* src, int32_t src_cstride, int32_t B,
                                vv_stream stream) {
   if (!src || !w || !out) return VV_ERR_BAD_ARG;
   const int64_t n = (int64_t)B * 4 * H * W;
-  VV_LAUNCH(deconv4x4_c2_kernel, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, src,
+  VV_LAUNCH(deconv4x4_c2_kernel<float>, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, src,
             src_cstride, B, H, W, w, bias, slope, out + out_coff, out_cstride);
   VV_CHECK_LAUNCH();
   return VV_OK;
@@ -844,7 +859,7 @@ extern "C" int vv_conv2d_splitk_finish(const float* ws, int32_t ksplit, int64_t 
                                        vv_stream stream) {
   if (!ws || !out || ksplit < 1) return VV_ERR_BAD_ARG;
   const int64_t n = M * Cout;
-  VV_LAUNCH(splitk_finish_kernel, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, ws, ksplit, M,
+  VV_LAUNCH(splitk_finish_kernel<float>, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, ws, ksplit, M,
             Cout, CoutP, bias, slope, out + out_coff, out_cstride);
   VV_CHECK_LAUNCH();
   return VV_OK;
@@ -868,6 +883,37 @@ extern "C" int vv_upsample4(const float* src, float* dst, int32_t BC, int32_t H,
   const int64_t n = (int64_t)BC * 16 * H * W;
   VV_LAUNCH(upsample4_kernel, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, n, src, dst, BC,
             H, W, bilinear, scale);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+// ---- fp16 activations (FlowNet2(fp16=True)): the same kernels instantiated on _Float16 storage, fp32 arithmetic
+extern "C" int vv_conv3x3_n2_f16(const uint16_t* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                                 const float* wq, int32_t C4P, const float* bias, float slope, uint16_t* out,
+                                 int32_t out_cstride, int32_t out_coff, vv_stream stream) {
+  return launch_n2<vv_h>(reinterpret_cast<const vv_h*>(src), src_cstride, B, H, W, Cin, wq, C4P, bias, slope,
+                         reinterpret_cast<vv_h*>(out), out_cstride, out_coff, (hipStream_t)stream);
+}
+
+extern "C" int vv_deconv4x4_c2_f16(const uint16_t* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, const float* w,
+                                   const float* bias, float slope, uint16_t* out, int32_t out_cstride, int32_t out_coff,
+                                   vv_stream stream) {
+  if (!src || !w || !out) return VV_ERR_BAD_ARG;
+  const int64_t n = (int64_t)B * 4 * H * W;
+  VV_LAUNCH(deconv4x4_c2_kernel<vv_h>, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream,
+            reinterpret_cast<const vv_h*>(src), src_cstride, B, H, W, w, bias, slope, reinterpret_cast<vv_h*>(out) + out_coff,
+            out_cstride);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_conv2d_splitk_finish_f16(const float* ws, int32_t ksplit, int64_t M, int32_t Cout, int32_t CoutP,
+                                           const float* bias, float slope, uint16_t* out, int32_t out_cstride, int32_t out_coff,
+                                           vv_stream stream) {
+  if (!ws || !out || ksplit < 1) return VV_ERR_BAD_ARG;
+  const int64_t n = M * Cout;
+  VV_LAUNCH(splitk_finish_kernel<vv_h>, dim3((unsigned)((n + VV_WG - 1) / VV_WG)), dim3(VV_WG), 0, (hipStream_t)stream, ws, ksplit,
+            M, Cout, CoutP, bias, slope, reinterpret_cast<vv_h*>(out) + out_coff, out_cstride);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

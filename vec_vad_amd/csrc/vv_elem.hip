@@ -809,15 +809,18 @@ nchw_to_nhwc_kernel(const int B, const int C, const int HW, const float* __restr
   const int64_t b = e / HW, pix = e % HW;
   for (int c = 0; c < C; ++c) dst[e * C + c] = src[(b * C + c) * HW + pix];
 }
+// TI = float: [B,HW,4] floats; TI = _Float16: [B,HW,8] halves (the fp16 forward's flow maps), written as TO
+template <typename TI, typename TO>
 __global__ void __launch_bounds__(VV_WG)
-out4_to_nchw_kernel(const int B, const int HW, const int oc, const float* __restrict__ out4, float* __restrict__ dst,
+out4_to_nchw_kernel(const int B, const int HW, const int oc, const TI* __restrict__ out4, TO* __restrict__ dst,
                     const int Ctot, const int choff) {
+  constexpr int CS = std::is_same<TI, float>::value ? 4 : 8;
   const int64_t e = (int64_t)blockIdx.x * VV_WG + threadIdx.x;
   if (e >= (int64_t)B * HW) return;
   const int64_t b = e / HW, pix = e % HW;
-  const float4 v = *reinterpret_cast<const float4*>(out4 + e * 4);
+  const float4 v = vv_ld4(out4 + e * CS);
   const float vv[4] = {v.x, v.y, v.z, v.w};
-  for (int c = 0; c < oc; ++c) dst[(b * Ctot + choff + c) * HW + pix] = vv[c];
+  for (int c = 0; c < oc; ++c) dst[(b * Ctot + choff + c) * HW + pix] = (TO)vv[c];
 }
 __global__ void __launch_bounds__(VV_WG)
 nchw_to_out4_kernel(const int B, const int HW, const int oc, const float* __restrict__ src, const int Ctot,
@@ -1576,8 +1579,21 @@ extern "C" int vv_nchw_to_nhwc(int32_t B, int32_t C, int32_t HW, const float* sr
 extern "C" int vv_out4_to_nchw(int32_t B, int32_t HW, int32_t oc, const float* out4, float* dst, int32_t Ctot,
                                int32_t choff, vv_stream stream) {
   if (!out4 || !dst || oc > 4) return VV_ERR_BAD_ARG;
-  VV_LAUNCH(out4_to_nchw_kernel, dim3(nblocks((int64_t)B * HW)), dim3(VV_WG), 0, (hipStream_t)stream, B, HW, oc,
+  VV_LAUNCH((out4_to_nchw_kernel<float, float>), dim3(nblocks((int64_t)B * HW)), dim3(VV_WG), 0, (hipStream_t)stream, B, HW, oc,
                      out4, dst, Ctot, choff);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+extern "C" int vv_out8_to_nchw_f16(int32_t B, int32_t HW, int32_t oc, const uint16_t* out8, void* dst, int32_t dst_f16,
+                                   int32_t Ctot, int32_t choff, vv_stream stream) {
+  if (!out8 || !dst || oc > 4) return VV_ERR_BAD_ARG;
+  const vv_h* src = reinterpret_cast<const vv_h*>(out8);
+  if (dst_f16)
+    VV_LAUNCH((out4_to_nchw_kernel<vv_h, vv_h>), dim3(nblocks((int64_t)B * HW)), dim3(VV_WG), 0, (hipStream_t)stream, B, HW, oc,
+              src, reinterpret_cast<vv_h*>(dst), Ctot, choff);
+  else
+    VV_LAUNCH((out4_to_nchw_kernel<vv_h, float>), dim3(nblocks((int64_t)B * HW)), dim3(VV_WG), 0, (hipStream_t)stream, B, HW, oc,
+              src, reinterpret_cast<float*>(dst), Ctot, choff);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

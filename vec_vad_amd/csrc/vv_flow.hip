@@ -104,10 +104,11 @@ correlation_k1_kernel(const float* __restrict__ in1, const float* __restrict__ i
 // Zero padding = LDS slots that are never written (zero-filled once); a displaced row that lies outside the image is all
 // padding, its wave skips the arithmetic and stores zeros.  58 KB of LDS and <= 128 registers: two workgroups per CU, the next
 // chunk's global loads fly (in registers) under the multiply-adds.  Offsets are arithmetic in (thread, item): no private arrays.
-template <int W_>
+// T = _Float16: fp16 maps widened on load, the same fp32 arithmetic, the output rounded, LeakyReLU'd and rounded (vv_act_out).
+template <int W_, typename T = float>
 __global__ void __launch_bounds__(VV_WG, 2)
-correlation_nhwc_kernel(const float* __restrict__ f1, const float* __restrict__ f2, const int cs, const int C,
-                        const int H, float* __restrict__ out, const int ocs, const int ocoff, const float slope,
+correlation_nhwc_kernel(const T* __restrict__ f1, const T* __restrict__ f2, const int cs, const int C,
+                        const int H, T* __restrict__ out, const int ocs, const int ocoff, const float slope,
                         const int NG) {
   constexpr int D = 21, MD = 20, CK = 16, NC4 = CK / 4;
   constexpr int DPW = 128 / W_;                 // row displacements per wave
@@ -130,8 +131,8 @@ correlation_nhwc_kernel(const float* __restrict__ f1, const float* __restrict__ 
   const int li = lane % LPD, j = li % NJ, par = li / NJ;
   const int slot = wave * DPW + lane / LPD;
   const int ti = grp * DYB + slot;              // row displacement index of this thread
-  const float* p1 = f1 + (int64_t)b * H * W_ * cs;
-  const float* p2 = f2 + (int64_t)b * H * W_ * cs;
+  const T* p1 = f1 + (int64_t)b * H * W_ * cs;
+  const T* p2 = f2 + (int64_t)b * H * W_ * cs;
 
   for (int e = tid; e < F1SZ + DYB * F2SZ; e += VV_WG) cl[e] = make_float4(0.f, 0.f, 0.f, 0.f);
 
@@ -154,8 +155,8 @@ correlation_nhwc_kernel(const float* __restrict__ f1, const float* __restrict__ 
       const int c4 = rem % NC4, x = rem / NC4;
       int yy = row == 0 ? y : y + 2 * (grp * DYB + row - 1 - MD / 2);
       yy = min(max(yy, 0), H - 1);
-      const float* src = (row == 0 ? p1 : p2) + ((int64_t)yy * W_ + x) * cs + c4 * 4 + c0;
-      r[k] = *reinterpret_cast<const float4*>(src);
+      const T* src = (row == 0 ? p1 : p2) + ((int64_t)yy * W_ + x) * cs + c4 * 4 + c0;
+      r[k] = vv_ld4(src);
     });
   };
   auto commit = [&]() {
@@ -231,13 +232,13 @@ correlation_nhwc_kernel(const float* __restrict__ f1, const float* __restrict__ 
   if (ti < D) {
     const float scale = 1.f / (float)C;
     const int x = 4 * j + par;
-    float* o = out + ((int64_t)(b * H + y) * W_ + x) * ocs + ocoff + ti * D;
+    T* o = out + ((int64_t)(b * H + y) * W_ + x) * ocs + ocoff + ti * D;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       float v = (aa[k].x + aa[k].y) * scale;
-      o[k] = v > 0.f ? v : v * slope;
+      o[k] = vv_act_out<T>(v, slope);
       v = (ab[k].x + ab[k].y) * scale;
-      o[2 * ocs + k] = v > 0.f ? v : v * slope;
+      o[2 * ocs + k] = vv_act_out<T>(v, slope);
     }
   }
 }
@@ -365,19 +366,19 @@ extern "C" int vv_correlation_fwd(const float* in1, const float* in2, float* out
   return VV_OK;
 }
 
-template <int W_>
-static int launch_corr_nhwc(const float* f1, const float* f2, int cs, int B, int C, int H, float* out, int ocs, int ocoff,
+template <int W_, typename T = float>
+static int launch_corr_nhwc(const T* f1, const T* f2, int cs, int B, int C, int H, T* out, int ocs, int ocoff,
                             float slope, hipStream_t st) {
   constexpr int DYB = 4 * (128 / W_), NC4 = 4;          // 16-channel chunks: the kernel's CK / 4
   constexpr int QS = ((W_ + 40 + 3) / 4 + 15) / 16 * 16, Q1 = (W_ / 4 + 15) / 16 * 16;
   constexpr size_t bytes = (size_t)(NC4 * (4 * Q1 + 1) + DYB * NC4 * (4 * QS + 1)) * 16;
   {   // idempotent and cheap: set on every call rather than remembering it in a static
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(correlation_nhwc_kernel<W_>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(correlation_nhwc_kernel<W_, T>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return VV_HIP_STATUS(e);
   }
   const int NG = (21 + DYB - 1) / DYB;
-  VV_LAUNCH(correlation_nhwc_kernel<W_>, dim3(H * NG, B), dim3(VV_WG), bytes, st, f1, f2, cs, C, H, out, ocs, ocoff,
+  VV_LAUNCH((correlation_nhwc_kernel<W_, T>), dim3(H * NG, B), dim3(VV_WG), bytes, st, f1, f2, cs, C, H, out, ocs, ocoff,
             slope, NG);
   VV_CHECK_LAUNCH();
   return VV_OK;
@@ -393,6 +394,21 @@ extern "C" int vv_correlation_nhwc(const float* f1, const float* f2, int32_t cst
   if (W == 128) return launch_corr_nhwc<128>(f1, f2, cstride, B, C, H, out, out_cstride, out_coff, slope, st);
   if (W == 64) return launch_corr_nhwc<64>(f1, f2, cstride, B, C, H, out, out_cstride, out_coff, slope, st);
   return VV_ERR_UNSUPPORTED;   /* other widths: vv_correlation_fwd (generic, NCHW) */
+}
+
+extern "C" int vv_correlation_nhwc_f16(const uint16_t* f1, const uint16_t* f2, int32_t cstride, int32_t B, int32_t C, int32_t H,
+                                       int32_t W, uint16_t* out, int32_t out_cstride, int32_t out_coff, float slope,
+                                       vv_stream stream) {
+  if (!f1 || !f2 || !out || B <= 0 || H <= 0) return VV_ERR_BAD_ARG;
+  if (C % 16 || cstride % 8 || cstride < C) return VV_ERR_UNSUPPORTED;
+  if (((uintptr_t)f1 | (uintptr_t)f2) & 15) return VV_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const vv_h* a = reinterpret_cast<const vv_h*>(f1);
+  const vv_h* b = reinterpret_cast<const vv_h*>(f2);
+  vv_h* o = reinterpret_cast<vv_h*>(out);
+  if (W == 128) return launch_corr_nhwc<128, vv_h>(a, b, cstride, B, C, H, o, out_cstride, out_coff, slope, st);
+  if (W == 64) return launch_corr_nhwc<64, vv_h>(a, b, cstride, B, C, H, o, out_cstride, out_coff, slope, st);
+  return VV_ERR_UNSUPPORTED;
 }
 
 extern "C" int vv_resample2d_fwd(const float* img, const float* flow, float* out, int32_t B, int32_t C, int32_t H,

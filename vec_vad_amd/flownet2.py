@@ -9,7 +9,11 @@ and the plumbing between the sub-networks (input normalisation, x4 flow up-sampl
 NHWC kernels (``vv_flownet_prep / vv_warp_pack12 / vv_fusion_pack11``).  No torch.nn op, no ATen kernel between input and
 output, no fallback.
 
-``with_bn`` must be False and ``fp16`` False (what VEC_VAD instantiates, flownet2.py:12-17).
+``with_bn`` must be False (what VEC_VAD instantiates, flownet2.py:12-17).  ``fp16=True`` runs the same graph on fp16
+activations ("fp16 storage fp32 math", FlowNet2_src/main.py:123-125): parameters stay fp32 in the module (state_dict and checkpoint
+loading are unchanged) and are rounded to fp16 once, when their panels are packed; every conv / deconv runs on fp16 MFMA
+(``vv_conv2d_f16``) with fp32 accumulation, the native ops and the plumbing widen fp16 inputs, compute in fp32 and round where
+the half graph materialises a tensor (no Winograd in this mode).
 """
 import os
 import ctypes as C
@@ -38,6 +42,15 @@ def _c16(c):
 
 def _c32(c):
     return (c + 31) // 32 * 32
+
+
+def _c8(c):
+    return (c + 7) // 8 * 8
+
+
+def _cs(c, dtype):
+    """channel stride of an NHWC activation buffer: 16-byte pixels groups (4 floats / 8 halves)."""
+    return _c8(c) if dtype == torch.float16 else _c4(c)
 
 
 def conv(in_channels, out_channels, kernel_size=3, stride=1, bias=True, with_bn=False, with_relu=True):
@@ -83,13 +96,14 @@ class _Pool:
     def end(self):
         self.cur = None
 
-    def take(self, shape, device):
+    def take(self, shape, device, dtype=torch.float32):
         if self.cur is None:
-            return torch.zeros(shape, device=device, dtype=torch.float32)
-        if self.i < len(self.cur) and tuple(self.cur[self.i].shape) == tuple(shape) and self.cur[self.i].device == device:
-            t = self.cur[self.i]
+            return torch.zeros(shape, device=device, dtype=dtype)
+        c = self.cur[self.i] if self.i < len(self.cur) else None
+        if c is not None and tuple(c.shape) == tuple(shape) and c.device == device and c.dtype == dtype:
+            t = c
         else:
-            t = torch.zeros(shape, device=device, dtype=torch.float32)
+            t = torch.zeros(shape, device=device, dtype=dtype)
             del self.cur[self.i:]
             self.cur.append(t)
         self.i += 1
@@ -100,20 +114,26 @@ _ACTIVE_POOL = [None]
 
 
 class _Buf:
-    """NHWC activation buffer [B,H,W,ceil4(C)] (zero initialised so pad channels are finite)."""
+    """NHWC activation buffer [B,H,W,ceil4(C)] fp32 or [B,H,W,ceil8(C)] fp16 (zero initialised so pad channels are finite)."""
 
-    def __init__(self, B, H, W, C, device):
-        self.B, self.H, self.W, self.C, self.cs = B, H, W, C, _c4(C)
+    def __init__(self, B, H, W, C, device, dtype=torch.float32):
+        self.B, self.H, self.W, self.C, self.cs = B, H, W, C, _cs(C, dtype)
         pool = _ACTIVE_POOL[0]
         shape = (B, H, W, self.cs)
-        self.t = pool.take(shape, torch.device(device)) if pool is not None else \
-            torch.zeros(shape, device=device, dtype=torch.float32)
+        self.t = pool.take(shape, torch.device(device), dtype) if pool is not None else \
+            torch.zeros(shape, device=device, dtype=dtype)
 
     def view(self, coff=0):
         return L.View(self.t.data_ptr(), 0, self.cs, coff)
 
-    def nchw(self, c0=0, c1=None):
+    def nchw(self, c0=0, c1=None, out_dtype=torch.float32):
         c1 = self.C if c1 is None else c1
+        if self.t.dtype == torch.float16 and self.cs == 8 and c0 == 0 and self.t.is_cuda:
+            out = torch.empty(self.B, c1, self.H, self.W, device=self.t.device, dtype=out_dtype)
+            L.check(L.lib().vv_out8_to_nchw_f16(self.B, self.H * self.W, c1, self.t.data_ptr(), out.data_ptr(),
+                                                1 if out_dtype == torch.float16 else 0, c1, 0,
+                                                torch.cuda.current_stream(self.t.device).cuda_stream), 'out8_to_nchw_f16')
+            return out
         if self.cs == 4 and c0 == 0 and self.t.is_cuda:
             # (the two-channel flow maps: a first-party launch, so a captured forward holds no framework kernel)
             out = torch.empty(self.B, c1, self.H, self.W, device=self.t.device, dtype=torch.float32)
@@ -272,6 +292,9 @@ class _Runner:
             m, slope = layer, 1.0
         de = isinstance(m, nn.ConvTranspose2d)
         stream = torch.cuda.current_stream(src.t.device).cuda_stream
+        if src.t.dtype == torch.float16:
+            assert dst.t.dtype == torch.float16
+            return self._launch_f16(m, de, slope, src, dst, dst_coff, stream)
         if m.out_channels == 2 and self._flow_head(m, de, src, dst, dst_coff, slope, stream):
             return dst
         if not de and self._rowk(m, src, dst, dst_coff, slope, stream):
@@ -315,6 +338,112 @@ class _Runner:
         return dst
 
 
+    # ---- fp16 activations: the panels hold the .half()-rounded parameters, cached apart from the fp32 ones
+    def _cached(self, key, m, make):
+        ver = (m.weight.data_ptr(), m.weight._version, None if m.bias is None else (m.bias.data_ptr(), m.bias._version))
+        ent = self.cache.get(key)
+        if ent is None or ent[0] != ver:
+            ent = (ver, make())
+            self.cache[key] = ent
+        return ent[1]
+
+    def _bias16(self, m):
+        if m.bias is None:
+            return None
+        return self._cached(('f16bias', id(m)), m, lambda: m.bias.detach().half().float().contiguous()).data_ptr()
+
+    def _launch_f16(self, m, de, slope, src, dst, dst_coff, stream):
+        lib = self.lib
+        bias = self._bias16(m)
+        assert m.in_channels == src.C, (m.in_channels, src.C)
+        if m.out_channels == 2 and de and m.in_channels == 2:
+            assert m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)
+            assert (dst.H, dst.W) == (2 * src.H, 2 * src.W) and dst_coff + 2 <= dst.cs
+            w = self._cached(('f16c2', id(m)), m, lambda: m.weight.detach().half().float().contiguous())
+            L.check(lib.vv_deconv4x4_c2_f16(src.t.data_ptr(), src.cs, src.B, src.H, src.W, w.data_ptr(), bias, slope,
+                                            dst.t.data_ptr(), dst.cs, dst_coff, stream), 'deconv4x4_c2_f16')
+            return dst
+        if m.out_channels == 2 and not de and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1):
+            assert (dst.H, dst.W) == (src.H, src.W) and dst_coff + 2 <= dst.cs
+
+            def make_n2():
+                w = m.weight.detach().half().float()                     # [2][Cin][3][3]
+                cin = w.shape[1]
+                cp = _c32(cin)
+                wp = torch.zeros(2, cp, 3, 3, device=w.device, dtype=torch.float32)
+                wp[:, :cin] = w
+                return wp.permute(2, 3, 1, 0).reshape(9, cp // 4, 4, 2).permute(0, 1, 3, 2).contiguous()
+            wq = self._cached(('f16n2', id(m)), m, make_n2)
+            L.check(lib.vv_conv3x3_n2_f16(src.t.data_ptr(), src.cs, src.B, src.H, src.W, m.in_channels, wq.data_ptr(), wq.shape[1],
+                                          bias, slope, dst.t.data_ptr(), dst.cs, dst_coff, stream), 'conv3x3_n2_f16')
+            return dst
+        R = m.kernel_size[0]
+        stride = m.stride[0]
+        N, NP = m.out_channels, _c32(m.out_channels)
+        if not de and (R, stride, src.cs) in ((7, 2, 8), (3, 1, 8)) and m.kernel_size[1] == R and src.C <= 8 and \
+                os.environ.get('VV_FN2_ROWK', '1') != '0':
+            # row-K (few-channel first layers): K = the (kx, c) run of 8-half pixels under one filter row, padded to 16
+            KF = (R * 8 + 15) // 16 * 16
+
+            def make_rowk():
+                w = m.weight.detach().float()                                  # [N][Cin][ky][kx]
+                wr = torch.zeros(N, KF, R, device=w.device, dtype=torch.float32)
+                wr[:, :R * 8].view(N, R, 8, R)[:, :, :m.in_channels] = w.permute(0, 3, 1, 2)      # [N][kx][c][ky]
+                packed = torch.empty(R * KF * NP, device=w.device, dtype=torch.float16)
+                L.check(lib.vv_pack_conv2d_f16(wr.data_ptr(), packed.data_ptr(), R, KF, KF, N, NP, 0, stream), 'pack_conv2d_f16 (row-K)')
+                return packed
+            packed = self._cached(('f16rowk', id(m)), m, make_rowk)
+            pad = (R - 1) // 2
+            OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
+            assert (dst.H, dst.W) == (OH, OW) and dst_coff + N <= dst.cs
+            p = L.Conv2dParams(2, R, stride, src.B, src.H, src.W, KF, KF, N, NP, src.view(0), packed.data_ptr(), bias, slope, 0,
+                               dst.view(dst_coff))
+            L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 row-K %dx%d s%d %d->%d' % (R, R, stride, m.in_channels, N))
+            return dst
+        K = m.in_channels
+        KP = _c32(K)
+        taps = m.kernel_size[0] * m.kernel_size[1]
+
+        def make_panel():
+            w = m.weight.detach().contiguous().float()
+            packed = torch.empty(taps * KP * NP, device=w.device, dtype=torch.float16)
+            L.check(lib.vv_pack_conv2d_f16(w.data_ptr(), packed.data_ptr(), taps, K, KP, N, NP, 1 if de else 0, stream),
+                    'pack_conv2d_f16')
+            return packed
+        packed = self._cached(('f16', id(m)), m, make_panel)
+        if de:
+            assert m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)
+            OH, OW = 2 * src.H, 2 * src.W
+            R, stride = 4, 2
+        else:
+            pad = (R - 1) // 2
+            assert m.padding == (pad, pad)
+            OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
+        assert (dst.H, dst.W) == (OH, OW), ((dst.H, dst.W), (OH, OW))
+        assert dst_coff + N <= dst.cs
+        # split-K on the tiny-M / huge-K levels, the policy of the fp32 path
+        lh, lw = (src.H, src.W) if de else (OH, OW)
+        wgs = src.B * (4 if de else 1) * (NP // (64 if (NP % 64 == 0 and N > 32) else 32)) * ((lh + 7) // 8) * ((lw + 31) // 32)
+        nchunk = KP // (16 if (not de and stride == 2) else 32)
+        ks = 1
+        if wgs < 256 and nchunk >= 4:
+            ks = max(1, min(nchunk // 2, _KS_TARGET // wgs, 16))
+        kind = 1 if de else 0
+        if ks > 1:
+            M = src.B * OH * OW
+            ws = torch.empty(ks * M * NP, device=src.t.device, dtype=torch.float32)
+            p = L.Conv2dParams(kind, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(), None, 1.0, ks,
+                               L.View(ws.data_ptr(), 0, NP, 0))
+            L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 split-k')
+            L.check(lib.vv_conv2d_splitk_finish_f16(ws.data_ptr(), ks, M, N, NP, bias, slope, dst.t.data_ptr(), dst.cs, dst_coff,
+                                                    stream), 'conv2d_f16 split-k finish')
+            return dst
+        p = L.Conv2dParams(kind, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(), bias, slope, 0,
+                           dst.view(dst_coff))
+        L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 %dx%d s%d %d->%d' % (R, R, stride, K, N))
+        return dst
+
+
 def _upsample4(x_nchw, bilinear, scale, align_corners=False):
     """nn.Upsample(scale_factor=4) on NCHW planes times ``scale``: nearest, bilinear, or bilinear with align_corners=True."""
     x = x_nchw.contiguous()
@@ -327,7 +456,7 @@ def _upsample4(x_nchw, bilinear, scale, align_corners=False):
 
 def _to_buf(x_nchw, device=None):
     B, Cc, H, W = x_nchw.shape
-    b = _Buf(B, H, W, Cc, x_nchw.device)
+    b = _Buf(B, H, W, Cc, x_nchw.device, x_nchw.dtype if x_nchw.dtype == torch.float16 else torch.float32)
     b.t[..., :Cc] = x_nchw.permute(0, 2, 3, 1)
     return b
 
@@ -337,11 +466,11 @@ class _Decoder:
 
     @staticmethod
     def run(net, run, out_conv6, cat5, cat4, cat3, cat2, inter=False):
-        dev = out_conv6.t.device
+        dev, dt = out_conv6.t.device, out_conv6.t.dtype
         B = out_conv6.B
 
         def flow_of(pred, src):
-            f = _Buf(B, src.H, src.W, 2, dev)
+            f = _Buf(B, src.H, src.W, 2, dev, dt)
             run(pred, src, f)
             return f
 
@@ -353,7 +482,7 @@ class _Decoder:
             src = cat
             if inter:
                 ic = getattr(net, 'inter_conv%d' % lvl)
-                src = _Buf(B, cat.H, cat.W, ic[0].out_channels, dev)
+                src = _Buf(B, cat.H, cat.W, ic[0].out_channels, dev, dt)
                 run(ic, cat, src)
             flow = flow_of(getattr(net, 'predict_flow%d' % lvl), src)
             run(getattr(net, 'upsampled_flow%d_to_%d' % (lvl, lvl - 1)), flow, nxt, nxt.C - 2)
@@ -361,7 +490,7 @@ class _Decoder:
             run(d, cat, nxt, nxt.C - 2 - d[0].out_channels)
         src = cat2
         if inter:
-            src = _Buf(B, cat2.H, cat2.W, net.inter_conv2[0].out_channels, dev)
+            src = _Buf(B, cat2.H, cat2.W, net.inter_conv2[0].out_channels, dev, dt)
             run(net.inter_conv2, cat2, src)
         return flow_of(net.predict_flow2, src)
 
@@ -372,8 +501,9 @@ _TOWER_STREAMS = {}
 class FlowNetC(nn.Module):
     def __init__(self, with_bn=False, fp16=False):
         super().__init__()
-        assert not with_bn and not fp16
-        self.with_bn, self.fp16 = with_bn, fp16
+        if with_bn:
+            raise NotImplementedError('FlowNet2 is built with_bn=False in VEC_VAD (flownet2.py:13)')
+        self.with_bn, self.fp16 = with_bn, bool(fp16)
         self.conv1 = conv(3, 64, kernel_size=7, stride=2)
         self.conv2 = conv(64, 128, kernel_size=5, stride=2)
         self.conv3 = conv(128, 256, kernel_size=5, stride=2)
@@ -404,7 +534,8 @@ class FlowNetC(nn.Module):
     def run(self, run, img0, img1):
         """img0 / img1: _Buf [B,H,W,3].  Returns flow2 _Buf [B,H/4,W/4,2] (FlowNetC.py:75-132)."""
         dev, B, H, W = img0.t.device, img0.B, img0.H, img0.W
-        nb = lambda h, w, c: _Buf(B, h, w, c, dev)
+        dt = img0.t.dtype
+        nb = lambda h, w, c: _Buf(B, h, w, c, dev, dt)
         cat2 = nb(H // 4, W // 4, 194)
         c1a, c1b = nb(H // 2, W // 2, 64), nb(H // 2, W // 2, 64)
         c2b = nb(H // 4, W // 4, 128)
@@ -428,10 +559,13 @@ class FlowNetC(nn.Module):
         in31 = nb(H // 8, W // 8, 473)
         # corr + corr_activation + the cat with conv_redir (FlowNetC.py:88-96,120): one launch on the NHWC maps, written
         # into channels [32, 473) of conv3_1's input; widths the specialised kernel does not cover take the generic op
-        rc = L.lib().vv_correlation_nhwc(c3a.t.data_ptr(), c3b.t.data_ptr(), c3a.cs, B, 256, H // 8, W // 8, in31.t.data_ptr(),
-                                         in31.cs, 32, 0.1, torch.cuda.current_stream(dev).cuda_stream)
+        corr_nhwc = L.lib().vv_correlation_nhwc_f16 if dt == torch.float16 else L.lib().vv_correlation_nhwc
+        rc = corr_nhwc(c3a.t.data_ptr(), c3b.t.data_ptr(), c3a.cs, B, 256, H // 8, W // 8, in31.t.data_ptr(),
+                       in31.cs, 32, 0.1, torch.cuda.current_stream(dev).cuda_stream)
         if rc == 3:       # VV_ERR_UNSUPPORTED
-            corr = correlation(c3a.nchw(), c3b.nchw(), 20, 1, 20, 1, 2, 1)
+            corr = correlation(c3a.nchw().float(), c3b.nchw().float(), 20, 1, 20, 1, 2, 1)
+            if dt == torch.float16:      # (the half graph: the op's fp32 result rounded, LeakyReLU on the rounded value)
+                corr = corr.half()
             in31.t[..., 32:473] = torch.where(corr > 0, corr, corr * 0.1).permute(0, 2, 3, 1)
         else:
             L.check(rc, 'correlation_nhwc')
@@ -492,7 +626,7 @@ class FlowNetS(nn.Module):
     def run(self, run, x):
         """x: _Buf [B,H,W,12] (FlowNetS.py:63-96)."""
         dev, B, H, W = x.t.device, x.B, x.H, x.W
-        nb = lambda h, w, c: _Buf(B, h, w, c, dev)
+        nb = lambda h, w, c: _Buf(B, h, w, c, dev, x.t.dtype)
         c1 = nb(H // 2, W // 2, 64)
         run(self.conv1, x, c1)
         cat2 = nb(H // 4, W // 4, 194)
@@ -547,7 +681,7 @@ class FlowNetSD(nn.Module):
     def run(self, run, x):
         """x: _Buf [B,H,W,6] (FlowNetSD.py:60-103)."""
         dev, B, H, W = x.t.device, x.B, x.H, x.W
-        nb = lambda h, w, c: _Buf(B, h, w, c, dev)
+        nb = lambda h, w, c: _Buf(B, h, w, c, dev, x.t.dtype)
         c0 = nb(H, W, 64)
         run(self.conv0, x, c0)
         t1, c1 = nb(H // 2, W // 2, 64), nb(H // 2, W // 2, 128)
@@ -589,7 +723,7 @@ class FlowNetFusion(nn.Module):
     def run(self, run, x):
         """x: _Buf [B,H,W,11] -> full-resolution flow _Buf [B,H,W,2] (FlowNetFusion.py:43-64)."""
         dev, B, H, W = x.t.device, x.B, x.H, x.W
-        nb = lambda h, w, c: _Buf(B, h, w, c, dev)
+        nb = lambda h, w, c: _Buf(B, h, w, c, dev, x.t.dtype)
         cat0 = nb(H, W, 82)
         run(self.conv0, x, cat0, 0)
         t1, cat1 = nb(H // 2, W // 2, 64), nb(H // 2, W // 2, 162)
@@ -618,8 +752,9 @@ class FlowNet2(nn.Module):
         authors ran (README.md:10,64) and mean align_corners=False under every torch >= 0.4 -- which is what importing the
         reference today computes and therefore the default; pass True to reproduce the published checkpoint's behaviour."""
         super().__init__()
-        if with_bn or fp16:
-            raise NotImplementedError('VEC_VAD instantiates FlowNet2() with_bn=False, fp16=False (calc_optical_flow.py:15)')
+        if with_bn:
+            raise NotImplementedError('VEC_VAD instantiates FlowNet2() with_bn=False (calc_optical_flow.py:15)')
+        self.fp16 = bool(fp16)
         self.upsample_align_corners = bool(upsample_align_corners)
         self.with_bn, self.div_flow, self.rgb_max = with_bn, div_flow, rgb_max
         self.grads = {} if grads is None else grads
@@ -645,7 +780,8 @@ class FlowNet2(nn.Module):
 
     @torch.no_grad()
     def forward(self, inputs):
-        """inputs [B,3,2,H,W] fp32 in 0..rgb_max (H, W multiples of 64) -> flow [B,2,H,W]."""
+        """inputs [B,3,2,H,W] in 0..rgb_max (H, W multiples of 64) -> flow [B,2,H,W].  fp32 mode: fp32 flow.  fp16 mode: an
+        fp16-valued flow, returned as float16 for a float16 input and widened to float32 otherwise."""
         if not inputs.is_cuda:
             raise L.VecVadHipError('FlowNet2 runs on the GPU only (no CPU fallback)')
         if inputs.shape[3] % 64 or inputs.shape[4] % 64:
@@ -653,6 +789,7 @@ class FlowNet2(nn.Module):
         if self._runner is None:
             self._runner = _Runner()
         run = self._runner
+        self._out_dtype = torch.float16 if (self.fp16 and inputs.dtype == torch.float16) else torch.float32
         inputs = inputs.float()
         self._pool.begin((tuple(inputs.shape), str(inputs.device)))
         _ACTIVE_POOL[0] = self._pool
@@ -671,17 +808,21 @@ class FlowNet2(nn.Module):
         st = torch.cuda.current_stream(dev).cuda_stream
         inputs = inputs.contiguous()
         B, _, _, H, W = inputs.shape
-        x6, img0, img1 = _Buf(B, H, W, 6, dev), _Buf(B, H, W, 3, dev), _Buf(B, H, W, 3, dev)
+        f16 = self.fp16
+        dt = torch.float16 if f16 else torch.float32
+        x6, img0, img1 = _Buf(B, H, W, 6, dev, dt), _Buf(B, H, W, 3, dev, dt), _Buf(B, H, W, 3, dev, dt)
         ws = self._pool.take((int(lib.vv_flownet_prep_workspace_bytes(B)) // 4,), dev)
-        L.check(lib.vv_flownet_prep(inputs.data_ptr(), B, H, W, float(self.rgb_max), ws.data_ptr(), ws.numel() * 4,
-                                    x6.t.data_ptr(), img0.t.data_ptr(), img1.t.data_ptr(), st), 'flownet_prep')
+        L.check((lib.vv_flownet_prep_f16 if f16 else lib.vv_flownet_prep)(
+            inputs.data_ptr(), B, H, W, float(self.rgb_max), ws.data_ptr(), ws.numel() * 4, x6.t.data_ptr(), img0.t.data_ptr(),
+            img1.t.data_ptr(), st), 'flownet_prep')
         bil = 2 if self.upsample_align_corners else 1
 
         def warp_pack(flow2):
             """[x, resample(img1, flow), flow / div_flow, |img0 - warped|], flow = upsample x4(flow2 * div_flow) (flownet2.py:76-86)."""
-            out = _Buf(B, H, W, 12, dev)
-            L.check(lib.vv_warp_pack12(x6.t.data_ptr(), img1.t.data_ptr(), flow2.t.data_ptr(), flow2.cs, B, H, W, bil,
-                                       float(self.div_flow), float(self.div_flow), out.t.data_ptr(), st), 'warp_pack12')
+            out = _Buf(B, H, W, 12, dev, dt)
+            L.check((lib.vv_warp_pack12_f16 if f16 else lib.vv_warp_pack12)(
+                x6.t.data_ptr(), img1.t.data_ptr(), flow2.t.data_ptr(), flow2.cs, B, H, W, bil, float(self.div_flow),
+                float(self.div_flow), out.t.data_ptr(), st), 'warp_pack12')
             return out
 
         # FlowNetSD reads only x (flownet2.py:96-98): it runs on a second HIP stream beside the FlowNetC -> S1 -> S2 chain and
@@ -716,9 +857,12 @@ class FlowNet2(nn.Module):
             sd_flow2 = self.flownets_d.run(run, x6)
         else:
             main.wait_stream(side)
-        cat3 = _Buf(B, H, W, 11, dev)
-        L.check(lib.vv_fusion_pack11(x6.t.data_ptr(), img1.t.data_ptr(), s2_flow2.t.data_ptr(), s2_flow2.cs, sd_flow2.t.data_ptr(),
-                                     sd_flow2.cs, B, H, W, float(self.div_flow), cat3.t.data_ptr(), st), 'fusion_pack11')
+        cat3 = _Buf(B, H, W, 11, dev, dt)
+        L.check((lib.vv_fusion_pack11_f16 if f16 else lib.vv_fusion_pack11)(
+            x6.t.data_ptr(), img1.t.data_ptr(), s2_flow2.t.data_ptr(), s2_flow2.cs, sd_flow2.t.data_ptr(), sd_flow2.cs, B, H, W,
+            float(self.div_flow), cat3.t.data_ptr(), st), 'fusion_pack11')
+        if f16:
+            return self.flownetfusion.run(run, cat3).nchw(0, 2, out_dtype=self._out_dtype)
         return self.flownetfusion.run(run, cat3).nchw(0, 2)
 
     @torch.no_grad()
