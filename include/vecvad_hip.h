@@ -41,7 +41,10 @@ enum vv_in_mode {
   VV_IN_ACT = 1,   /* relu(a[c]*x + b[c])      nn.BatchNorm2d + nn.ReLU  model/unet.py:11-12,14-15 */
   VV_IN_POOL = 2,  /* 2x2 max of relu(a*x+b)   + nn.MaxPool2d(2)         model/unet.py:38          */
   VV_IN_CAT = 3,   /* [relu(a*x0+b) , x1]      torch.cat([x2, x1], 1)    model/unet.py:59          */
-  VV_IN_CUBE = 4   /* channel gather through chmap (frame erasure)       model/unet.py:178-183     */
+  VV_IN_CUBE = 4,  /* channel gather through chmap (frame erasure)       model/unet.py:178-183     */
+  VV_IN_BNBWD = 5  /* BatchNorm + ReLU backward on load: src0 = dA, src1 = z (the layer's pre-BN conv output, plain),
+                      a = the layer's vv_bn_bwd_sums table (group stride ab_gstride):  gk (dA [a z + b > 0] - c1 - xhat c2),
+                      xhat = (z - mean) invstd -- bit-identical to the dy vv_bn_bwd_apply stores.  Per-tile vv_conv_wino only. */
 };
 
 enum vv_conv_kind {
@@ -162,6 +165,11 @@ typedef struct vv_wgrad_params {
   vv_view dy;        /* gradient wrt the conv output (CONV3: HxW; CONVT: 2Hx2W) */
   float* partial;    /* [G][nslab][9][32][32] with nslab = (CinP/32... see vv_wgrad_nslab) */
   int64_t partial_gstride;
+  /* dy_bn != NULL: `dy` holds dA (the gradient wrt relu(bn(z))) and the operand is formed on load as VV_IN_BNBWD does, from dA, z
+   * (dy_z: [B,H,W,Cout] plain) and the vv_bn_bwd_sums table dy_bn (group stride dy_bn_gstride).  VV_CONV3 with the Winograd flag
+   * (pad0 bit 8) only. */
+  vv_view dy_z;
+  const float* dy_bn; int64_t dy_bn_gstride;
 } vv_wgrad_params;
 
 int vv_wgrad_mfma(const vv_wgrad_params* p, vv_stream stream);
@@ -282,6 +290,12 @@ int vv_bn_bwd_nblk(int32_t B, int32_t H, int32_t W, int32_t C);
  * dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)) into p->dz (dz itself is never materialised). */
 int vv_bn_bwd_apply(const vv_bnbwd_params* p, const float* gamma, int64_t param_gstride, float* dgamma, float* dbeta,
                     int64_t grad_gstride, float* scratch /* [G][2][C] */, vv_stream stream);
+/* phase 2 without the apply pass: sums the partials exactly as vv_bn_bwd_apply does, writes dgamma/dbeta and the per-channel table
+ * [G][VV_BNBWD_TAB_ROWS][C] (group stride table_gstride floats) that consumers reading dA and z with VV_IN_BNBWD (data gradient) or
+ * vv_wgrad_params.dy_bn (weight gradient) form dy from.  p->dz is not used; fp32 tensors only, no dpool. */
+#define VV_BNBWD_TAB_ROWS 7   /* rows: a, b, mean, invstd, gk = gamma * invstd, c1 = mean(dz), c2 = mean(dz * xhat) */
+int vv_bn_bwd_sums(const vv_bnbwd_params* p, const float* gamma, int64_t param_gstride, float* dgamma, float* dbeta,
+                   int64_t grad_gstride, float* table, int64_t table_gstride, vv_stream stream);
 
 /* ---- output 1x1 conv + squared error (model/unet.py:63-70 ; train.py:385-392,421-426 ; test.py:330-335) ----
  * out[p][co] = bias[co] + sum_c relu(a*y+b)[p][c] * W[co][c];  score[g][cube] = sum (out - target)^2;

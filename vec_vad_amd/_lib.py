@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get('VV_LIB_PATH') or os.path.join(HERE, 'csrc', 'libvecva
 
 c_i32, c_i64, c_f32, c_f64, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
-IN_PLAIN, IN_ACT, IN_POOL, IN_CAT, IN_CUBE = 0, 1, 2, 3, 4
+IN_PLAIN, IN_ACT, IN_POOL, IN_CAT, IN_CUBE, IN_BNBWD = 0, 1, 2, 3, 4, 5
+BNBWD_TAB_ROWS = 7      # rows of a vv_bn_bwd_sums table: a, b, mean, invstd, gk, c1, c2
 CONV3, CONVT_FWD, CONVT_DGRAD = 0, 1, 2
 CONV_BF16 = 1          # vv_conv_params.pad0 flag (include/vecvad_hip.h VV_CONV_BF16)
 CONV_SRC_BF16 = 2      # VV_CONV_SRC_BF16
@@ -58,7 +59,8 @@ class WgradParams(C.Structure):
                 ('Cin', c_i32), ('CinP', c_i32), ('Cout', c_i32), ('ksplit', c_i32),
                 ('src0', View), ('a', c_vp), ('b', c_vp), ('ab_gstride', c_i64),
                 ('src1', View), ('csplit', c_i32), ('pad0', c_i32), ('chmap', c_vp),
-                ('dy', View), ('partial', c_vp), ('partial_gstride', c_i64)]
+                ('dy', View), ('partial', c_vp), ('partial_gstride', c_i64),
+                ('dy_z', View), ('dy_bn', c_vp), ('dy_bn_gstride', c_i64)]
 
 
 class PackEntry(C.Structure):
@@ -129,6 +131,7 @@ _SIGS = {
     'vv_bn_bwd_reduce': (c_i32, [C.POINTER(BnBwdParams), c_vp]),
     'vv_bn_bwd_nblk': (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     'vv_bn_bwd_apply': (c_i32, [C.POINTER(BnBwdParams), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'vv_bn_bwd_sums': (c_i32, [C.POINTER(BnBwdParams), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'vv_outconv_fwd': (c_i32, [C.POINTER(OutconvParams), c_vp]),
     'vv_outconv_bwd': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
                                c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -916,6 +916,26 @@ class UNetBank:
                     fused_t[u] = sidx
         fused |= set(fused_t.values())
 
+        # VV_FUSE_BN_APPLY: layers whose BatchNorm-backward apply pass is folded into its two consumers -- vv_bn_bwd_sums leaves the
+        # per-channel table, the data gradient (VV_IN_BNBWD, per-tile F(2x2) kernel) and the weight gradient (dy_bn) read dA and z and
+        # form dy on load (bit-identical to the stored dy).  '0' = every layer keeps its apply pass; 'set:2,4,...' = exactly these
+        # (probing).  Candidates: no pooling fan-in (1 / 3 / 5 route dPool), fp32 Winograd path, a data gradient on the per-tile
+        # F(2x2) kernel at 16x16 / 8x8 (or none: layer 0); 7 keeps its pass.  Default = the layers measured faster folded at B = 256
+        # (profiles/README.md): 0, 2, 4.  9 was measured slower (its data gradient loses the two-N-tile form); 8 / 10 / 11 run their
+        # data gradient on F(4x4) there and were not measured folded.
+        fold_env = os.environ.get('VV_FUSE_BN_APPLY', '1').lower()
+        fold_set = {int(t) for t in fold_env[4:].split(',') if t} if fold_env.startswith('set:') else \
+            (set() if fold_env in ('0', 'off') else {0, 2, 4})
+
+        def folded(l):
+            if l.idx not in fold_set or self.cflag or not self.wino or not self.wino_wgrad or l.idx == last.idx:
+                return False
+            if self.dz16 or self.da16 or self.y16 or l.H == 4 or l.cout > 256 or dA_for(l)[1] is not None:
+                return False
+            return l.idx == 0 or (l.H in (16, 8) and not self._w44(B, l, True))
+        fold = {l.idx for l in lay.convs if folded(l)}
+        ws.bntab = {i: f(Ga, L.BNBWD_TAB_ROWS * lay.convs[i].cout) for i in fold}   # one table per folded layer (read on the side stream)
+
         def dgrad_flags(i):
             # pad0 of layer i's data-gradient launch (also decides its tile count: vv_conv_ntiles2)
             dz16 = bool(self.dz16 and len(wplan['c%d' % i]) > 2)
@@ -945,11 +965,20 @@ class UNetBank:
                                self._p(ws.ab[2, i]), self._p(ws.ab[3, i]), abg, dA, dpool, dpg, dzb.data_ptr(), dzb.stride(0),
                                ws.bnpart.data_ptr())
             P.keep.append(bp)
+            fl = i in fold
+            if fl:
+                reuse_wait = ()                    # no dy buffer
             if not (from_outconv or from_dgrad):
                 P.add(lib.vv_bn_bwd_reduce, (C.byref(bp),), 'bn_bwd_reduce%d' % i, wait=reuse_wait)
-            P.add(lib.vv_bn_bwd_apply, (C.byref(bp), pbase + 4 * lay.p['c%d.g' % i][0], U, self._g('c%d.g' % i)[0],
-                                        self._g('c%d.beta' % i)[0], self._g('c%d.g' % i)[1], ws.bnscr.data_ptr()), 'bn_bwd_apply%d' % i,
-                  record='dy%d' % i, wait=reuse_wait if (from_outconv or from_dgrad) else ())
+            if fl:
+                tab = ws.bntab[i]
+                P.add(lib.vv_bn_bwd_sums, (C.byref(bp), pbase + 4 * lay.p['c%d.g' % i][0], U, self._g('c%d.g' % i)[0],
+                                           self._g('c%d.beta' % i)[0], self._g('c%d.g' % i)[1], tab.data_ptr(), tab.stride(0)),
+                      'bn_bwd_sum%d' % i, record='dy%d' % i)
+            else:
+                P.add(lib.vv_bn_bwd_apply, (C.byref(bp), pbase + 4 * lay.p['c%d.g' % i][0], U, self._g('c%d.g' % i)[0],
+                                            self._g('c%d.beta' % i)[0], self._g('c%d.g' % i)[1], ws.bnscr.data_ptr()), 'bn_bwd_apply%d' % i,
+                      record='dy%d' % i, wait=reuse_wait if (from_outconv or from_dgrad) else ())
             # data gradient
             if i > 0:
                 Dl = ws.D[i]
@@ -961,6 +990,9 @@ class UNetBank:
                                   L.view(Dl, l.cin, 0, Dl.stride(0)),
                                   # concat layers: per-tile column sums of the data gradient = the transposed conv's bias gradient
                                   ws.dstats.data_ptr() if l.mode == L.IN_CAT else None)
+                if fl:                             # dy formed on load from dA, z and the layer's table
+                    cp.in_mode, cp.src0, cp.src1 = L.IN_BNBWD, dA, L.view(y, l.cout, 0, y.stride(0))
+                    cp.a, cp.ab_gstride = ws.bntab[i].data_ptr(), ws.bntab[i].stride(0)
                 if l.mode == L.IN_CAT:
                     v0, v1, osplit = dcat_views(l)
                     if osplit:
@@ -987,6 +1019,10 @@ class UNetBank:
             wp = L.WgradParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, ks, s0, a, b, abg, s1, csplit,
                                wflag, chmap,
                                L.View(dzb.data_ptr(), dzb.stride(0), l.cout, 0), ws.wpart.data_ptr() + 4 * woff['c%d' % i], wpg)
+            if fl:
+                # (side stream: dA, z and the table are written once per step, before 'dy%d' is recorded, and not again before wdone)
+                wp.dy, wp.dy_z = dA, L.view(y, l.cout, 0, y.stride(0))
+                wp.dy_bn, wp.dy_bn_gstride = ws.bntab[i].data_ptr(), ws.bntab[i].stride(0)
             P.keep.append(wp)
             P.add(lib.vv_wgrad_bf16 if kw else lib.vv_wgrad_mfma, (C.byref(wp),), 'wgrad%d' % i, stream=1, wait=('dy%d' % i,),
                   record='wdone%d' % i, pwait=('*main',))

@@ -75,6 +75,35 @@ __device__ __forceinline__ float4 vv_act4(float4 v, float4 a, float4 b) {
   v.w = fmaxf(fmaf(a.w, v.w, b.w), 0.f);
   return v;
 }
+// BatchNorm + ReLU backward of 4 channels: dy = gk (d [a y + b > 0] - c1 - xhat c2), xhat = (y - m) i; d = dA, y = z (pre-BN conv
+// output).  The ONE place this expression lives: vv_bn_bwd_apply's store and the consumers forming dy on load (VV_IN_BNBWD,
+// vv_wgrad_params.dy_bn) all call it, so they agree to the bit (including the compiler's fma contraction).
+struct VVBnBwd4 { float4 a, b, m, i, gk, c1, c2; };
+// channels [c, c+4) of a vv_bn_bwd_sums table (rows of C floats: a, b, mean, invstd, gk, c1, c2)
+__device__ __forceinline__ VVBnBwd4 vv_bnbwd_consts(const float* tab, const int C, const int c) {
+  VVBnBwd4 k;
+  k.a = *reinterpret_cast<const float4*>(tab + c);
+  k.b = *reinterpret_cast<const float4*>(tab + C + c);
+  k.m = *reinterpret_cast<const float4*>(tab + 2 * C + c);
+  k.i = *reinterpret_cast<const float4*>(tab + 3 * C + c);
+  k.gk = *reinterpret_cast<const float4*>(tab + 4 * C + c);
+  k.c1 = *reinterpret_cast<const float4*>(tab + 5 * C + c);
+  k.c2 = *reinterpret_cast<const float4*>(tab + 6 * C + c);
+  return k;
+}
+__device__ __forceinline__ float vv_bnbwd1(float d, const float y, const float a, const float b, const float m, const float i,
+                                           const float gk, const float c1, const float c2) {
+  const float z = fmaf(a, y, b);
+  d = z > 0.f ? d : 0.f;
+  const float xh = (y - m) * i;
+  return gk * (d - c1 - xh * c2);
+}
+__device__ __forceinline__ float4 vv_bnbwd4(const float4 d, const float4 y, const VVBnBwd4& k) {
+  return make_float4(vv_bnbwd1(d.x, y.x, k.a.x, k.b.x, k.m.x, k.i.x, k.gk.x, k.c1.x, k.c2.x),
+                     vv_bnbwd1(d.y, y.y, k.a.y, k.b.y, k.m.y, k.i.y, k.gk.y, k.c1.y, k.c2.y),
+                     vv_bnbwd1(d.z, y.z, k.a.z, k.b.z, k.m.z, k.i.z, k.gk.z, k.c1.z, k.c2.z),
+                     vv_bnbwd1(d.w, y.w, k.a.w, k.b.w, k.m.w, k.i.w, k.gk.w, k.c1.w, k.c2.w));
+}
 __device__ __forceinline__ float4 vv_max4(float4 p, float4 q) {
   p.x = fmaxf(p.x, q.x); p.y = fmaxf(p.y, q.y); p.z = fmaxf(p.z, q.z); p.w = fmaxf(p.w, q.w);
   return p;

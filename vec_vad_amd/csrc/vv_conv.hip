@@ -567,6 +567,7 @@ extern "C" int vv_conv_mfma(const vv_conv_params* p, vv_stream stream) {
   if (!p || !p->src0.ptr || !p->w || !p->out.ptr) return VV_ERR_BAD_ARG;
   if (p->G <= 0 || p->B <= 0) return VV_ERR_BAD_ARG;
   if (p->Cout % 32) return VV_ERR_UNSUPPORTED;
+  if (p->in_mode == VV_IN_BNBWD) return VV_ERR_UNSUPPORTED;       // BatchNorm backward on load: vv_conv_wino's per-tile kernel only
   hipStream_t st = (hipStream_t)stream;
   const bool bf = (p->pad0 & VV_CONV_BF16) != 0;
   if (bf && p->CinP % 16) return VV_ERR_BAD_ARG;

@@ -168,12 +168,13 @@ bn_bwd_reduce_kernel(const vv_bnbwd_params p, const int nblk, const int bp, cons
   const float4 a4 = *reinterpret_cast<const float4*>(p.a + abo), b4 = *reinterpret_cast<const float4*>(p.b + abo);
   const float4 m4 = *reinterpret_cast<const float4*>(p.mean + abo), i4 = *reinterpret_cast<const float4*>(p.invstd + abo);
   float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
-  float4 gk = make_float4(0, 0, 0, 0), c1 = gk, c2 = gk;
+  VVBnBwd4 kc;                          // PASS 1: the constants of vv_bnbwd4 (the same values vv_bn_bwd_sums tabulates)
   if constexpr (PASS == 1) {
     const float4 gm = *reinterpret_cast<const float4*>(gamma + (int64_t)g * param_gstride + c);
-    gk = make_float4(gm.x * i4.x, gm.y * i4.y, gm.z * i4.z, gm.w * i4.w);
-    c1 = *reinterpret_cast<const float4*>(scratch + (int64_t)g * 2 * C + c);
-    c2 = *reinterpret_cast<const float4*>(scratch + (int64_t)g * 2 * C + C + c);
+    kc.a = a4; kc.b = b4; kc.m = m4; kc.i = i4;
+    kc.gk = make_float4(gm.x * i4.x, gm.y * i4.y, gm.z * i4.z, gm.w * i4.w);
+    kc.c1 = *reinterpret_cast<const float4*>(scratch + (int64_t)g * 2 * C + c);
+    kc.c2 = *reinterpret_cast<const float4*>(scratch + (int64_t)g * 2 * C + C + c);
   }
 
   const bool y16 = (p.flags & VV_BNBWD_Y_BF16) != 0;
@@ -182,16 +183,15 @@ bn_bwd_reduce_kernel(const vv_bnbwd_params p, const int nblk, const int bp, cons
     return *reinterpret_cast<const float4*>(y + pix * C + c);
   };
   auto one = [&](const int64_t pix, float4 d, const float4 yv) {
-    float4 z;
-    z.x = fmaf(a4.x, yv.x, b4.x); z.y = fmaf(a4.y, yv.y, b4.y); z.z = fmaf(a4.z, yv.z, b4.z); z.w = fmaf(a4.w, yv.w, b4.w);
-    d.x = z.x > 0.f ? d.x : 0.f; d.y = z.y > 0.f ? d.y : 0.f; d.z = z.z > 0.f ? d.z : 0.f; d.w = z.w > 0.f ? d.w : 0.f;
-    const float4 xh = make_float4((yv.x - m4.x) * i4.x, (yv.y - m4.y) * i4.y, (yv.z - m4.z) * i4.z, (yv.w - m4.w) * i4.w);
     if constexpr (PASS == 0) {
+      float4 z;
+      z.x = fmaf(a4.x, yv.x, b4.x); z.y = fmaf(a4.y, yv.y, b4.y); z.z = fmaf(a4.z, yv.z, b4.z); z.w = fmaf(a4.w, yv.w, b4.w);
+      d.x = z.x > 0.f ? d.x : 0.f; d.y = z.y > 0.f ? d.y : 0.f; d.z = z.z > 0.f ? d.z : 0.f; d.w = z.w > 0.f ? d.w : 0.f;
+      const float4 xh = make_float4((yv.x - m4.x) * i4.x, (yv.y - m4.y) * i4.y, (yv.z - m4.z) * i4.z, (yv.w - m4.w) * i4.w);
       s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
       s2.x = fmaf(d.x, xh.x, s2.x); s2.y = fmaf(d.y, xh.y, s2.y); s2.z = fmaf(d.z, xh.z, s2.z); s2.w = fmaf(d.w, xh.w, s2.w);
     } else {
-      d.x = gk.x * (d.x - c1.x - xh.x * c2.x); d.y = gk.y * (d.y - c1.y - xh.y * c2.y);
-      d.z = gk.z * (d.z - c1.z - xh.z * c2.z); d.w = gk.w * (d.w - c1.w - xh.w * c2.w);
+      d = vv_bnbwd4(d, yv, kc);
       if (p.flags & VV_BNBWD_DZ_BF16) *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(dz) + pix * C + c) = vv_pack_bf16x4(d);
       else *reinterpret_cast<float4*>(dz + pix * C + c) = d;
     }
@@ -384,7 +384,8 @@ bn_bwd16_kernel(const vv_bnbwd_params p, const int nblk, const int bp, const flo
 __global__ void __launch_bounds__(32 * VV_NP)
 bn_bwd_sum_kernel(const int C, const int nblk, const double M, const float* __restrict__ partial,
                   float* __restrict__ dgamma, float* __restrict__ dbeta, const int64_t grad_gstride,
-                  float* __restrict__ scratch) {
+                  float* __restrict__ scratch, const vv_bnbwd_params tp, const float* __restrict__ gamma,
+                  const int64_t param_gstride, float* __restrict__ tab, const int64_t tab_gstride) {
   __shared__ double sh[2][VV_NP][32];
   const int g = blockIdx.y;
   const int cl = threadIdx.x & 31, part = threadIdx.x >> 5;
@@ -403,8 +404,22 @@ bn_bwd_sum_kernel(const int C, const int nblk, const double M, const float* __re
   for (int k = 0; k < VV_NP; ++k) { s1 += sh[0][k][cl]; s2 += sh[1][k][cl]; }
   dbeta[(int64_t)g * grad_gstride + c] = (float)s1;
   dgamma[(int64_t)g * grad_gstride + c] = (float)s2;
-  scratch[(int64_t)g * 2 * C + c] = (float)(s1 / M);
-  scratch[(int64_t)g * 2 * C + C + c] = (float)(s2 / M);
+  if (!tab) {
+    scratch[(int64_t)g * 2 * C + c] = (float)(s1 / M);
+    scratch[(int64_t)g * 2 * C + C + c] = (float)(s2 / M);
+    return;
+  }
+  // vv_bn_bwd_sums: the whole per-channel table of vv_bnbwd4 (gk: the same fp32 product the apply pass forms)
+  float* t = tab + (int64_t)g * tab_gstride + c;
+  const int64_t o = (int64_t)g * tp.ab_gstride + c;
+  const float iv = tp.invstd[o];
+  t[0] = tp.a[o];
+  t[C] = tp.b[o];
+  t[2 * C] = tp.mean[o];
+  t[3 * C] = iv;
+  t[4 * C] = gamma[(int64_t)g * param_gstride + c] * iv;
+  t[5 * C] = (float)(s1 / M);
+  t[6 * C] = (float)(s2 / M);
 }
 
 // ------------------------------------------------------------------------------------------------ output conv
@@ -1389,21 +1404,40 @@ extern "C" int vv_bn_bwd_reduce(const vv_bnbwd_params* p, vv_stream stream) {
   return VV_OK;
 }
 
+// rows of the partial-sum array p->partial holds
+static inline int bn_partial_rows(const vv_bnbwd_params* p) {
+  // VV_BNBWD_PARTIALS_PER_CUBE: the partials were left by vv_outconv_bwd (one block per cube), not by vv_bn_bwd_reduce
+  // VV_BNBWD_PARTIALS_PER_TILE: ... by the Winograd data-gradient launch that produced dA (one block per pixel tile)
+  return (p->flags & VV_BNBWD_PARTIALS_PER_CUBE) ? p->B
+         : (p->flags & VV_BNBWD_PARTIALS_PER_TILE) ? vv_wino_ntiles(p->B, p->H)
+         : (p->flags & VV_BNBWD_PARTIALS_PER_TILE44) ? vv_wino44_ntiles(p->B, p->H)
+         : (p->flags & VV_BNBWD_PARTIALS_PER_CTILE) ? vv_conv_ntiles(p->B, p->H, p->W)
+         : (p->flags & VV_BNBWD_PARTIALS_PER_TTILE) ? vv_convt_dgrad_ntiles(p->B, p->H, p->W, 0) : bn_nblk_of(p);
+}
+
+extern "C" int vv_bn_bwd_sums(const vv_bnbwd_params* p, const float* gamma, int64_t param_gstride, float* dgamma, float* dbeta,
+                              int64_t grad_gstride, float* table, int64_t table_gstride, vv_stream stream) {
+  if (!p || !p->partial || !p->a || !p->b || !p->mean || !p->invstd || !gamma || !dgamma || !dbeta || !table) return VV_ERR_BAD_ARG;
+  if (p->dpool || (p->flags & (VV_BNBWD_DZ_BF16 | VV_BNBWD_DA_BF16 | VV_BNBWD_Y_BF16))) return VV_ERR_UNSUPPORTED;
+  if (table_gstride < (int64_t)VV_BNBWD_TAB_ROWS * p->C) return VV_ERR_BAD_ARG;
+  const int nblk = bn_partial_rows(p);
+  if (nblk <= 0) return VV_ERR_BAD_ARG;
+  const int64_t M = (int64_t)p->B * p->H * p->W;
+  VV_LAUNCH(bn_bwd_sum_kernel, dim3((p->C + 31) / 32, p->G), dim3(32 * VV_NP), 0, (hipStream_t)stream, p->C, nblk, (double)M,
+            p->partial, dgamma, dbeta, grad_gstride, nullptr, *p, gamma, param_gstride, table, table_gstride);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
 extern "C" int vv_bn_bwd_apply(const vv_bnbwd_params* p, const float* gamma, int64_t param_gstride, float* dgamma,
                                float* dbeta, int64_t grad_gstride, float* scratch, vv_stream stream) {
   if (!p || !p->y || !p->dA.ptr || !p->dz || !p->partial || !gamma || !dgamma || !dbeta || !scratch) return VV_ERR_BAD_ARG;
-  // VV_BNBWD_PARTIALS_PER_CUBE: the partials were left by vv_outconv_bwd (one block per cube), not by vv_bn_bwd_reduce
-  // VV_BNBWD_PARTIALS_PER_TILE: ... by the Winograd data-gradient launch that produced dA (one block per pixel tile)
-  const int nblk = (p->flags & VV_BNBWD_PARTIALS_PER_CUBE) ? p->B
-                   : (p->flags & VV_BNBWD_PARTIALS_PER_TILE) ? vv_wino_ntiles(p->B, p->H)
-                   : (p->flags & VV_BNBWD_PARTIALS_PER_TILE44) ? vv_wino44_ntiles(p->B, p->H)
-                   : (p->flags & VV_BNBWD_PARTIALS_PER_CTILE) ? vv_conv_ntiles(p->B, p->H, p->W)
-                   : (p->flags & VV_BNBWD_PARTIALS_PER_TTILE) ? vv_convt_dgrad_ntiles(p->B, p->H, p->W, 0) : bn_nblk_of(p);
+  const int nblk = bn_partial_rows(p);
   if (nblk <= 0) return VV_ERR_BAD_ARG;
   const int nblk_apply = bn_nblk_of(p);
   const int64_t M = (int64_t)p->B * p->H * p->W;
   VV_LAUNCH(bn_bwd_sum_kernel, dim3((p->C + 31) / 32, p->G), dim3(32 * VV_NP), 0, (hipStream_t)stream, p->C, nblk, (double)M,
-            p->partial, dgamma, dbeta, grad_gstride, scratch);
+            p->partial, dgamma, dbeta, grad_gstride, scratch, *p, nullptr, 0, nullptr, 0);
   VV_CHECK_LAUNCH();
   if (bn_all16(p)) {
     if (p->dpool)

@@ -248,7 +248,9 @@ wgrad_mfma_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
 //   instead of -dY[1][.], column nu = 3 uses +t1 instead of -t1, so acc[nu] = s(xi) s(nu) dU[xi][nu] with s(3) = -1.
 //   Epilogue: each wave folds its columns (dU G), the four xi rows meet in LDS, wave w finishes accumulator rows 4w..4w+3 of
 //   all 9 taps (G^T .) and writes them to the workgroup's slab -- the layout vv_wgrad_reduce expects.
-template <int TH, int TW, int NI, int UH, int UNI>
+// BNB: vv_wgrad_params.dy_bn set -- dy is formed on load from dA (p.dy) and z (p.dy_z) by vv_bnbwd4 (no halo: every dy item is a real pixel
+// of a live image or a zero-filled one past the batch, which stays zero).
+template <int TH, int TW, int NI, int UH, int UNI, bool BNB>
 __global__ void __launch_bounds__(256, 3)
 wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const int NCO, const int total, const int nper) {
   constexpr int NTH = 256, W_ = TW;
@@ -298,6 +300,19 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
   const float* baseB = p.dy.ptr + (int64_t)g * p.dy.gstride + p.dy.coff;
   const int csB = p.dy.cstride;
 
+  // dy_bn: z (pixel stride csZ) and this thread's four channels' constants
+  const float* baseZ = BNB ? p.dy_z.ptr + (int64_t)g * p.dy_z.gstride + p.dy_z.coff : nullptr;
+  const int csZ = p.dy_z.cstride;
+  // (the constants of the workgroup's 32 channels live in LDS, read at commit: held in registers they spilled)
+  __shared__ float bnk[BNB ? VV_BNBWD_TAB_ROWS * 32 : 1];
+  if constexpr (BNB) {
+    if (tid < VV_BNBWD_TAB_ROWS * 32)
+      bnk[tid] = p.dy_bn[(int64_t)g * p.dy_bn_gstride + (tid >> 5) * p.Cout + cot * 32 + (tid & 31)];
+  }
+  unsigned voffZ[BNB ? NPB : 1];
+  float4 rz[BNB ? NPB : 1];
+  __amdgpu_buffer_rsrc_t rsZ;
+
   // ---- staging items (once per workgroup): byte offset inside the source relative to the unit's origin pixel, LDS slot
   unsigned voffA[NPA], voffB[NPB];
   int slotA[NPA];
@@ -322,6 +337,7 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
     const int px = (tid + k * NTH) >> 3;                                   // pixel of the unit: [im][y][x]
     const int im = px / (UH * W_), rem = px % (UH * W_);
     voffB[k] = (unsigned)((im * H * W_ + rem) * csB + cB) * 4u;
+    if constexpr (BNB) voffZ[k] = (unsigned)((im * H * W_ + rem) * csZ + cB) * 4u;
   }
 
   // ---- unit walk: k-split tiles ks, ks + KS, ... < NT, UPT units each
@@ -341,6 +357,9 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
     const int64_t ob = ((int64_t)(img0 * H + uy0) * W_) * csB;
     rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(baseA + oa), 0, 0x7FFFFFFF, 0x00020000);
     rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(baseB + ob), 0, 0x7FFFFFFF, 0x00020000);
+    if constexpr (BNB)
+      rsZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(baseZ + ((int64_t)(img0 * H + uy0) * W_) * csZ), 0, 0x7FFFFFFF,
+                                              0x00020000);
     const bool img_ok = live && img0 < p.B;                                // UNI == 1: the whole unit
     kill = img_ok ? 0u : 0xFFFFFFFFu;
     if (ROWDYN) {
@@ -370,6 +389,10 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
     } else {
       const v4f v = __builtin_amdgcn_raw_buffer_load_b128(rsB, liveB[k - NPA] ? voffB[k - NPA] : OOB, 0, 0);
       r[k] = make_float4(v.x, v.y, v.z, v.w);
+      if constexpr (BNB) {
+        const v4f z = __builtin_amdgcn_raw_buffer_load_b128(rsZ, liveB[k - NPA] ? voffZ[k - NPA] : OOB, 0, 0);
+        rz[k - NPA] = make_float4(z.x, z.y, z.z, z.w);
+      }
     }
   };
   auto commit_piece = [&](auto K, float* buf) {
@@ -381,7 +404,11 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
         *reinterpret_cast<float4*>(buf + slotA[k]) = v;
       }
     } else {
-      *reinterpret_cast<float4*>(buf + ASZ + ((tid + (k - NPA) * NTH) >> 3) * 32 + q8 * 4) = r[k];
+      float4 v = r[k];
+      if constexpr (BNB) {
+        if (liveB[k - NPA]) v = vv_bnbwd4(v, rz[k - NPA], vv_bnbwd_consts(bnk, 32, q8 * 4));
+      }
+      *reinterpret_cast<float4*>(buf + ASZ + ((tid + (k - NPA) * NTH) >> 3) * 32 + q8 * 4) = v;
     }
   };
 
@@ -425,6 +452,7 @@ wgrad_wino_kernel(const vv_wgrad_params p, const int NT, const int NCI, const in
     for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
 
   // ---- first unit
+  if constexpr (BNB) __syncthreads();    // bnk
   begin_unit();
   vv_static_for<0, NP>([&](auto K) { load_piece(K); });
   vv_static_for<0, NP>([&](auto K) { commit_piece(K, lds); });
@@ -576,16 +604,24 @@ inline bool wgeo(int kind, int H, int W, WGeo* t) {
   return false;
 }
 
-template <int TH, int TW, int NI, int UH, int UNI>
-int launch_ww(const vv_wgrad_params* p, hipStream_t st) {
+template <int TH, int TW, int NI, int UH, int UNI, bool BNB>
+int launch_ww_(const vv_wgrad_params* p, hipStream_t st) {
   if (p->W != TW) return VV_ERR_UNSUPPORTED;
   const int NT = ((p->B + NI - 1) / NI) * (p->H / TH) * (p->W / TW);
   const int NCI = (p->CinP + 31) / 32, NCO = p->Cout / 32;
   const int total = p->G * NCI * NCO * p->ksplit;
   const int nper = (total + 7) / 8;
-  VV_LAUNCH((wgrad_wino_kernel<TH, TW, NI, UH, UNI>), dim3(nper * 8), dim3(256), 0, st, *p, NT, NCI, NCO, total, nper);
+  VV_LAUNCH((wgrad_wino_kernel<TH, TW, NI, UH, UNI, BNB>), dim3(nper * 8), dim3(256), 0, st, *p, NT, NCI, NCO, total, nper);
   VV_CHECK_LAUNCH();
   return VV_OK;
+}
+
+template <int TH, int TW, int NI, int UH, int UNI>
+int launch_ww(const vv_wgrad_params* p, hipStream_t st) {
+  if constexpr (TW == 4) {
+    if (p->dy_bn) return VV_ERR_UNSUPPORTED;      // (the 4x4 level's form spilled with the dy_bn stage)
+  } else if (p->dy_bn) return launch_ww_<TH, TW, NI, UH, UNI, true>(p, st);
+  return launch_ww_<TH, TW, NI, UH, UNI, false>(p, st);
 }
 
 template <int TH, int TW, int NI, int KIND>
@@ -613,6 +649,11 @@ extern "C" int vv_wgrad_mfma(const vv_wgrad_params* p, vv_stream stream) {
   if (p->Cout % 32 || p->ksplit < 1) return VV_ERR_BAD_ARG;
   if (p->kind == VV_CONV3 && (p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE))
     return VV_ERR_UNSUPPORTED;    // feed the materialised tensor (vv_pool_act / vv_cube_erase) as VV_IN_PLAIN
+  if (p->in_mode == VV_IN_BNBWD) return VV_ERR_UNSUPPORTED;
+  if (p->dy_bn) {                 // dy formed on load: the Winograd 3x3 form on the 32x32 ... 8x8 levels, z the same pixels as dA
+    if (p->kind != VV_CONV3 || !(p->pad0 & 256) || !p->dy_z.ptr) return VV_ERR_UNSUPPORTED;
+    if ((int64_t)p->B * p->H * p->W * p->dy_z.cstride * 4 >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   if (p->kind == VV_CONV3 && (p->pad0 & 256)) {           // Winograd F(2x2,3x3) form (same k-split tiles, same slabs)
     switch (p->H) {

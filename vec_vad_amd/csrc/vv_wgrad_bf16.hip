@@ -918,6 +918,7 @@ extern "C" int vv_wgrad_bf16(const vv_wgrad_params* p, vv_stream stream) {
   if (!p || !p->src0.ptr || !p->dy.ptr || !p->partial) return VV_ERR_BAD_ARG;
   if (p->Cout % 32 || p->ksplit < 1) return VV_ERR_BAD_ARG;
   if (p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE) return VV_ERR_UNSUPPORTED;   // feed the materialised tensor
+  if (p->dy_bn || p->in_mode == VV_IN_BNBWD) return VV_ERR_UNSUPPORTED;                  // BatchNorm backward on load: fp32 only
   hipStream_t st = (hipStream_t)stream;
   if ((p->pad0 & VV_WGRAD_DY_BF16) && p->dy.coff % 2) return VV_ERR_BAD_ARG;
   if ((p->pad0 & VV_WGRAD_X_BF16) && !(p->pad0 & VV_WGRAD_DY_BF16)) return VV_ERR_UNSUPPORTED;

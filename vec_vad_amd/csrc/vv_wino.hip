@@ -64,7 +64,8 @@ struct WGeo {
 // CU) and the input transform, the patch reads and the halo staging of a chunk serve 32 MFMAs instead of 16 -- an fp32 MFMA holds the
 // SIMD's issue port, so a tile costs 64 cycles per MFMA plus ~5 per other instruction of every wave: fewer other
 // instructions per MFMA is the only lever.  Same arithmetic per output in the same order: bit-identical to NB = 1.
-template <int H_, int NB>
+// BNB: VV_IN_BNBWD input (data gradient reading dA and z; dy formed on load by vv_bnbwd4, real pixels only).
+template <int H_, int NB, bool BNB>
 __global__ void __launch_bounds__(WN, NB == 2 ? 2 : 3)
 wino_conv_kernel(const vv_conv_params p, const int NT, const int NN, const int total, const int nper) {
   using G_ = WGeo<H_>;
@@ -134,8 +135,35 @@ wino_conv_kernel(const vv_conv_params p, const int NT, const int NN, const int t
       voff[k] = ((valid >> k) & 1u) ? (unsigned)((tile + pixv[k]) * cs + q4) * 4u : 0x80000000u;
     cur_second = second ? 1 : 0;
   };
+  // VV_IN_BNBWD: z at the same pixels (plain, src1) and the channels' constants of the chunk in flight
+  float4 rz[BNB ? NIT : 1];
+  unsigned zoff[BNB ? NIT : 1];
+  // (the table is staged in LDS once per workgroup and read at commit: held in registers across a chunk it spilled)
+  __shared__ float bnt[BNB ? VV_BNBWD_TAB_ROWS * 256 : 1];
+  int cur_c = 0;
+  __amdgpu_buffer_rsrc_t rsZ;
+  if constexpr (BNB) {
+    rsZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.p1 + s.co1), 0, 0x7FFFFFFF, 0x00020000);
+#pragma unroll
+    for (int k = 0; k < NIT; ++k)
+      zoff[k] = ((valid >> k) & 1u) ? (unsigned)((tile + pixv[k]) * s.cs1 + q4) * 4u : 0x80000000u;
+    for (int i = tid; i < VV_BNBWD_TAB_ROWS * CinP; i += WN) bnt[i] = s.a[i];
+    __syncthreads();
+  }
   auto issue = [&](const int c0) {
     const int c = c0 + q4;
+    if constexpr (BNB) {
+      if (cur_second != 0) set_source(false);
+      cur_c = c;
+#pragma unroll
+      for (int k = 0; k < NIT; ++k) {
+        const v4f v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff[k], c0 * 4, 0);
+        r[k] = make_float4(v.x, v.y, v.z, v.w);
+        const v4f z = __builtin_amdgcn_raw_buffer_load_b128(rsZ, zoff[k], c0 * 4, 0);
+        rz[k] = make_float4(z.x, z.y, z.z, z.w);
+      }
+      return;
+    }
     act = (s.mode == VV_IN_ACT) || (s.mode == VV_IN_CAT && c < s.csplit);
     if (act) {
       sa = *reinterpret_cast<const float4*>(s.a + c);
@@ -150,11 +178,15 @@ wino_conv_kernel(const vv_conv_params p, const int NT, const int NN, const int t
     }
   };
   auto commit = [&]() {
+    VVBnBwd4 kc;
+    if constexpr (BNB) kc = vv_bnbwd_consts(bnt, CinP, cur_c);
 #pragma unroll
     for (int k = 0; k < NIT; ++k)
       if (NITEMS % WN == 0 || k < NIT - 1 || slot[k] >= 0) {
         float4 v = r[k];
-        if (act && ((valid >> k) & 1u)) v = vv_act4(v, sa, sb);
+        if constexpr (BNB) {
+          if ((valid >> k) & 1u) v = vv_bnbwd4(v, rz[k], kc);
+        } else if (act && ((valid >> k) & 1u)) v = vv_act4(v, sa, sb);
         lds4[slot[k]] = v;
       }
   };
@@ -808,7 +840,7 @@ int launch_wino_ring(const vv_conv_params* p, hipStream_t st) {
 // the launches wino_ring_kernel takes: 32x32 level, K <= 32, one plain or activated source, enough tiles for runs of >= 4 per workgroup
 inline bool vv_wino_ring_ok(const vv_conv_params* p) {
   if (p->H != 32 || (p->CinP != 16 && p->CinP != 32) || (p->pad0 & VV_CONV_NO_RING)) return false;
-  if (p->in_mode != VV_IN_PLAIN && p->in_mode != VV_IN_ACT) return false;
+  if (p->in_mode != VV_IN_PLAIN && p->in_mode != VV_IN_ACT) return false;     // (VV_IN_BNBWD: the per-tile kernel)
   if (p->bn_partial && (p->pad0 & VV_CONV_RELU)) return false;
   return (int64_t)p->G * (p->Cout / 32) * p->B * 8 >= VV_RING_MIN;
 }
@@ -820,7 +852,8 @@ int launch_wino(const vv_conv_params* p, hipStream_t st) {
   // two N tiles per workgroup (two workgroups per CU) where that leaves whole rounds of 512 workgroups: at least two, the last one
   // at least 90 % full; VV_WINO_NB=1 in the environment keeps one N tile everywhere (A/B switch, read once)
   static const bool nb1 = [] { const char* e = getenv("VV_WINO_NB"); return e && e[0] == '1'; }();
-  bool two = !nb1 && p->Cout % 64 == 0;
+  // (VV_IN_BNBWD: one N tile -- with two the dA / z stage spilled; bit-identical either way)
+  bool two = !nb1 && p->Cout % 64 == 0 && p->in_mode != VV_IN_BNBWD;
   if (two) {
     const int64_t wgs = (int64_t)p->G * (p->Cout / 64) * NT;
     const int64_t rounds = (wgs + 511) / 512;
@@ -829,10 +862,15 @@ int launch_wino(const vv_conv_params* p, hipStream_t st) {
   const int NN = p->Cout / (two ? 64 : 32);
   const int total = p->G * NN * NT;
   const int nper = (total + 7) / 8;
+  const bool bnb = p->in_mode == VV_IN_BNBWD;
   if (two)
-    VV_LAUNCH((wino_conv_kernel<H_, 2>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
+    VV_LAUNCH((wino_conv_kernel<H_, 2, false>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
+  else if constexpr (H_ != 4) {
+    if (bnb) VV_LAUNCH((wino_conv_kernel<H_, 1, true>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
+    else VV_LAUNCH((wino_conv_kernel<H_, 1, false>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
+  }
   else
-    VV_LAUNCH((wino_conv_kernel<H_, 1>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
+    VV_LAUNCH((wino_conv_kernel<H_, 1, false>), dim3(nper * 8), dim3(WN), 0, st, *p, NT, NN, total, nper);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }
@@ -863,6 +901,12 @@ extern "C" int vv_conv_wino(const vv_conv_params* p, vv_stream stream) {
   }
   if (p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE)
     return VV_ERR_UNSUPPORTED;    // feed the materialised tensor (vv_pool_act / vv_cube_erase) as VV_IN_PLAIN
+  if (p->in_mode == VV_IN_BNBWD) {
+    // dA in src0, z in src1 (same pixels), the vv_bn_bwd_sums table in a: every GEMM-K channel is a BatchNorm channel
+    if (!p->src1.ptr || !p->a || p->Cin != p->CinP || (p->pad0 & (VV_CONV_BF16 | VV_CONV_RELU))) return VV_ERR_BAD_ARG;
+    if (p->H == 4 || p->CinP > 256) return VV_ERR_UNSUPPORTED;       // (the 4x4 level's kernel spilled with this stage)
+    if ((int64_t)p->B * p->H * p->W * p->src1.cstride * 4 >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   if (vv_wino_ring_ok(p)) return p->CinP == 16 ? launch_wino_ring<2>(p, st) : launch_wino_ring<4>(p, st);
   switch (p->H) {
