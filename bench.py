@@ -12,15 +12,18 @@ Cubes live on the GPU as uint8 / fp32 (the reference's on-disk cube layout); eve
 (vv_cube_gather), runs the grouped HIP forward, backward and fused Adam.  Multi-GPU: one process per GPU, each rank
 trains on its own cubes and the flat gradient buffer is all-reduced over RCCL in three buckets.
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; the
+records below that need runs of their own (forward-only passes and eager event steps after the timed region, configs, cpu_baseline,
+the DataParallel-faithful record of N > 1) are measured with --full only.
   roofline      the dominant kernel family (3x3 convolution forward + data-gradient launches), timed with HIP events on the
                 launch stream inside the timed region.  ``achieved`` / ``frac`` count the multiply-adds the matrix cores EXECUTE
                 (the Winograd F(2x2,3x3) kernel executes 16/36 of the direct convolution's), so frac <= 1 is a hardware
                 utilisation; the algorithmic (direct-convolution) rate is ``algorithmic_tflops`` and their ratio
-                ``effective_vs_direct``.
-  cpu_baseline  the reference's op sequence (oracle, stock PyTorch CPU ops) on the host cores: 3 warm-up + 10 timed steps per
+                ``effective_vs_direct``.  A plain run has the events of the first timed step only; --full adds 4 eager event steps
+                right after the timed region.
+  cpu_baseline  (--full, N=1) the reference's op sequence (oracle, stock PyTorch CPU ops) on the host cores: 3 warm-up + 10 timed steps per
                 thread count, best-of sweep AND the all-cores figure, train step and eval forward.
-  configs       secondary records measured in the same run (N=1 only): BASELINE config 4 (SelfCompleteNetFull, B=512, mixed
+  configs       secondary records measured in the same run (--full, N=1 only): BASELINE config 4 (SelfCompleteNetFull, B=512, mixed
                 bf16), config 5 (FlowNet2 forward on a 1024x448 pair) and the eval-mode scoring pass, each with its own roofline.
   comm          (N>1) ranks + backend, per-bucket all-reduce time and the exposed communication per step.
 The scalar headline of every secondary record is repeated inside ``config`` (cfg4_cubes_per_s, flownet2_ms_per_pair, net4_b32_ms ...)
@@ -728,19 +731,23 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=256, help='cubes per GPU per step (32 with --gpus 8 = DataParallel split of 256)')
-    ap.add_argument('--dp-split-of', type=int, default=256, help='N > 1: global batch of the second, DataParallel-faithful record (one batch of '
-                    'this size split over the ranks, train.py:373-375); 0 = headline only')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: forward-only passes and eager '
+                    'event steps after the timed region, the secondary configs and the CPU baseline (N=1), the DataParallel-faithful '
+                    'record (N>1)')
+    ap.add_argument('--dp-split-of', type=int, default=256, help='N > 1 with --full: global batch of the second, DataParallel-faithful record '
+                    '(one batch of this size split over the ranks, train.py:373-375); 0 = headline only')
     ap.add_argument('--pool', type=int, default=4096, help='device-resident synthetic cubes per GPU')
     ap.add_argument('--model', default='net4', choices=['net4', 'full'])
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                     help="bf16 = BASELINE config 4's mixed precision; the headline number is fp32, like the reference")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-child', type=int, default=0, help=argparse.SUPPRESS)          # one leg of the CPU baseline (internal)
     ap.add_argument('--cpu-child-limit', type=float, default=10.0, help=argparse.SUPPRESS)
     ap.add_argument('--no-graph', action='store_true', help='eager launch loop in every timed step (default: hipGraph replay)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the config-4 / config-5 / scoring records')
-    ap.add_argument('--no-forward-timing', action='store_true', help='skip the forward-only passes (counter profiles: the process '
-                    'then runs train steps alone, so whole-process HBM bytes / Adam launches = bytes per step)')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the config-4 / config-5 / scoring records')
+    ap.add_argument('--no-forward-timing', action='store_true', help='with --full: skip the forward-only passes and the event steps after '
+                    'the timed region (counter profiles: the process then runs train steps alone, so whole-process HBM bytes / Adam '
+                    'launches = bytes per step; a plain run never has them)')
     ap.add_argument('--breakdown', action='store_true', help='print a per-launch time table to stderr')
     ap.add_argument('--overlap', nargs='?', const='free', default='none', choices=('none', 'free', 'paired'),
                     help="side stream for the weight-gradient kernels: 'free' = under everything that follows (conv launches "
@@ -778,9 +785,9 @@ def main():
     if dist is not None and dist.get_world_size() != args.gpus:
         raise SystemExit('process group has %d ranks, --gpus %d' % (dist.get_world_size(), args.gpus))
     dump = {} if (args.dump_outputs and rank == 0) else None
+    extra = args.full and not args.no_forward_timing
     rec = run_unet(args.model, args.precision, args.batch, args.steps, args.warmup, dev, rank, world, dist, args.overlap,
-                   args.breakdown, args.pool, graph=not args.no_graph, measure_forward=not args.no_forward_timing,
-                   ev_extra=0 if args.no_forward_timing else 4, dump=dump)
+                   args.breakdown, args.pool, graph=not args.no_graph, measure_forward=extra, ev_extra=4 if extra else 0, dump=dump)
     if dump is not None:
         import numpy as np
         os.makedirs(args.dump_outputs, exist_ok=True)
@@ -790,7 +797,7 @@ def main():
     # nn.DataParallel scatters ONE 256-cube batch over the GPUs => 256 / N cubes per rank and step, per-rank BatchNorm statistics)
     rec_dp = None
     dpg = args.dp_split_of
-    if world > 1 and not args.no_secondary and dpg > 0 and dpg % world == 0 and dpg // world != args.batch:
+    if args.full and world > 1 and not args.no_secondary and dpg > 0 and dpg % world == 0 and dpg // world != args.batch:
         try:
             rec_dp = run_unet(args.model, args.precision, dpg // world, min(50, max(args.steps, 4)), 5, dev, rank, world, dist, args.overlap,
                               False, min(args.pool, 1024), graph=not args.no_graph, measure_forward=False, ev_extra=0)
@@ -814,7 +821,7 @@ def main():
         out['config'].update({'dp_faithful_cubes_per_s': rec_dp.get('value'), 'dp_faithful_ms_per_step': rec_dp.get('ms_per_step'),
                               'dp_faithful_exposed_comm_us': (rec_dp.get('comm') or {}).get('exposed_comm_us_per_step'),
                               'weak_exposed_comm_us': (rec.get('comm') or {}).get('exposed_comm_us_per_step')})
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         sec = {}
         for name, fn in (('full_b512_bf16', lambda: run_unet('full', 'bf16', 512, 20, 5, dev, 0, 1, None, 'none', False, 2048,
                                                              graph=not args.no_graph)),
@@ -847,7 +854,7 @@ def main():
                               'net4_b16_ms': _g('net4_b16', 'ms_per_step'), 'net4_b16_cubes_per_s': _g('net4_b16', 'value'),
                               'flownet2_ms_per_pair': _g('flownet2_1024x448', 'ms_per_pair'),
                               'eval_scoring_cubes_per_s': _g('net4_eval_scoring', 'value')})
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             out['cpu_baseline'] = cpu_baseline()
         except Exception as e:   # the oracle is optional infrastructure for the bench line

@@ -1,5 +1,5 @@
-"""GPU: bench.py --dump-outputs writes what the last timed train step computed -- not a later step -- the same arrays from run to run,
-and --steps sets the number of timed steps."""
+"""GPU: bench.py --dump-outputs writes what the last timed train step computed -- not a later step -- the same arrays from run to run
+and with or without --full, and --steps sets the number of timed steps."""
 import json
 import os
 import subprocess
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(out_dir, steps, *extra):
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '3', '--batch', '32',
-           '--pool', '128', '--no-cpu-baseline', '--no-secondary', '--dump-outputs', str(out_dir)] + list(extra)
+           '--pool', '128', '--dump-outputs', str(out_dir)] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -24,12 +24,14 @@ def _bench(out_dir, steps, *extra):
 
 
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
-    # the default run follows the timed steps with 4 eager event steps (roofline samples) and forward passes, --no-forward-timing
-    # with neither; the inputs of the timed steps are the same, so the dumps agree only if they were taken before those extra steps
-    a = _bench(tmp_path / 'a', 4)
-    b = _bench(tmp_path / 'b', 4, '--no-forward-timing')
+    # --full follows the timed steps with 4 eager event steps (roofline samples) and forward passes, a plain run with neither; the
+    # inputs of the timed steps are the same, so the dumps agree only if they were taken before those extra steps
+    a = _bench(tmp_path / 'a', 4, '--full', '--no-cpu-baseline', '--no-secondary')
+    b = _bench(tmp_path / 'b', 4)
     assert 'in 4 further eager event step(s)' in a['roofline']['launches_timed_where'], a['roofline']
     assert 'in 0 further eager event step(s)' in b['roofline']['launches_timed_where'], b['roofline']
+    assert 'forward_ms' in a['config'] and 'forward_ms' not in b['config']
+    assert not {'configs', 'cpu_baseline'} & set(b), sorted(b)
     for d in (a, b):
         assert d['steps'] == 4 and d['ms_per_step'] > 0
         assert abs(d['value'] - 32 * 4 / (d['ms_per_step'] * 4e-3)) <= 1e-6 * d['value']

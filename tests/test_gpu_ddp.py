@@ -331,7 +331,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_valid_line():
     port = 31900 + (os.getpid() % 1000)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '3', '--batch', '16',
-           '--pool', '64', '--no-cpu-baseline', '--dp-split-of', '8']
+           '--pool', '64', '--full', '--no-cpu-baseline', '--dp-split-of', '8']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -346,7 +346,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_valid_line():
     assert np.isfinite(d['config']['loss_raw'])
     # graph mode reports the exposed communication (one event pair around the last bucket + wait, between the captured segments)
     assert d['comm']['exposed_comm_steps_timed'] >= 6 and d['comm']['exposed_comm_us_per_step'] > 0
-    # ... and the second, DataParallel-faithful record beside the weak-scaling headline: one 8-cube batch over 2 ranks
+    # ... and with --full the second, DataParallel-faithful record beside the weak-scaling headline: one 8-cube batch over 2 ranks
     assert list(d['configs']) == ['dp_faithful_global_batch_8'], list(d.get('configs', {}))
     dp = d['configs']['dp_faithful_global_batch_8']
     assert dp['config']['batch_per_gpu'] == 4 and dp['config']['global_batch'] == 8 and dp['value'] > 0

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_r02
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 20 --warmup 5 > $O/bench_under_rocprof.json 2> /dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- $B --steps 3 --warmup 2 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- $B --steps 3 --warmup 2 > /dev/null 2>&1
@@ -20,7 +20,7 @@ cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv
 cp $O/fn2stats/*/*kernel_stats.csv $O/flownet2_kernel_stats.csv
 cp $O/stats16/*/*kernel_stats.csv $O/kernel_stats_bf16_full_b512.csv
 rm -rf $O/stats $O/fn2stats $O/stats16 $O/pmc_fetch $O/pmc_write $O/pmc_mfma
-python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.err
 python -c "
 import json

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_r05
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary"
 C4="$B --precision bf16 --model full --batch 512"
 F="python $R/tools/bench_flownet2.py --eager"
 pmc() {  # pmc <tag> <runs> <cmd...>: FETCH_SIZE / WRITE_SIZE passes -> pmc_hbm_traffic<tag>.json, MFMA-busy pass -> pmc_mfma_busy<tag>.json
@@ -64,7 +64,7 @@ python $R/tools/ubench_wino.py 20 > $O/ubench_wino.txt 2>/dev/null
 UB_PLAIN=1 UB_ONLY32=1 python $R/tools/ubench_wino.py 20 > $O/ubench_wino_plain32.txt 2>/dev/null
 # the bench line last, the way the driver runs it; its `traffic` now comes from the counter files of THIS library
 cp $O/launch_census.json $R/profiles/r05_launch_census.json
-python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.err
 VV_WINO_RING=0 $B --steps 20 --warmup 5 > $O/bench_per_tile_kernel_only.json 2>/dev/null
 $B --steps 20 --warmup 5 > $O/bench_headline_only.json 2>/dev/null

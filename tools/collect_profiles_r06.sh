@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_r06
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary"
 C4="$B --precision bf16 --model full --batch 512"
 F="python $R/tools/bench_flownet2.py --eager"
 pmc() {  # pmc <tag> <runs> <cmd...>: FETCH_SIZE / WRITE_SIZE passes -> pmc_hbm_traffic<tag>.json, MFMA-busy pass -> pmc_mfma_busy<tag>.json
@@ -63,7 +63,7 @@ $C4 --steps 10 --warmup 3 --no-graph --breakdown > /dev/null 2> $O/breakdown_bf1
 python $R/tools/eval_breakdown.py 2048 10 > $O/breakdown_eval_net4_b2048.txt 2>/dev/null
 # the bench line last, the way the driver runs it; its `traffic` now comes from the counter files of THIS library
 cp $O/launch_census.json $R/profiles/r06_launch_census.json
-python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.err
 $B --steps 20 --warmup 5 > $O/bench_headline_only.json 2>/dev/null
 $C4 --steps 20 --warmup 5 > $O/bench_bf16_full_b512.json 2>/dev/null

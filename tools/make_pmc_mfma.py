@@ -1,5 +1,5 @@
 """profiles/r01_pmc_mfma_busy.json from a rocprofv3 counter-collection CSV of
-    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline
 MFMA-busy fraction per kernel = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x SQ_BUSY_CU_CYCLES), both summed over the launches."""
 import collections
 import csv
@@ -24,7 +24,7 @@ def main():
             rows.append({'kernel': k, 'launches': n[k], 'mfma_busy_cycles': busy, 'busy_cu_cycles': cu,
                          'mfma_busy_frac': round(busy / (4.0 * cu), 4)})
     rows.sort(key=lambda r: -r['busy_cu_cycles'])
-    out = {'source': 'rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline',
+    out = {'source': 'rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline',
            'definition': 'mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (4 * SQ_BUSY_CU_CYCLES): share of the SIMD-cycles of busy CUs in which '
                          'the matrix pipe was executing (the chip clocks down to ~1.9-2.0 GHz under dense fp32 MFMA, so this is utilisation '
                          'at the sustained clock, not a fraction of the 157.3 TFLOP/s data-sheet peak)',

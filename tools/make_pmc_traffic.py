@@ -40,7 +40,7 @@ def main():
            k['kernel'].startswith(('conv_gemm16p_kernel', 'conv_ring16_kernel'))]
     n = sum(k['launches'] for k in fam)
     out = {
-        'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE  /  --pmc WRITE_SIZE (two separate passes) -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline',
+        'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE  /  --pmc WRITE_SIZE (two separate passes) -- python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline',
         'units': 'FETCH_SIZE / WRITE_SIZE are reported in KB; FETCH_SIZE is doubled (gfx950 tallies 128-B read requests at 64 B for '
                  'wide coalesced reads, MI355X_MICROARCH.md section HBM)',
         'conv_family': {'kernels': sorted(set(k['kernel'] for k in fam)), 'launches': n,

@@ -9,5 +9,5 @@ for v in A B A B; do
   if [ $v = B ]; then export VV_LIB_PATH=$V; else unset VV_LIB_PATH; fi
   echo "== $v (${VV_LIB_PATH:-product})"
   UB_H=${UB_H:-16} python tools/ubench_conv16.py 20 2>/dev/null | grep -E "H=|weighted" | cut -c1-60
-  python bench.py --no-cpu-baseline --no-secondary --precision bf16 --model full --batch 512 --steps 20 --warmup 5 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('cfg4', round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['avg_launch_us'],1))"
+  python bench.py --full --no-cpu-baseline --no-secondary --precision bf16 --model full --batch 512 --steps 20 --warmup 5 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('cfg4', round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['avg_launch_us'],1))"
 done

@@ -13,8 +13,8 @@ for sw in "VV_WINOGRAD=0" "VV_WINOGRAD_WGRAD=0" "VV_WINOGRAD=1"; do
 done
 cp gpurun_out/observed.jsonl $O/observed_switches.jsonl
 cat $O/observed_switches.jsonl
-python bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_headline.json 2>$O/err1.txt
-python bench.py --no-cpu-baseline --no-secondary --precision bf16 --model full --batch 512 --steps 20 --warmup 5 > $O/bench_c4.json 2>$O/err2.txt
+python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_headline.json 2>$O/err1.txt
+python bench.py --full --no-cpu-baseline --no-secondary --precision bf16 --model full --batch 512 --steps 20 --warmup 5 > $O/bench_c4.json 2>$O/err2.txt
 python - <<PY
 import json
 for n in ('headline','c4'):

@@ -10,7 +10,7 @@ for v in 0 1 0 1; do
 done
 # fp32 transposed-conv weight gradient: 64-pixel tiles + two LDS buffers vs the 128-pixel form, same box
 timeout 900 python -m pytest tests/test_gpu_unet.py tests/test_gpu_fullsize.py -m gpu -x -q 2>&1 | tail -3
-B="python bench.py --no-cpu-baseline --no-secondary"
+B="python bench.py --full --no-cpu-baseline --no-secondary"
 for v in 0 1 0 1; do
   VV_WGRADT_TILE64=$v $B --steps 20 --warmup 5 > $O/b256_t64_$v.json 2>/dev/null
   VV_WGRADT_TILE64=$v $B --batch 32 --steps 50 --warmup 5 > $O/b32_t64_$v.json 2>/dev/null

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/s7_r06; rm -rf $O; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests/test_gpu_unet.py tests/test_gpu_bf16.py tests/test_gpu_fullsize.py tests/test_gpu_scripts.py tests/test_gpu_longtrain.py -m gpu -x -q 2>&1 | tail -6
-B="python bench.py --no-cpu-baseline --no-secondary"
+B="python bench.py --full --no-cpu-baseline --no-secondary"
 for v in 0 1 0 1; do
   VV_FUSE_BN_SUMS_T=$v $B --steps 20 --warmup 5 > $O/b256_$v.json 2>/dev/null
   VV_FUSE_BN_SUMS_T=$v $B --batch 32 --steps 50 --warmup 5 > $O/b32_$v.json 2>/dev/null

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/s9_r06; rm -rf $O; mkdir -p $O
 cd $R
 timeout 1700 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $O/pytest.txt
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d=json.load(open('$O/bench.json'))
