@@ -49,7 +49,7 @@ def test_train_then_test_scripts_match_reference(tmp_path, monkeypatch, precisio
     2 x observed, rounded: training scores 2e-3 (unchanged since round 4), loss 1.2e-4 (was 2e-4), frame scores 1.4e-2 (was 2e-2), AUROC 1e-3
     (the config's own criterion).  Why the bf16 training-score bar is 2e-3 and not the fp32 path's 1e-3 (round 4):
     after 6 Adam steps the bf16 path sits 6.4e-4 from the reference's fp32 scores with the round-3 conv kernel and 1.26e-3 with the
-    round-4 one (VV_CONV_GEMM16=0 / 1), although the two kernels' convolution outputs are BIT-EQUAL (tests/test_gpu_bf16.py): they sum
+    round-4 one (with / without the C flag CONV_NO_GEMM16), although the two kernels' convolution outputs are BIT-EQUAL (tests/test_gpu_bf16.py): they sum
     the BatchNorm partial sums in a different order, scale / shift move by 1e-7 relative, a handful of activations on a bf16 rounding
     boundary flip by one ulp (2^-8), and six training steps on 8-cube batches carry that to a coherent ~1e-3 shift of all 24 scores.
     That spread between two correct implementations IS the resolution of this comparison."""

@@ -471,6 +471,35 @@ def test_embedded_width_layout_roundtrip():
         assert b1[1].start == l12.cin // 2 and m1[1].start == nf and b0[1] == slice(0, nf)
 
 
+def test_bank_switches_are_checked_at_construction(monkeypatch):
+    """Every VV_* switch of the UNet bank is read once, when the bank is built, and a value it does not know raises there instead of
+    silently acting as some other setting."""
+    from vec_vad_amd.bank import UNetBank, UnitSpec
+    units = [UnitSpec('raw', i, i) for i in range(5)] + [UnitSpec('of', 4, 0)]
+    bools = ['VV_WINOGRAD', 'VV_WINOGRAD_WGRAD', 'VV_FUSE_BN_SUMS', 'VV_FUSE_BN_SUMS_T', 'VV_GROUP_REDUCE', 'VV_SPLIT_DCAT',
+             'VV_FUSE_OUTCONV', 'VV_EVAL_FOLD', 'VV_BF16_DZ', 'VV_BF16_DA', 'VV_BF16_Y']
+    bad = [('VV_PRECISION', 'fp16'), ('VV_WINO44', 'foo'), ('VV_WINO44', 'set:f3,x10'), ('VV_WINO44', 'set:d0'),
+           ('VV_WINO44', 'set:f14'), ('VV_WINO44_EVAL', 'dgrad2'), ('VV_FUSE_BN_APPLY', 'all'),
+           ('VV_FUSE_BN_APPLY', 'set:2,x'), ('VV_FUSE_BN_APPLY', 'set:14')] + [(n, v) for n in bools for v in ('2', 'on', '')]
+    for name, value in bad:
+        monkeypatch.setenv(name, value)
+        with pytest.raises(ValueError, match=name):
+            UNetBank(units, nf=32, device='cpu')
+        monkeypatch.delenv(name)
+    monkeypatch.setenv('VV_WINO44', 'SET:f3,d10')
+    monkeypatch.setenv('VV_FUSE_BN_APPLY', 'set:2,9')
+    b = UNetBank(units, nf=32, device='cpu')
+    assert [(l.idx, d) for l in b.lay.convs for d in (False, True) if b._w44(5, l, d)] == [(3, False), (10, True)]
+    assert b.fold_bn_apply == {2, 9}
+    for n in bools:
+        monkeypatch.setenv(n, '0')
+    monkeypatch.setenv('VV_WINO44', 'off')
+    monkeypatch.setenv('VV_FUSE_BN_APPLY', 'off')
+    b = UNetBank(units, nf=32, device='cpu')
+    assert not (b.wino or b.wino_wgrad or b.fuse_bn_sums or b.fuse_outconv or b.eval_fold) and b.fold_bn_apply == set()
+    assert not any(b._w44(256, l, d) for l in b.lay.convs for d in (False, True))
+
+
 def test_wino44_routing_policy(monkeypatch):
     """VV_WINO44 (round 5): default 'dgrad' = the data-gradient launches of the measured policy (GEMM-K >= 64 and workgroups that fill the
     chip evenly -- at B = 256 the 16x16-level 64- / 128-channel launches and dgrad8), forward launches stay on F(2x2); '1' adds the forward

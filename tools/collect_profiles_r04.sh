@@ -63,7 +63,6 @@ python $R/tools/ubench_conv16.py 10 legacy > $O/ubench_conv16_legacy.txt 2>/dev/
 # config 4 as its own process (the bench line's cfg4_* record runs behind the fp32 workload of the same process and reads 1 - 3 % lower),
 # twice around the round-3-kernel run of the same box
 $C4 --steps 20 --warmup 5 > $O/bench_bf16_full_b512.json 2>/dev/null
-VV_CONV_GEMM16=0 $C4 --steps 10 --warmup 3 > $O/bench_bf16_full_b512_round3_conv_kernel.json 2>/dev/null
 $C4 --steps 20 --warmup 5 >> $O/bench_bf16_full_b512.json 2>/dev/null
 VV_FN2_WINO=0 python $R/tools/bench_flownet2.py > $O/bench_flownet2_no_winograd.json 2>/dev/null
 python - <<PY

@@ -66,7 +66,6 @@ UB_PLAIN=1 UB_ONLY32=1 python $R/tools/ubench_wino.py 20 > $O/ubench_wino_plain3
 cp $O/launch_census.json $R/profiles/r05_launch_census.json
 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.err
-VV_WINO_RING=0 $B --steps 20 --warmup 5 > $O/bench_per_tile_kernel_only.json 2>/dev/null
 $B --steps 20 --warmup 5 > $O/bench_headline_only.json 2>/dev/null
 $C4 --steps 20 --warmup 5 > $O/bench_bf16_full_b512.json 2>/dev/null
 python - <<PY

@@ -17,6 +17,7 @@ import ctypes as C
 import math
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 
@@ -181,8 +182,6 @@ class UNetBank:
             raise L.VecVadHipError('features_root = %d: nf = 32 (the value of every shipped config.cfg) and nf = 64 (the default of '
                                    'SelfCompleteNet1raw1of, model/unet.py:563) are implemented -- the fused 1x1 output conv + loss '
                                    'kernels are instantiated for these two widths' % nf)
-        if nf != 32 and os.environ.get('VV_PRECISION', 'fp32').lower() != 'fp32':
-            raise L.VecVadHipError('mixed precision is implemented for features_root = 32 only')
         self.in_ch = RAW_C * (tot_raw_num if padding else tot_raw_num - 1)
         self.lay = BankLayout(nf, self.in_ch)
         self.g0, self.Ga = active if active is not None else (0, self.G)
@@ -203,6 +202,84 @@ class UNetBank:
     # ------------------------------------------------------------------------------------------ persistent state
     def _alloc_state(self):
         d, lay, G = self.device, self.lay, self.G
+        nconv = len(lay.convs)
+
+        # ---- options: every VV_* switch of the bank, read here once and checked (tests set them before they build a net)
+        def switch(name):
+            v = os.environ.get(name, '1')
+            if v not in ('0', '1'):
+                raise ValueError('%s must be 0 or 1, got %r' % (name, v))
+            return v == '1'
+
+        def launch_set(name, default, words, names):
+            v = os.environ.get(name, default).lower()
+            if v.startswith('set:'):
+                picked = frozenset(t for t in v[4:].split(',') if t)
+                if not picked <= names:
+                    raise ValueError('%s=%s: unknown entries %s' % (name, v, sorted(picked - names)))
+                return picked
+            if v not in words:
+                raise ValueError('%s must be one of %s or set:..., got %r' % (name, ' / '.join(words), v))
+            return '0' if v == 'off' else v
+
+        # VV_PRECISION=bf16 (config.cfg [mi355x] precision): mixed precision, BASELINE config 4 -- the convolutions / transposed
+        # convolutions round their operands to bf16 and contract on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (direct kernel;
+        # Winograd's transforms would amplify the bf16 rounding); tensors in HBM, BatchNorm, loss, master weights, Adam stay fp32
+        self.precision = os.environ.get('VV_PRECISION', 'fp32').lower()
+        if self.precision not in ('fp32', 'bf16'):
+            raise ValueError("VV_PRECISION / [mi355x] precision must be 'fp32' or 'bf16', got %r" % self.precision)
+        if self.nf != 32 and self.precision != 'fp32':
+            raise L.VecVadHipError('mixed precision is implemented for features_root = 32 only')
+        self.cflag = L.CONV_BF16 if self.precision == 'bf16' else 0
+        # BatchNorm backward stores dy as bf16 when both of its consumers round it to bf16 anyway (bit-identical results)
+        self.dz16 = switch('VV_BF16_DZ') and bool(self.cflag)
+        # activation gradients (outputs of the data-gradient kernels and of the output-conv backward) stored as bf16 -- NOT
+        # neutral: it is torch.autocast's dtype for them; BatchNorm backward and the transposed conv's gradients read them back
+        self.da16 = switch('VV_BF16_DA') and bool(self.cflag)
+        # ... and so are the conv / transposed-conv OUTPUTS (pre-BatchNorm tensors; torch.autocast's output dtype, oracle 'y16') and
+        # with them the pooled / frame-erased inputs: every tensor a bf16 kernel stages is then bf16 (VV_CONV_ALLSRC_BF16)
+        self.y16 = switch('VV_BF16_Y') and self.dz16 and self.da16
+        # concat layers' data gradient as two dense planes (backward_plan.dcat_views): bf16-output launches of vv_conv_mfma only
+        self.split_dcat = switch('VV_SPLIT_DCAT') and self.da16        # (da16 => bf16 kernels => no Winograd path)
+        self.fflag = self.cflag | ((L.CONV_OUT_BF16 | L.CONV_ALLSRC_BF16) if self.y16 else 0)      # forward launches
+        # fused train / scoring steps (no reconstruction store): the 1x1 output conv's forward and backward in ONE pass over y
+        # (vv_outconv_fwdbwd); the module API (forward -> outputs -> set_dout -> backward) keeps the two launches
+        self.fuse_outconv = switch('VV_FUSE_OUTCONV')
+        # VV_WINOGRAD=0 keeps the direct implicit-GEMM kernel for the 3x3 convolutions (A/B comparisons, bit-for-bit fmaf
+        # chains); default: Winograd F(2x2,3x3) for forward and data-gradient (2.25x fewer MFMA cycles, a few ulp apart)
+        wino_env = switch('VV_WINOGRAD')
+        self.wino = wino_env and not self.cflag
+        self.wino_wgrad = switch('VV_WINOGRAD_WGRAD') and wino_env
+        self.wgrad_flag = 256                  # vv_wgrad_params.pad0 bit 8: Winograd form of the 3x3 weight gradient
+        # VV_WINO44 (round 5): which fp32 3x3 launches of a TRAIN step run as Winograd F(4x4,3x3) (vv_conv_wino44: 1.78x fewer matrix-core
+        # cycles than F(2x2); with the interpolation points scaled by 3/4 its rounding error is 1 - 3e-6 of the tensor maximum, 2 - 3 x
+        # F(2x2)'s).  'dgrad' (default): the DATA-GRADIENT launches the policy of _w44 takes -- a data gradient's rounding feeds no ReLU /
+        # max-pool gate and no BatchNorm statistic, and every parameter gradient's distance from float64 is the same to three digits
+        # with and without it (tools/w44_grad_probe.py), while the forward pass -- losses, activations, statistics -- stays bit-identical
+        # to the F(2x2) path; '1': forward launches too (median gradient distance as good, but a cancellation-heavy bias gradient
+        # crosses its calibrated bar on one of the two full-size test batches); 'all': every launch it takes; '0' / 'off': none;
+        # 'set:f3,d10,...': explicit launches (probing)
+        w44_words = ('0', 'off', '1', 'dgrad', 'all')
+        w44_names = frozenset(['f%d' % i for i in range(nconv)] + ['d%d' % i for i in range(1, nconv)])
+        self.w44_mode = launch_set('VV_WINO44', 'dgrad', w44_words, w44_names)
+        self._w44_tables = {}
+        self._w44_eval_used = set()      # forward panels some eval plan routes to F(4x4): the only ones prepare_eval packs
+        # VV_WINO44_EVAL: the same choice for the eval-mode forward on the folded model (test.py:312-345 scoring; no gradients, scores
+        # and AUROC judged at 1e-3: a few 1e-6 per layer are noise there).  '1' (default): the policy of _w44; '0': none; 'all'
+        self.w44_eval_mode = launch_set('VV_WINO44_EVAL', '1', w44_words, w44_names)
+        # first reduction pass of the BatchNorm backward inside the data-gradient launch that produces dA (where it is the only producer);
+        # VV_FUSE_BN_SUMS_T=0 keeps the separate pass where that producer is a transposed conv's data gradient (A/B)
+        self.fuse_bn_sums = switch('VV_FUSE_BN_SUMS')
+        self.fuse_bn_sums_t = switch('VV_FUSE_BN_SUMS_T')
+        # VV_FUSE_BN_APPLY: layers whose BatchNorm-backward apply pass is folded into its two consumers (_plan_backward); '1' (default)
+        # = layers 0, 2, 4, '0' / 'off' = none, 'set:2,4,...' = exactly these (probing)
+        fold = launch_set('VV_FUSE_BN_APPLY', '1', ('0', 'off', '1'), frozenset(str(i) for i in range(nconv)))
+        self.fold_bn_apply = frozenset(int(t) for t in fold) if isinstance(fold, frozenset) else \
+            frozenset() if fold == '0' else frozenset((0, 2, 4))
+        # VV_GROUP_REDUCE=0: one vv_wgrad_reduce launch per weight gradient instead of one grouped launch per gradient bucket
+        self.group_reduce = switch('VV_GROUP_REDUCE')
+        self.eval_fold = switch('VV_EVAL_FOLD') and not self.cflag      # eval mode, below
+
         self.params = torch.zeros(G, lay.U, device=d)
         self.bufs = torch.zeros(G, lay.UB, device=d)
         # gradients: BUCKET-MAJOR flat buffer.  Bucket k = parameter columns [gb[k], gb[k+1]) of every UNet, stored contiguously as
@@ -237,55 +314,6 @@ class UNetBank:
             tsrc[g] = 0 if u.role == 'raw' else 1
             tcoff[g] = u.tgt * (RAW_C if u.role == 'raw' else OF_C)
         self.chmap, self.oc, self.tsrc, self.tcoff = chmap.to(d), oc.to(d), tsrc.to(d), tcoff.to(d)
-        # VV_WINOGRAD=0 keeps the direct implicit-GEMM kernel for the 3x3 convolutions (A/B comparisons, bit-for-bit fmaf
-        # chains); default: Winograd F(2x2,3x3) for forward and data-gradient (2.25x fewer MFMA cycles, a few ulp apart)
-        # VV_PRECISION=bf16 (config.cfg [mi355x] precision): mixed precision, BASELINE config 4 -- the convolutions / transposed
-        # convolutions round their operands to bf16 and contract on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (direct kernel;
-        # Winograd's transforms would amplify the bf16 rounding); tensors in HBM, BatchNorm, loss, master weights, Adam stay fp32
-        self.precision = os.environ.get('VV_PRECISION', 'fp32').lower()
-        if self.precision not in ('fp32', 'bf16'):
-            raise ValueError("VV_PRECISION / [mi355x] precision must be 'fp32' or 'bf16', got %r" % self.precision)
-        self.cflag = L.CONV_BF16 if self.precision == 'bf16' else 0
-        if self.cflag and os.environ.get('VV_CONV_GEMM16', '1') == '0':      # A/B switch: the round-3 bf16 3x3 kernel
-            self.cflag |= L.CONV_NO_GEMM16
-        self.bf16_wgrad = os.environ.get('VV_BF16_WGRAD', '1') != '0'      # 0: keep the fp32 (Winograd) weight gradient in bf16 mode
-        # BatchNorm backward stores dy as bf16 when both of its consumers round it to bf16 anyway (bit-identical results)
-        self.dz16 = bool(self.cflag) and self.bf16_wgrad and os.environ.get('VV_BF16_DZ', '1') != '0'
-        # activation gradients (outputs of the data-gradient kernels and of the output-conv backward) stored as bf16 -- NOT
-        # neutral: it is torch.autocast's dtype for them; BatchNorm backward and the transposed conv's gradients read them back
-        self.da16 = bool(self.cflag) and self.bf16_wgrad and os.environ.get('VV_BF16_DA', '1') != '0'
-        # ... and so are the conv / transposed-conv OUTPUTS (pre-BatchNorm tensors; torch.autocast's output dtype, oracle 'y16') and
-        # with them the pooled / frame-erased inputs: every tensor a bf16 kernel stages is then bf16 (VV_CONV_ALLSRC_BF16)
-        self.y16 = self.dz16 and self.da16 and os.environ.get('VV_BF16_Y', '1') != '0'
-        # concat layers' data gradient as two dense planes (backward_plan.dcat_views): bf16-output launches of vv_conv_mfma only
-        self.split_dcat = self.da16 and os.environ.get('VV_SPLIT_DCAT', '1') != '0'        # (da16 => bf16 kernels => no Winograd path)
-        self.fflag = self.cflag | ((L.CONV_OUT_BF16 | L.CONV_ALLSRC_BF16) if self.y16 else 0)      # forward launches
-        # fused train / scoring steps (no reconstruction store): the 1x1 output conv's forward and backward in ONE pass over y
-        # (vv_outconv_fwdbwd); the module API (forward -> outputs -> set_dout -> backward) keeps the two launches
-        self.fuse_outconv = os.environ.get('VV_FUSE_OUTCONV', '1') != '0'
-        wino_env = os.environ.get('VV_WINOGRAD', '1') != '0'
-        self.wino = wino_env and not self.cflag
-        self.wino_wgrad = wino_env and os.environ.get('VV_WINOGRAD_WGRAD', '1') != '0'
-        # VV_WINO_RING=0 / VV_CONV_RING=0: A/B switch, the 32x32-level launches stay on the per-tile kernels instead of the persistent
-        # LDS-DMA ring kernels of round 5 (fp32: wino_ring_kernel, all-bf16: conv_ring16_kernel; bit-identical results either way)
-        self.wino_flag = L.CONV_NO_RING if '0' in (os.environ.get('VV_WINO_RING', '1'), os.environ.get('VV_CONV_RING', '1')) else 0
-        self.wgrad_flag = 256                  # vv_wgrad_params.pad0 bit 8: Winograd form of the 3x3 weight gradient
-        # VV_WINO44 (round 5): which fp32 3x3 launches of a TRAIN step run as Winograd F(4x4,3x3) (vv_conv_wino44: 1.78x fewer matrix-core
-        # cycles than F(2x2); with the interpolation points scaled by 3/4 its rounding error is 1 - 3e-6 of the tensor maximum, 2 - 3 x
-        # F(2x2)'s).  'dgrad' (default): the DATA-GRADIENT launches the policy of _w44 takes -- a data gradient's rounding feeds no ReLU /
-        # max-pool gate and no BatchNorm statistic, and every parameter gradient's distance from float64 is the same to three digits
-        # with and without it (tools/w44_grad_probe.py), while the forward pass -- losses, activations, statistics -- stays bit-identical
-        # to the F(2x2) path; '1': forward launches too (median gradient distance as good, but a cancellation-heavy bias gradient
-        # crosses its calibrated bar on one of the two full-size test batches); 'all': every launch it takes; '0': none;
-        # 'set:f3,d10,...': explicit launches (probing)
-        self.w44_mode = os.environ.get('VV_WINO44', 'dgrad').lower()
-        self._w44_tables = {}
-        self._w44_eval_used = set()      # forward panels some eval plan routes to F(4x4): the only ones prepare_eval packs
-        # VV_WINO44_EVAL: the same choice for the eval-mode forward on the folded model (test.py:312-345 scoring; no gradients, scores
-        # and AUROC judged at 1e-3: a few 1e-6 per layer are noise there).  '1' (default): the policy of _w44; '0': none; 'all'
-        self.w44_eval_mode = os.environ.get('VV_WINO44_EVAL', '1').lower()
-        # first reduction pass of the BatchNorm backward inside the data-gradient launch that produces dA (where it is the only producer)
-        self.fuse_bn_sums = os.environ.get('VV_FUSE_BN_SUMS', '1') != '0'
         direct = [(k, v) for k, v in lay.pk.items() if not (self.wino and k[0] == 'c')]
         ents = (L.PackEntry * len(direct))()
         mx = 0
@@ -315,7 +343,6 @@ class UNetBank:
         # packed_eval), the producing conv applies the ReLU (VV_CONV_RELU) and every consumer reads plain values: no per-forward
         # weight packing, no BatchNorm launches, no activation arithmetic on the consumers' load path.  fp32 only: the mixed mode keeps
         # the rounding points its oracle restates.  VV_EVAL_FOLD=0 keeps the train-mode kernel family with running statistics.
-        self.eval_fold = (not self.cflag) and os.environ.get('VV_EVAL_FOLD', '1') != '0'
         self.eval_path = ('BatchNorm folded into filter + bias once per model state (vv_fold_bn), ReLU in the conv epilogue, plain loads'
                           if self.eval_fold else 'train-mode kernel family with running statistics')
         self.params_eval = self.packed_eval = None
@@ -455,15 +482,13 @@ class UNetBank:
     def _ks_bf16(self, groups, ntiles):
         """k-split of a bf16 weight-gradient launch (one workgroup per CU): the largest split that keeps the launch in ONE round of 256
         workgroups -- unless one round leaves more than a third of the chip idle (the 160-workgroup launches of the 4x4 level and the
-        first transposed conv at G = 10): then up to VV_WGRAD_BF16_ROUNDS (default 2) rounds, choosing the split with the smallest
-        rounds x ceil(tiles / split) + 1."""
+        first transposed conv at G = 10): then up to two rounds, choosing the split with the smallest rounds x ceil(tiles / split) + 1."""
         ncu = self.ncu
         one = max(1, min(ntiles, ncu // groups))
-        rmax = int(os.environ.get('VV_WGRAD_BF16_ROUNDS', '2'))
-        if groups * one * 3 > ncu * 2 or rmax <= 1:
+        if groups * one * 3 > ncu * 2:
             return one
         best, cost = one, -(-ntiles // one) + 1
-        for ks in range(one + 1, min(ntiles, ncu * rmax // groups) + 1):
+        for ks in range(one + 1, min(ntiles, ncu * 2 // groups) + 1):
             c = -(-groups * ks // ncu) * (-(-ntiles // ks) + 1)
             if c < cost:
                 best, cost = ks, c
@@ -476,10 +501,10 @@ class UNetBank:
         -- GEMM-K (input channels of the launch) >= 64 -- AND its coarser workgroups (64 tiles of 4x4 pixels x 32 channels, one per CU)
         still fill the chip evenly: at least two rounds of 256 workgroups with <= 10 % of the last round idle."""
         mode = self.w44_eval_mode if evalm else self.w44_mode
-        if not self.wino or mode in ('0', 'off') or (dgrad and l.idx == 0):
+        if not self.wino or mode == '0' or (dgrad and l.idx == 0):
             return False
-        if mode.startswith('set:'):                      # explicit launches, e.g. VV_WINO44=set:f3,f10,d10 (probing a policy)
-            return ('%s%d' % ('d' if dgrad else 'f', l.idx)) in mode[4:].split(',')
+        if isinstance(mode, frozenset):                  # explicit launches, e.g. VV_WINO44=set:f3,f10,d10 (probing a policy)
+            return ('%s%d' % ('d' if dgrad else 'f', l.idx)) in mode
         if mode == 'dgrad' and not dgrad:
             return False
         K, N = (l.cout, l.cin) if dgrad else (l.cinp, l.cout)
@@ -490,6 +515,18 @@ class UNetBank:
         wgs = self.Ga * (N // 32) * -(-self.lib.vv_wino44_ntiles(B, l.H) // 2)
         rounds = wgs / float(self.ncu)
         return K >= 64 and wgs >= 2 * self.ncu and rounds / math.ceil(rounds) >= 0.9
+
+    def _route(self, B, l, dgrad, flags, plan='train'):
+        """The kernel of conv layer l's 3x3 forward (dgrad=False) / data-gradient launch at batch size B with pad0 = flags, in the
+        'train' plans, the folded 'eval' plan or the unfolded eval plan ('eval_bn': no F(4x4) panels are packed for it):
+        (entry point, panel offset in the packed block, rows of per-tile partial sums the launch leaves = the tile count of
+        vv_bn_finalize / vv_bias_from_partials / a fused BatchNorm backward, BNBWD_PARTIALS_* flag of that BatchNorm backward)."""
+        lib, key = self.lib, 'c%d.%s' % (l.idx, 'd' if dgrad else 'f')
+        if plan != 'eval_bn' and self._w44(B, l, dgrad, evalm=plan == 'eval'):
+            return lib.vv_conv_wino44, self.lay.pkw44[key][0], lib.vv_wino44_ntiles(B, l.H), L.BNBWD_PARTIALS_PER_TILE44
+        if self.wino:
+            return lib.vv_conv_wino, self.lay.pkw[key][0], lib.vv_wino_ntiles(B, l.H), L.BNBWD_PARTIALS_PER_TILE
+        return lib.vv_conv_mfma, self.lay.pk[key][0], lib.vv_conv_ntiles2(B, l.H, l.H, L.CONV3, flags), L.BNBWD_PARTIALS_PER_CTILE
 
     def _w44_pack(self, B):
         """device pack table (vv_pack_wino44) of the panels the plans for batch size B use; (tensor, entries, max K*N) or None"""
@@ -567,22 +604,21 @@ class UNetBank:
         es = C.sizeof(L.PackEntry)
         hn, whn = self.pack_head_n, self.pack_w_head_n
         pack_tail = []          # events the third conv layer waits for (the tail packs run on the side stream)
-        ts = 0 if os.environ.get('VV_PACK_TAIL_MAIN', '0') == '1' else 1      # A/B switch: 1 = everything on the main stream
         if hn:
             P.add(lib.vv_pack_weights, (self.pack_table.data_ptr(), hn, Ga, pbase, U, kbase, UP, self.pack_max), 'pack')
         if self.wino and whn:
             P.add(lib.vv_pack_wino, (self.pack_table_w.data_ptr(), whn, Ga, pbase, U, kbase, UP, self.pack_w_max), 'pack_wino')
         if self.pack_n > hn:
             P.add(lib.vv_pack_weights, (self.pack_table.data_ptr() + hn * es, self.pack_n - hn, Ga, pbase, U, kbase, UP, self.pack_max),
-                  'pack_tail', stream=ts, record='pack_tail')
+                  'pack_tail', stream=1, record='pack_tail')
             pack_tail.append('pack_tail')
         if self.wino and self.pack_w_n > whn:
             P.add(lib.vv_pack_wino, (self.pack_table_w.data_ptr() + whn * es, self.pack_w_n - whn, Ga, pbase, U, kbase, UP,
-                                     self.pack_w_max), 'pack_wino_tail', stream=ts, record='pack_wino_tail')
+                                     self.pack_w_max), 'pack_wino_tail', stream=1, record='pack_wino_tail')
             pack_tail.append('pack_wino_tail')
         w44p = self._w44_pack(B) if train else None
         if w44p:
-            P.add(lib.vv_pack_wino44, (w44p[0].data_ptr(), w44p[1], Ga, pbase, U, kbase, UP, w44p[2]), 'pack_wino44', stream=ts,
+            P.add(lib.vv_pack_wino44, (w44p[0].data_ptr(), w44p[1], Ga, pbase, U, kbase, UP, w44p[2]), 'pack_wino44', stream=1,
                   record='pack_wino44')
             pack_tail.append('pack_wino44')
         abg = lay.cmax
@@ -590,19 +626,16 @@ class UNetBank:
         def conv(l):
             mode, s0, a, b, s1, csplit, chmap = self._src_for(ws, l)
             y = ws.y[l.idx]
-            w44 = train and self._w44(B, l, False)
-            panel = (lay.pkw44 if w44 else lay.pkw if self.wino else lay.pk)['c%d.f' % l.idx][0]
-            cp = L.ConvParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, s0, a, b, abg, s1, csplit, self.fflag | self.wino_flag, chmap,
+            fn, panel, nt, _ = self._route(B, l, False, self.fflag, 'train' if train else 'eval_bn')
+            cp = L.ConvParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, s0, a, b, abg, s1, csplit, self.fflag, chmap,
                               kbase + 4 * panel, UP, pbase + 4 * lay.p['c%d.b' % l.idx][0], U,
                               L.view(y, l.cout, 0, y.stride(0)), ws.stats.data_ptr() if train else None)
             P.keep.append(cp)
-            P.add(lib.vv_conv_wino44 if w44 else lib.vv_conv_wino if self.wino else lib.vv_conv_mfma, (C.byref(cp),), 'conv%d' % l.idx,
+            P.add(fn, (C.byref(cp),), 'conv%d' % l.idx,
                   # the third conv joins the side-stream packs; a launch of the FIRST TWO layers routed to F(4x4) (VV_WINO44=all | set:f0,f1)
                   # reads a panel of that side-stream pack too and waits for it on its own (under the two-stream schedules it
                   # read stale panels)
-                  wait=tuple(pack_tail) if l.idx == 2 else (('pack_wino44',) if (w44 and l.idx < 2) else ()))
-            nt = lib.vv_wino44_ntiles(B, l.H) if w44 else lib.vv_wino_ntiles(B, l.H) if self.wino else \
-                lib.vv_conv_ntiles2(B, l.H, l.H, L.CONV3, self.fflag)
+                  wait=tuple(pack_tail) if l.idx == 2 else (('pack_wino44',) if (fn is lib.vv_conv_wino44 and l.idx < 2) else ()))
             P.add(lib.vv_bn_finalize,
                   (Ga, l.cout, nt, B * l.H * l.H, 1 if train else 0, 0.1, 1e-5, ws.stats.data_ptr(), nt * 2 * l.cout,
                    pbase + 4 * lay.p['c%d.g' % l.idx][0], pbase + 4 * lay.p['c%d.beta' % l.idx][0], U,
@@ -674,7 +707,7 @@ class UNetBank:
         if self.wino:
             L.check(lib.vv_pack_wino(self.pack_table_w.data_ptr(), self.pack_w_n, G, self.params_eval.data_ptr(), lay.U,
                                      self.packed_eval.data_ptr(), lay.UP, self.pack_w_max, st), 'pack_wino (eval)')
-            if self.w44_eval_mode not in ('0', 'off'):
+            if self.w44_eval_mode != '0':
                 if getattr(self, '_w44_eval_table', None) is None and self._w44_eval_used:
                     keys = sorted(self._w44_eval_used)
                     ents = (L.PackEntry * len(keys))()
@@ -733,15 +766,15 @@ class UNetBank:
                                         pb.stride(0), 0), 'pool%d' % l.idx)
             mode, s0, a, b, s1, csplit = src(l)
             y = ws.y[l.idx]
-            w44 = self._w44(B, l, False, evalm=True)
-            if w44 and ('c%d.f' % l.idx) not in self._w44_eval_used:      # a panel no earlier plan used: repack on the next prepare_eval
+            fn, panel, _, _ = self._route(B, l, False, L.CONV_RELU, 'eval')
+            # a F(4x4) panel no earlier plan used: repack on the next prepare_eval
+            if fn is lib.vv_conv_wino44 and ('c%d.f' % l.idx) not in self._w44_eval_used:
                 self._w44_eval_used.add('c%d.f' % l.idx)
                 self._w44_eval_table, self._eval_key = None, None
-            panel = (lay.pkw44 if w44 else lay.pkw if self.wino else lay.pk)['c%d.f' % l.idx][0]
-            cp = L.ConvParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, s0, a, b, abg, s1, csplit, L.CONV_RELU | self.wino_flag, None,
+            cp = L.ConvParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, s0, a, b, abg, s1, csplit, L.CONV_RELU, None,
                               kbase + 4 * panel, UP, pbase + 4 * lay.p['c%d.b' % l.idx][0], U, L.view(y, l.cout, 0, y.stride(0)), None)
             P.keep.append(cp)
-            P.add(lib.vv_conv_wino44 if w44 else lib.vv_conv_wino if self.wino else lib.vv_conv_mfma, (C.byref(cp),), 'conv%d' % l.idx)
+            P.add(fn, (C.byref(cp),), 'conv%d' % l.idx)
         last = lay.convs[-1]
         y = ws.y[last.idx]
         op = L.OutconvParams(Ga, B, HW0 * HW0, self.nf, y.data_ptr(), y.stride(0), one, zero, abg,
@@ -754,7 +787,7 @@ class UNetBank:
 
     def _plan_backward(self, ws, B):
         lib, lay, Ga, g0, d = self.lib, self.lay, self.Ga, self.g0, self.device
-        U, UB, UP = lay.U, lay.UB, lay.UP
+        U, UP = lay.U, lay.UP
         nf = self.nf
         f = lambda *s: torch.empty(*s, device=d, dtype=torch.float32)
         P = _Plan()
@@ -780,68 +813,137 @@ class UNetBank:
         ws.DT = [f(Ga, B * H * H, ci) for (_, H, ci, co) in lay.convT]
         ws.dz2 = [f(Ga, B * HWp * nf), f(Ga, B * HWp * nf)]   # dy of consecutive layers alternate (weight-grad runs on a side stream)
         ws.dz = ws.dz2[0]
-        nblk = [lib.vv_bn_bwd_nblk(B, l.H, l.H, l.cout) for l in lay.convs]
         ws.bnscr = f(Ga, 2 * lay.cmax)
         ws.bscr = f(Ga, (B * HWp + 1023) // 1024 * lay.cmax)
         ws.dstats = f(Ga, max(max(lib.vv_conv_ntiles2(B, l.H, l.H, L.CONV3, self.cflag), lib.vv_conv_ntiles(B, l.H, l.H),
                                   lib.vv_wino_ntiles(B, l.H)) * 2 * l.cin for l in lay.convs if l.mode == L.IN_CAT))
-        # wgrad split-K choice: ~1024 workgroups per launch
-        wplan = {}
-        wmax = 0
+
+        # ---- every per-layer decision, made once before any launch: rec[i] for conv layer i, trec[u] for transposed conv u
+        # the consumers of act(y_j) besides the next conv layer: transposed conv, skip concat, pooling (BankLayout)
+        t_of = {sidx: u for u, (sidx, _, _, _) in enumerate(lay.convT)}
+        skip_of = {m.skip: m for m in lay.convs if m.mode == L.IN_CAT}
+        pool_of = {m.src: m for m in lay.convs if m.mode == L.IN_POOL}
+        act_of = {m.src: m for m in lay.convs if m.mode == L.IN_ACT}
+
+        def dA_for(i):
+            """(dA view, dpool ptr, dpool gstride) feeding the BN backward of conv layer i."""
+            if i == last.idx:
+                return L.view(ws.gA_last, nf, 0, ws.gA_last.stride(0)), None, 0
+            if i in t_of:
+                t = ws.DT[t_of[i]]
+                return L.view(t, t.shape[2], 0, t.stride(0)), None, 0
+            if i in skip_of:
+                dp = ws.D[pool_of[i].idx] if i in pool_of else None
+                return dcat_views(skip_of[i])[0], dp.data_ptr() if dp is not None else None, dp.stride(0) if dp is not None else 0
+            dn = ws.D[i + 1]
+            return L.view(dn, lay.convs[i + 1].cin, 0, dn.stride(0)), None, 0
+
+        def wgrad(kind, H, cinp, cout, bf16_flags, wide):
+            """weight-gradient launch: bf16 = the bf16-operand kernel (mixed precision, where vv_wgrad_bf16_plan takes the shape: HBM
+            bound, one workgroup of up to 512 registers per lane per CU), else the fp32 one; its k-split; kw; slabs per 32 x 32 tile"""
+            tiles = ((cinp + 31) // 32) * (cout // 32)
+            nt = lib.vv_wgrad_ntiles(kind, B, H, H)
+            # wide: the fp32 Winograd form, three workgroups per CU; 768 slots also at small batches (swept 256 / 384 / 512 / 768 at
+            # B = 32 and 256: fewer slabs shorten the grouped reduction but lengthen the weight-gradient launches by more)
+            ks = _pick_ksplit(Ga * tiles, nt, ncu=3 * self.ncu, max_wg=12 * self.ncu) if wide else \
+                _pick_ksplit(Ga * tiles, nt, ncu=self.ncu, max_wg=4 * self.ncu)
+            w = SimpleNamespace(bf16=False, ks=ks, kw=0)
+            ntb, nblk, kw = C.c_int32(), C.c_int32(), C.c_int32()
+            # (the flags of the launch go with the query: the all-bf16 weight gradient runs the LDS-ring kernel, whose tiling differs)
+            if self.cflag and lib.vv_wgrad_bf16_plan(kind | (bf16_flags << 8), B, H, H, cinp, cout,
+                                                     C.byref(ntb), C.byref(nblk), C.byref(kw)):
+                w = SimpleNamespace(bf16=True, ks=self._ks_bf16(Ga * nblk.value, ntb.value), kw=kw.value)
+            w.nslab = w.ks * max(w.kw, 1)
+            w.size = tiles * w.nslab * 9 * 1024
+            return w
+
+        rec = []
         for l in lay.convs:
-            nci, nco = (l.cinp + 31) // 32, l.cout // 32
-            nt = lib.vv_wgrad_ntiles(L.CONV3, B, l.H, l.H)
-            if self.wino_wgrad and not self.cflag:
-                # three workgroups per CU; 768 slots also at small batches (swept 256 / 384 / 512 / 768 at B = 32 and 256: fewer slabs
-                # shorten the grouped reduction but lengthen the weight-gradient launches by more)
-                ks = _pick_ksplit(Ga * nci * nco, nt, ncu=3 * self.ncu, max_wg=12 * self.ncu)
-            else:
-                ks = _pick_ksplit(Ga * nci * nco, nt, ncu=self.ncu, max_wg=4 * self.ncu)
-            wplan['c%d' % l.idx] = (ks, nci * nco * ks)
-            if self.cflag and self.bf16_wgrad:
-                # bf16 weight gradient: HBM bound, one workgroup (up to 512 registers per lane) per CU
-                ntb, nblk, kw = C.c_int32(), C.c_int32(), C.c_int32()
-                # (the flags of the launch go with the query: the all-bf16 weight gradient runs the LDS-ring kernel, whose tiling differs)
-                wfl = (L.WGRAD_DY_BF16 | L.WGRAD_X_BF16) if (self.dz16 and self.y16) else 0
-                if lib.vv_wgrad_bf16_plan(L.CONV3 | (wfl << 8), B, l.H, l.H, l.cinp, l.cout, C.byref(ntb), C.byref(nblk), C.byref(kw)):
-                    ks = self._ks_bf16(Ga * nblk.value, ntb.value)
-                    wplan['c%d' % l.idx] = (ks, nci * nco * ks * kw.value, kw.value)
-            wmax = max(wmax, wplan['c%d' % l.idx][1])
-        for u, (_, H, ci, co) in enumerate(lay.convT):
-            nci, nco = ci // 32, co // 32
-            nt = lib.vv_wgrad_ntiles(L.CONVT_FWD, B, H, H)
-            ks = _pick_ksplit(Ga * nci * nco, nt, ncu=self.ncu, max_wg=4 * self.ncu)
-            wplan['t%d' % u] = (ks, nci * nco * ks)
-            if self.cflag and self.bf16_wgrad:
-                ntb, nblk, kw = C.c_int32(), C.c_int32(), C.c_int32()
-                if lib.vv_wgrad_bf16_plan(L.CONVT_FWD, B, H, H, ci, co, C.byref(ntb), C.byref(nblk), C.byref(kw)):
-                    ks = self._ks_bf16(Ga * nblk.value, ntb.value)
-                    wplan['t%d' % u] = (ks, nci * nco * ks * kw.value, kw.value)
-            wmax = max(wmax, wplan['t%d' % u][1])
+            r = wgrad(L.CONV3, l.H, l.cinp, l.cout, (L.WGRAD_DY_BF16 | L.WGRAD_X_BF16) if self.y16 else 0,
+                      self.wino_wgrad and not self.cflag)
+            r.dA, r.dpool, r.dpg = dA_for(l.idx)
+            # mixed precision: both consumers of dy (data gradient, weight gradient) round it to bf16 -- BatchNorm backward stores it
+            # that way (same values, half the bytes written once and read twice)
+            r.dz16 = self.dz16 and r.bf16
+            r.dflags = (self.cflag | ((L.CONV_ALLSRC_BF16 if self.y16 else L.CONV_SRC_BF16) if r.dz16 else 0) |
+                        (L.CONV_OUT_BF16 if self.da16 else 0))
+            r.dgrad = self._route(B, l, True, r.dflags) if l.idx > 0 else None       # (entry point, panel, tiles, partials flag)
+            r.partials, r.bn_sums_of = 0, None
+            rec.append(r)
+        trec = [wgrad(L.CONVT_FWD, H, ci, co, 0, False) for (_, H, ci, co) in lay.convT]
+        for t in trec:
+            t.bn_sums_of = None
+
+        # fused BatchNorm-backward sums: the first pass of layer j's BatchNorm backward rides on the epilogue of the launch that produces
+        # dA_j (vv_conv_params.bn_partial) where that launch is its only producer; rec[j].partials = the BNBWD_PARTIALS_* flag of its
+        # rows (0: a vv_bn_bwd_reduce pass of its own).  The last conv layer's are written by vv_outconv_bwd.
+        rec[last.idx].partials = L.BNBWD_PARTIALS_PER_CUBE
+        for l in lay.convs:
+            # conv layer l's data gradient, when l reads relu(bn(y_j)) of the layer right before it and nobody else reads that
+            # activation.  fp32 Winograd path (every level), and all-bf16 tensors on the 32x32 level (vv_conv_mfma's kernel with 32-wide
+            # N tiles: HBM-latency-bound launches that absorb the extra read of z; on the deeper levels the stores belong to the
+            # single-issue producer waves of vv_conv_bf16.hip, where the sums would cost more than the separate pass)
+            r, j = rec[l.idx], l.idx - 1
+            if self.fuse_bn_sums and l.mode == L.IN_ACT and l.idx > 0 and l.src == j and j not in t_of and j not in skip_of \
+                    and j not in pool_of and (self.wino or (self.y16 and r.bf16 and l.H == 32 and l.cin % 64 != 0)):
+                r.bn_sums_of, rec[j].partials = j, r.dgrad[3]
+        # round 6: conv layers whose activation feeds ONLY a transposed conv (7 / 9 / 11): dA is that transposed conv's data gradient
+        # (vv_conv_mfma, VV_CONVT_DGRAD), which leaves the sums in its epilogue -- fp32 path only (the all-bf16 form of that launch was
+        # measured slower than launch + separate pass on config 4)
+        for u, (sidx, _, _, _) in enumerate(lay.convT):
+            if self.fuse_bn_sums and self.fuse_bn_sums_t and not self.cflag and sidx != last.idx and sidx not in skip_of \
+                    and sidx not in pool_of and sidx not in act_of:
+                trec[u].bn_sums_of, rec[sidx].partials = sidx, L.BNBWD_PARTIALS_PER_TTILE
+
+        # layers whose BatchNorm-backward apply pass is folded into its two consumers (VV_FUSE_BN_APPLY) -- vv_bn_bwd_sums leaves the
+        # per-channel table, the data gradient (VV_IN_BNBWD, per-tile F(2x2) kernel) and the weight gradient (dy_bn) read dA and z and
+        # form dy on load (bit-identical to the stored dy).  Candidates: no pooling fan-in (1 / 3 / 5 route dPool), fp32 Winograd path,
+        # a data gradient on the per-tile F(2x2) kernel at 16x16 / 8x8 (or none: layer 0); 7 keeps its pass.  Default = the layers
+        # measured faster folded at B = 256 (profiles/README.md): 0, 2, 4.  9 was measured slower (its data gradient loses the two-N-tile
+        # form); 8 / 10 / 11 run their data gradient on F(4x4) there and were not measured folded.
+        for l, r in zip(lay.convs, rec):
+            r.fold = (self.wino and self.wino_wgrad and l.idx in self.fold_bn_apply and l.idx != last.idx and l.cout <= 256
+                      and r.dpool is None and (l.idx == 0 or (l.H in (16, 8) and r.dgrad[0] is not lib.vv_conv_wino44)))
+
         # weight-gradient slabs: one region per layer (the reductions of a whole gradient bucket run as ONE grouped launch after the
         # bucket's last weight-gradient kernel, so every layer's slabs must still be there)
-        woff, wtot = {}, 0
-        for key, wpl in wplan.items():
-            woff[key] = wtot
-            wtot += wpl[1] * 9 * 1024
+        wtot = 0
+        for w in rec + trec:
+            w.woff, wtot = wtot, wtot + w.size
         ws.wpart = f(Ga, wtot)
+        ws.bntab = {i: f(Ga, L.BNBWD_TAB_ROWS * lay.convs[i].cout) for i, r in enumerate(rec) if r.fold}   # (read on the side stream)
         wpg = ws.wpart.stride(0)
-        group_reduce = os.environ.get('VV_GROUP_REDUCE', '1') != '0'
-        pending = []                     # (key, kind, cin, cinp, cout, nslab) of weight gradients whose reduction is still to be launched
+        pending = []                     # ReduceEntry fields of weight gradients whose reduction is still to be launched
 
-        def flush_reduce(label, **kw_):
-            """one vv_wgrad_reduce_grouped launch for everything in `pending` (all of it lies in one gradient bucket)"""
+        def reduce_wgrad(key, kind, cin, cinp, cout, w, label, bucket_done, **kw_):
+            """the reduction of a weight gradient's slabs: one vv_wgrad_reduce_grouped launch per gradient bucket (after the bucket's
+            last weight gradient), or one vv_wgrad_reduce per layer (VV_GROUP_REDUCE=0)"""
+            gptr, gstride = self._g(key + '.w')
+            if not self.group_reduce:
+                P.add(lib.vv_wgrad_reduce, (kind, Ga, cin, cinp, cout, w.nslab, ws.wpart.data_ptr() + 4 * w.woff, wpg, gptr, gstride),
+                      label, stream=1, **kw_)
+                return
+            pending.append((kind, cin, cinp, cout, w, gptr, gstride))
+            if not bucket_done:
+                return
             ents = (L.ReduceEntry * len(pending))()
             start = 0
-            for i, (key, kind, cin, cinp, cout, nslab) in enumerate(pending):
-                gptr, gstride = self._g(key + '.w')
-                ents[i] = L.ReduceEntry(kind, cin, cout, cout // 32, nslab, start, woff[key], (gptr - self.grads.data_ptr()) // 4, gstride)
+            for n, (kind, cin, cinp, cout, w, gptr, gstride) in enumerate(pending):
+                ents[n] = L.ReduceEntry(kind, cin, cout, cout // 32, w.nslab, start, w.woff, (gptr - self.grads.data_ptr()) // 4, gstride)
                 start += ((cinp + 31) // 32) * (cout // 32) * 36
             tab = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8).to(d)
             P.keep.append(tab)
             P.add(lib.vv_wgrad_reduce_grouped, (tab.data_ptr(), len(pending), start, Ga, ws.wpart.data_ptr(), wpg, self.grads.data_ptr()),
-                  label, **kw_)
+                  label, stream=1, **kw_)
             del pending[:]
+
+        def bn_sums(cp, j):
+            """the first pass of layer j's BatchNorm backward rides on this data-gradient launch's epilogue"""
+            yj = ws.y[j]
+            cp.bn_z, cp.bn_z_gstride = yj.data_ptr(), yj.stride(0)
+            cp.bn_a, cp.bn_b = self._p(ws.ab[0, j]), self._p(ws.ab[1, j])
+            cp.bn_mean, cp.bn_invstd = self._p(ws.ab[2, j]), self._p(ws.ab[3, j])
+            cp.bn_gstride, cp.bn_partial = abg, ws.bnpart.data_ptr()
 
         # 1x1 output conv
         y = ws.y[last.idx]
@@ -855,122 +957,25 @@ class UNetBank:
         P.add(lib.vv_outconv_bwd_reduce, (Ga, nf, B, ws.ocpart.data_ptr(), self._p(self.oc, g0), self._g('o.w')[0],
                                           self._g('o.b')[0], self._g('o.w')[1]), 'outconv_bwd_reduce')
 
-        def dA_for(l):
-            """(dA view, dpool ptr, dpool gstride) feeding the BN backward of conv layer l."""
-            i = l.idx
-            if i == last.idx:
-                return L.view(ws.gA_last, nf, 0, ws.gA_last.stride(0)), None, 0
-            nxt = lay.convs[i + 1] if i + 1 < len(lay.convs) else None
-            # who consumes act(y_i)?
-            cons_t = [u for u, (sidx, _, _, _) in enumerate(lay.convT) if sidx == i]
-            skip_of = [m for m in lay.convs if m.mode == L.IN_CAT and m.skip == i]
-            pool_of = [m for m in lay.convs if m.mode == L.IN_POOL and m.src == i]
-            if cons_t:
-                t = ws.DT[cons_t[0]]
-                return L.view(t, t.shape[2], 0, t.stride(0)), None, 0
-            if skip_of:
-                m = skip_of[0]
-                dp = ws.D[pool_of[0].idx] if pool_of else None
-                return (dcat_views(m)[0], dp.data_ptr() if dp is not None else None,
-                        dp.stride(0) if dp is not None else 0)
-            m = nxt
-            dn = ws.D[m.idx]
-            return L.view(dn, m.cin, 0, dn.stride(0)), None, 0
-
         order = [l.idx for l in reversed(lay.convs)]            # backward visiting order: 13, 12, ..., 0
 
-        def fused_producer(l):
-            """Index of the layer whose BatchNorm-backward sums the data-gradient launch of conv layer l can leave behind
-            (vv_conv_params.bn_partial): l reads relu(bn(y_j)) of the layer right before it and nobody else consumes that activation
-            (no pooling / skip / transposed-conv consumer), so dA_j is exactly this launch's output.  fp32 Winograd path (every
-            level), and all-bf16 tensors on the 32x32 level (vv_conv_mfma's kernel with 32-wide N tiles: HBM-latency-bound launches
-            that absorb the extra read of z; on the deeper levels the stores belong to the single-issue producer waves of
-            vv_conv_bf16.hip, where the sums would cost more than the separate pass)."""
-            if not self.fuse_bn_sums or l.mode != L.IN_ACT or l.idx == 0:
-                return None
-            if self.wino and not self.cflag:
-                pass
-            elif self.y16 and self.da16 and self.dz16 and len(wplan['c%d' % l.idx]) > 2 and l.H == 32 and l.cin % 64 != 0:
-                pass                           # (that launch carries VV_CONV_ALLSRC_BF16 | VV_CONV_OUT_BF16: dgrad_flags)
-            else:
-                return None
-            j = l.src
-            if j != l.idx - 1 or j == last.idx:
-                return None
-            if any(sidx == j for (sidx, _, _, _) in lay.convT) or any(m.mode == L.IN_CAT and m.skip == j for m in lay.convs) \
-                    or any(m.mode == L.IN_POOL and m.src == j for m in lay.convs):
-                return None
-            return j
-
-        fused = {fused_producer(l) for l in lay.convs} - {None}
-        # round 6: conv layers whose activation feeds ONLY a transposed conv (7 / 9 / 11): dA is that transposed conv's data gradient
-        # (vv_conv_mfma, VV_CONVT_DGRAD), which leaves the first BatchNorm-backward pass in its epilogue -- fp32 path only (the all-bf16
-        # form of that launch was measured slower than launch + separate pass on config 4); VV_FUSE_BN_SUMS_T=0 keeps the separate
-        # reduce pass for these three (A/B)
-        fused_t = {}
-        if self.fuse_bn_sums and os.environ.get('VV_FUSE_BN_SUMS_T', '1') != '0' and not self.cflag:
-            for u, (sidx, _, _, _) in enumerate(lay.convT):
-                others = any(m.mode == L.IN_CAT and m.skip == sidx for m in lay.convs) or any(m.mode == L.IN_POOL and m.src == sidx for m in lay.convs) \
-                    or any(m.mode == L.IN_ACT and m.src == sidx for m in lay.convs)
-                if not others and sidx != last.idx:
-                    fused_t[u] = sidx
-        fused |= set(fused_t.values())
-
-        # VV_FUSE_BN_APPLY: layers whose BatchNorm-backward apply pass is folded into its two consumers -- vv_bn_bwd_sums leaves the
-        # per-channel table, the data gradient (VV_IN_BNBWD, per-tile F(2x2) kernel) and the weight gradient (dy_bn) read dA and z and
-        # form dy on load (bit-identical to the stored dy).  '0' = every layer keeps its apply pass; 'set:2,4,...' = exactly these
-        # (probing).  Candidates: no pooling fan-in (1 / 3 / 5 route dPool), fp32 Winograd path, a data gradient on the per-tile
-        # F(2x2) kernel at 16x16 / 8x8 (or none: layer 0); 7 keeps its pass.  Default = the layers measured faster folded at B = 256
-        # (profiles/README.md): 0, 2, 4.  9 was measured slower (its data gradient loses the two-N-tile form); 8 / 10 / 11 run their
-        # data gradient on F(4x4) there and were not measured folded.
-        fold_env = os.environ.get('VV_FUSE_BN_APPLY', '1').lower()
-        fold_set = {int(t) for t in fold_env[4:].split(',') if t} if fold_env.startswith('set:') else \
-            (set() if fold_env in ('0', 'off') else {0, 2, 4})
-
-        def folded(l):
-            if l.idx not in fold_set or self.cflag or not self.wino or not self.wino_wgrad or l.idx == last.idx:
-                return False
-            if self.dz16 or self.da16 or self.y16 or l.H == 4 or l.cout > 256 or dA_for(l)[1] is not None:
-                return False
-            return l.idx == 0 or (l.H in (16, 8) and not self._w44(B, l, True))
-        fold = {l.idx for l in lay.convs if folded(l)}
-        ws.bntab = {i: f(Ga, L.BNBWD_TAB_ROWS * lay.convs[i].cout) for i in fold}   # one table per folded layer (read on the side stream)
-
-        def dgrad_flags(i):
-            # pad0 of layer i's data-gradient launch (also decides its tile count: vv_conv_ntiles2)
-            dz16 = bool(self.dz16 and len(wplan['c%d' % i]) > 2)
-            return (self.cflag | ((L.CONV_ALLSRC_BF16 if self.y16 else L.CONV_SRC_BF16) if dz16 else 0) |
-                    (L.CONV_OUT_BF16 if self.da16 else 0))
-
         def conv_bwd(l):
-            i = l.idx
+            i, r = l.idx, rec[l.idx]
             y = ws.y[i]
-            # mixed precision: both consumers of dy (data gradient, weight gradient) round it to bf16 -- let BatchNorm backward
-            # store it that way (same values, half the bytes written once and read twice)
-            wpl = wplan['c%d' % i]
-            dz16 = bool(self.dz16 and len(wpl) > 2)
             pos = order.index(i)
             dzb = ws.dz2[pos % 2]
-            # the layer visited two steps earlier used the same dy buffer: its weight-grad (side stream) must be done
-            reuse_wait = ('wdone%d' % order[pos - 2],) if pos >= 2 else ()
-            dA, dpool, dpg = dA_for(l)
-            from_outconv = i == last.idx           # its partial sums were written by vv_outconv_bwd
-            from_dgrad = i in fused                # ... by the data-gradient launch of layer i + 1
+            # the layer visited two steps earlier used the same dy buffer: its weight-grad (side stream) must be done (a folded layer
+            # stores no dy)
+            reuse_wait = ('wdone%d' % order[pos - 2],) if pos >= 2 and not r.fold else ()
             bp = L.BnBwdParams(Ga, B, l.H, l.H, l.cout,
-                               (L.BNBWD_DZ_BF16 if dz16 else 0) | (L.BNBWD_PARTIALS_PER_CUBE if from_outconv else 0) |
-                               ((L.BNBWD_PARTIALS_PER_TTILE if i in fused_t.values() else
-                                 L.BNBWD_PARTIALS_PER_TILE44 if self._w44(B, lay.convs[i + 1], True) else L.BNBWD_PARTIALS_PER_TILE if self.wino
-                                 else L.BNBWD_PARTIALS_PER_CTILE) if from_dgrad else 0) |
-                               (L.BNBWD_DA_BF16 if self.da16 else 0) | (L.BNBWD_Y_BF16 if self.y16 else 0), y.data_ptr(), y.stride(0), self._p(ws.ab[0, i]), self._p(ws.ab[1, i]),
-                               self._p(ws.ab[2, i]), self._p(ws.ab[3, i]), abg, dA, dpool, dpg, dzb.data_ptr(), dzb.stride(0),
+                               (L.BNBWD_DZ_BF16 if r.dz16 else 0) | r.partials | (L.BNBWD_DA_BF16 if self.da16 else 0) |
+                               (L.BNBWD_Y_BF16 if self.y16 else 0), y.data_ptr(), y.stride(0), self._p(ws.ab[0, i]), self._p(ws.ab[1, i]),
+                               self._p(ws.ab[2, i]), self._p(ws.ab[3, i]), abg, r.dA, r.dpool, r.dpg, dzb.data_ptr(), dzb.stride(0),
                                ws.bnpart.data_ptr())
             P.keep.append(bp)
-            fl = i in fold
-            if fl:
-                reuse_wait = ()                    # no dy buffer
-            if not (from_outconv or from_dgrad):
+            if not r.partials:
                 P.add(lib.vv_bn_bwd_reduce, (C.byref(bp),), 'bn_bwd_reduce%d' % i, wait=reuse_wait)
-            if fl:
+            if r.fold:
                 tab = ws.bntab[i]
                 P.add(lib.vv_bn_bwd_sums, (C.byref(bp), pbase + 4 * lay.p['c%d.g' % i][0], U, self._g('c%d.g' % i)[0],
                                            self._g('c%d.beta' % i)[0], self._g('c%d.g' % i)[1], tab.data_ptr(), tab.stride(0)),
@@ -978,101 +983,75 @@ class UNetBank:
             else:
                 P.add(lib.vv_bn_bwd_apply, (C.byref(bp), pbase + 4 * lay.p['c%d.g' % i][0], U, self._g('c%d.g' % i)[0],
                                             self._g('c%d.beta' % i)[0], self._g('c%d.g' % i)[1], ws.bnscr.data_ptr()), 'bn_bwd_apply%d' % i,
-                      record='dy%d' % i, wait=reuse_wait if (from_outconv or from_dgrad) else ())
+                      record='dy%d' % i, wait=reuse_wait if r.partials else ())
             # data gradient
             if i > 0:
                 Dl = ws.D[i]
-                w44 = self._w44(B, l, True)
+                fn, panel = r.dgrad[:2]
                 cp = L.ConvParams(L.CONV3, L.IN_PLAIN, Ga, B, l.H, l.H, l.cout, l.cout, l.cin,
-                                  L.View(dzb.data_ptr(), dzb.stride(0), l.cout, 0), None, None, 0, L.NULL_VIEW, 0,
-                                  dgrad_flags(i) | self.wino_flag, None,
-                                  kbase + 4 * (lay.pkw44 if w44 else lay.pkw if self.wino else lay.pk)['c%d.d' % i][0], UP, None, 0,
-                                  L.view(Dl, l.cin, 0, Dl.stride(0)),
+                                  L.View(dzb.data_ptr(), dzb.stride(0), l.cout, 0), None, None, 0, L.NULL_VIEW, 0, r.dflags, None,
+                                  kbase + 4 * panel, UP, None, 0, L.view(Dl, l.cin, 0, Dl.stride(0)),
                                   # concat layers: per-tile column sums of the data gradient = the transposed conv's bias gradient
                                   ws.dstats.data_ptr() if l.mode == L.IN_CAT else None)
-                if fl:                             # dy formed on load from dA, z and the layer's table
-                    cp.in_mode, cp.src0, cp.src1 = L.IN_BNBWD, dA, L.view(y, l.cout, 0, y.stride(0))
+                if r.fold:                         # dy formed on load from dA, z and the layer's table
+                    cp.in_mode, cp.src0, cp.src1 = L.IN_BNBWD, r.dA, L.view(y, l.cout, 0, y.stride(0))
                     cp.a, cp.ab_gstride = ws.bntab[i].data_ptr(), ws.bntab[i].stride(0)
                 if l.mode == L.IN_CAT:
                     v0, v1, osplit = dcat_views(l)
                     if osplit:
                         cp.out, cp.out1, cp.osplit = v0, v1, osplit
-                j = fused_producer(l)
-                if j is not None:                  # the first pass of layer j's BatchNorm backward rides on this launch's epilogue
-                    yj = ws.y[j]
-                    cp.bn_z, cp.bn_z_gstride = yj.data_ptr(), yj.stride(0)
-                    cp.bn_a, cp.bn_b = self._p(ws.ab[0, j]), self._p(ws.ab[1, j])
-                    cp.bn_mean, cp.bn_invstd = self._p(ws.ab[2, j]), self._p(ws.ab[3, j])
-                    cp.bn_gstride, cp.bn_partial = abg, ws.bnpart.data_ptr()
+                if r.bn_sums_of is not None:
+                    bn_sums(cp, r.bn_sums_of)
                 P.keep.append(cp)
                 # paired schedule: the MFMA data-gradient runs alone (the side stream has drained) ...
-                P.add(lib.vv_conv_wino44 if w44 else lib.vv_conv_wino if self.wino else lib.vv_conv_mfma, (C.byref(cp),), 'dgrad%d' % i,
-                      record='D%d' % i, pwait=('*side',))
+                P.add(fn, (C.byref(cp),), 'dgrad%d' % i, record='D%d' % i, pwait=('*side',))
             # weight gradient (side stream: only depends on dy_i and forward products).  Paired schedule: ... and the
             # weight-gradient starts when it is done, sharing the chip with the HBM-bound BatchNorm backward of the
             # next layer only.
             mode, s0, a, b, s1, csplit, chmap = self._src_for(ws, l)
-            ks, kw = wpl[0], (wpl[2] if len(wpl) > 2 else 0)           # kw > 0: the bf16-operand kernel (mixed precision)
-            # pad0 bit 8: Winograd F(2x2,3x3) form of the weight gradient (same tiles / slabs, 2.25x fewer MFMA cycles)
-            wflag = ((L.WGRAD_DY_BF16 if dz16 else 0) | (L.WGRAD_X_BF16 if (dz16 and self.y16) else 0)) if kw else \
+            # fp32 kernel, pad0 bit 8: Winograd F(2x2,3x3) form of the weight gradient (same tiles / slabs, 2.25x fewer MFMA cycles)
+            wflag = ((L.WGRAD_DY_BF16 | (L.WGRAD_X_BF16 if self.y16 else 0)) if r.dz16 else 0) if r.bf16 else \
                 (self.wgrad_flag if self.wino_wgrad else 0)
-            wp = L.WgradParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, ks, s0, a, b, abg, s1, csplit,
-                               wflag, chmap,
-                               L.View(dzb.data_ptr(), dzb.stride(0), l.cout, 0), ws.wpart.data_ptr() + 4 * woff['c%d' % i], wpg)
-            if fl:
+            wp = L.WgradParams(L.CONV3, mode, Ga, B, l.H, l.H, l.cin, l.cinp, l.cout, r.ks, s0, a, b, abg, s1, csplit, wflag, chmap,
+                               L.View(dzb.data_ptr(), dzb.stride(0), l.cout, 0), ws.wpart.data_ptr() + 4 * r.woff, wpg)
+            if r.fold:
                 # (side stream: dA, z and the table are written once per step, before 'dy%d' is recorded, and not again before wdone)
-                wp.dy, wp.dy_z = dA, L.view(y, l.cout, 0, y.stride(0))
+                wp.dy, wp.dy_z = r.dA, L.view(y, l.cout, 0, y.stride(0))
                 wp.dy_bn, wp.dy_bn_gstride = ws.bntab[i].data_ptr(), ws.bntab[i].stride(0)
             P.keep.append(wp)
-            P.add(lib.vv_wgrad_bf16 if kw else lib.vv_wgrad_mfma, (C.byref(wp),), 'wgrad%d' % i, stream=1, wait=('dy%d' % i,),
+            P.add(lib.vv_wgrad_bf16 if r.bf16 else lib.vv_wgrad_mfma, (C.byref(wp),), 'wgrad%d' % i, stream=1, wait=('dy%d' % i,),
                   record='wdone%d' % i, pwait=('*main',))
-            if group_reduce:
-                pending.append(('c%d' % i, L.CONV3, l.cin, l.cinp, l.cout, ks * max(kw, 1)))
-                if i in (4, 0):            # last weight gradient of the deep-encoder / shallow-encoder bucket (self.gb)
-                    flush_reduce('wgrad_reduce%d' % i, stream=1)
-            else:
-                P.add(lib.vv_wgrad_reduce, (L.CONV3, Ga, l.cin, l.cinp, l.cout, ks * max(kw, 1), ws.wpart.data_ptr() + 4 * woff['c%d' % i], wpg)
-                      + self._g('c%d.w' % i), 'wgrad_reduce%d' % i, stream=1)
+            # (4, 0: the last weight gradients of the deep-encoder / shallow-encoder buckets, self.gb)
+            reduce_wgrad('c%d' % i, L.CONV3, l.cin, l.cinp, l.cout, r, 'wgrad_reduce%d' % i, i in (4, 0))
 
         def convT_bwd(u, m):
             """m: the CAT conv layer that consumed convT u; its data gradient holds d(convT out) in channels [skipC, cin)."""
             sidx, H, ci, co = lay.convT[u]
+            t = trec[u]
             skipc = lay.convs[m.skip].cout
             dy = dcat_views(m)[1]
             DT = ws.DT[u]
             cp = L.ConvParams(L.CONVT_DGRAD, L.IN_PLAIN, Ga, B, H, H, co, co, ci, dy, None, None, 0, L.NULL_VIEW, 0,
                               self.cflag | (((L.CONV_ALLSRC_BF16 if self.y16 else L.CONV_SRC_BF16) | L.CONV_OUT_BF16) if self.da16 else 0), None,
                               kbase + 4 * lay.pk['t%d.d' % u][0], UP, None, 0, L.view(DT, ci, 0, DT.stride(0)), None)
-            if u in fused_t:                   # the first pass of layer sidx's BatchNorm backward rides on this launch's epilogue
-                yj = ws.y[sidx]
-                cp.bn_z, cp.bn_z_gstride = yj.data_ptr(), yj.stride(0)
-                cp.bn_a, cp.bn_b = self._p(ws.ab[0, sidx]), self._p(ws.ab[1, sidx])
-                cp.bn_mean, cp.bn_invstd = self._p(ws.ab[2, sidx]), self._p(ws.ab[3, sidx])
-                cp.bn_gstride, cp.bn_partial = abg, ws.bnpart.data_ptr()
+            if t.bn_sums_of is not None:
+                bn_sums(cp, t.bn_sums_of)
             P.keep.append(cp)
             P.add(lib.vv_conv_mfma, (C.byref(cp),), 'dgradT%d' % u, pwait=('*side',))
-            ntd = lib.vv_wino44_ntiles(B, m.H) if self._w44(B, m, True) else lib.vv_wino_ntiles(B, m.H) if self.wino else \
-                lib.vv_conv_ntiles2(B, m.H, m.H, L.CONV3, dgrad_flags(m.idx))
+            ntd = rec[m.idx].dgrad[2]          # pixel tiles of m's data-gradient launch, which left the column sums
             P.add(lib.vv_bias_from_partials, (Ga, m.cin, ntd, skipc, co, ws.dstats.data_ptr(), ntd * 2 * m.cin)
                   + self._g('t%d.b' % u), 'convT_bias%d' % u)
             y = ws.y[sidx]
-            wpl = wplan['t%d' % u]
-            ks, kw = wpl[0], (wpl[2] if len(wpl) > 2 else 0)
-            wp = L.WgradParams(L.CONVT_FWD, L.IN_ACT, Ga, B, H, H, ci, ci, co, ks, L.view(y, ci, 0, y.stride(0)),
+            wp = L.WgradParams(L.CONVT_FWD, L.IN_ACT, Ga, B, H, H, ci, ci, co, t.ks, L.view(y, ci, 0, y.stride(0)),
                                self._p(ws.ab[0, sidx]), self._p(ws.ab[1, sidx]), abg, L.NULL_VIEW, 0,
-                               ((L.WGRAD_DY_BF16 | (L.WGRAD_X_BF16 if self.y16 else 0)) if (kw and self.da16) else 0), None, dy,
-                               ws.wpart.data_ptr() + 4 * woff['t%d' % u], wpg)
+                               ((L.WGRAD_DY_BF16 | (L.WGRAD_X_BF16 if self.y16 else 0)) if (t.bf16 and self.da16) else 0), None, dy,
+                               ws.wpart.data_ptr() + 4 * t.woff, wpg)
             P.keep.append(wp)
             # side stream: its dy is the concat layer's data gradient (main stream) -- wait for it
-            P.add(lib.vv_wgrad_bf16 if kw else lib.vv_wgrad_mfma, (C.byref(wp),), 'wgradT%d' % u, stream=1,
+            P.add(lib.vv_wgrad_bf16 if t.bf16 else lib.vv_wgrad_mfma, (C.byref(wp),), 'wgradT%d' % u, stream=1,
                   wait=('D%d' % m.idx,), pwait=('*main',))
-            if group_reduce:
-                pending.append(('t%d' % u, L.CONVT_FWD, ci, ci, co, ks * max(kw, 1)))
-                if u == 0:                 # last weight gradient of the decoder bucket
-                    flush_reduce('wgradT_reduce0', stream=1, record='sideT0')
-            else:
-                P.add(lib.vv_wgrad_reduce, (L.CONVT_FWD, Ga, ci, ci, co, ks * max(kw, 1), ws.wpart.data_ptr() + 4 * woff['t%d' % u], wpg)
-                      + self._g('t%d.w' % u), 'wgradT_reduce%d' % u, stream=1, record='sideT%d' % u)
+            # (0: the last weight gradient of the decoder bucket)
+            reduce_wgrad('t%d' % u, L.CONVT_FWD, ci, ci, co, t, 'wgradT_reduce%d' % u, u == 0, record='sideT%d' % u)
 
         for l in reversed(lay.convs):
             conv_bwd(l)
