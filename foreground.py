@@ -6,9 +6,10 @@ frame instead of one ``cv2.resize`` call per box per frame), drop boxes whose fl
 the cubes under the grid block(s) the box falls in.  Outputs use the reference's file names and nesting so that either
 implementation can consume the other's files.
 
-The bounding boxes themselves come from ``raw_datasets/<ds>/bboxes_{train,test}_<mode>.npy`` (written by the reference's
-mmdet / motion detector stage, train.py:44-99, which is outside the hot path); the trivially computable 'frame' mode is
-produced here.
+The bounding boxes themselves come from ``raw_datasets/<ds>/bboxes_{train,test}_<mode>.npy``.  ``load_bboxes`` writes that
+file for the detector-free modes when it is absent (train.py:44-99): 'frame', 'simple_patch' and 'obj_det_with_motion', whose
+motion stage runs on the GPU (vec_vad_amd/motion.py) on top of whatever detector output ``bboxes_<mode>_obj_det.npy`` holds.
+The mmdet detector itself is not part of this build.
 """
 import os
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from utils import calc_block_idx
-from vad_datasets import frame_size, unified_dataset_interface
+from vad_datasets import frame_size, get_inputs, unified_dataset_interface
 
 
 def save_nested(path, nested, depth):
@@ -38,11 +39,55 @@ def save_nested(path, nested, depth):
     os.replace(tmp, final)
 
 
-def load_bboxes(c, mode, dataset=None):
-    """train.py:96-99 / test.py:92-96.  ``<raw_dataset_dir>/<ds>/bboxes_<mode>_<fg mode>.npy``; 'frame' mode needs no
-    detector and is generated when the file is absent."""
+def _motion_bboxes(c, mode, ap_path, device, log):
+    """'obj_det_with_motion' without a saved file (train.py:62-76): per frame, the appearance boxes (rows of ``ap_path``, the
+    file the reference's 'obj_det' mode saves, when it exists; none otherwise) followed by the motion boxes of the frame and
+    its two neighbours.  Consecutive frames go through the GPU in chunks: every frame of a chunk is decoded and uploaded once
+    and the windows, which repeat frames at video borders ('hard'), are index triples into the chunk."""
+    from vec_vad_amd.motion import motion_boxes
+    cp, ds = c['cp'], c['dataset_name']
+    dataset = unified_dataset_interface(dataset_name=ds, dir=os.path.join(c['raw_dataset_dir'], ds), context_frame_num=1,
+                                        mode=mode, border_mode='hard')
+    n = len(dataset)
+    if os.path.exists(ap_path):
+        ap_all = np.load(ap_path, allow_pickle=True)
+        if len(ap_all) != n:
+            raise ValueError('{} holds boxes of {} frames, the dataset has {}'.format(ap_path, len(ap_all), n))
+        ap_all = [np.asarray(b)[:, :4] if np.asarray(b).ndim == 2 else np.zeros((0, 4), np.float32) for b in ap_all]
+    else:
+        log('no {}: motion boxes only (no appearance boxes)'.format(ap_path))
+        ap_all = [np.zeros((0, 4), np.float32) for _ in range(n)]
+    per_launch = max(1, cp.getint('mi355x', 'motion_frames_per_launch', fallback=16))
+    all_bboxes = []
+    for s in range(0, n, per_launch):
+        e = min(s + per_launch, n)
+        log('Extracting bboxes of frames {}-{}, {} in total'.format(s + 1, e, n))
+        ranges = [dataset.context_range(i) for i in range(s, e)]
+        used = sorted({f for r in ranges for f in r})
+        local = {f: k for k, f in enumerate(used)}
+        frames = np.stack([get_inputs(dataset.all_frame_addr[f]) for f in used])             # [F,H,W,C] uint8, BGR
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).to(device)
+        win = [[local[f] for f in r] for r in ranges]
+        mt = motion_boxes(frames, win, ap_all[s:e], ds)
+        for i, m in zip(range(s, e), mt):
+            all_bboxes.append(np.concatenate((ap_all[i], m), axis=0) if m.shape[0] > 0 else ap_all[i])
+    return all_bboxes
+
+
+def load_bboxes(c, mode, dataset=None, device='cuda', log=print):
+    """train.py:44-99 / test.py:50-96.  ``<raw_dataset_dir>/<ds>/bboxes_<mode>_<fg mode>.npy`` is loaded when
+    ``<mode>_bbox_saved`` is set or the file exists.  Otherwise the detector-free modes are computed and saved there (an object
+    array of per-frame arrays, written atomically):
+      frame                 the whole frame (needs ``dataset`` for the frame count)
+      simple_patch          the (3,4) and (6,8) patch grids of train.py:81-86, 60 boxes per frame
+      obj_det_with_motion   the rows of ``bboxes_<mode>_obj_det.npy`` (what the reference's 'obj_det' mode saves: detector
+                            boxes after ``del_cover_bboxes``; first four columns) when that file exists, none otherwise,
+                            followed by the motion boxes found on the GPU (vec_vad_amd/motion.py), ``[mi355x]
+                            motion_frames_per_launch`` consecutive frames per launch
+    'obj_det' itself needs the mmdet detector, which is not part of this build: without a file it raises."""
     cp, ds, fg = c['cp'], c['dataset_name'], c['mode_fg']
-    path = os.path.join(c['raw_dataset_dir'], ds, 'bboxes_{}_{}.npy'.format(mode, fg))
+    ds_dir = os.path.join(c['raw_dataset_dir'], ds)
+    path = os.path.join(ds_dir, 'bboxes_{}_{}.npy'.format(mode, fg))
     if cp.getboolean(ds, '{}_bbox_saved'.format(mode)) or os.path.exists(path):
         return np.load(path, allow_pickle=True)
     if fg == 'frame' and dataset is not None:
@@ -50,9 +95,22 @@ def load_bboxes(c, mode, dataset=None):
         boxes = [np.array([[0, 0, w, h]]) for _ in range(len(dataset))]
         np.save(path, boxes)
         return boxes
-    raise NotImplementedError(
-        '{}_bbox_saved = False: the object-detector / motion foreground localisation (reference train.py:44-95: mmdet '
-        'cascade R-CNN + fore_det) is outside the hot path built here; produce {} with the reference once.'.format(mode, path))
+    if fg == 'simple_patch':
+        from fore_det.simple_patch import get_patch_loc
+        n = len(dataset) if dataset is not None else len(unified_dataset_interface(
+            dataset_name=ds, dir=ds_dir, context_frame_num=1, mode=mode, border_mode='hard'))
+        h, w = frame_size[ds][0], frame_size[ds][1]
+        grid = np.concatenate([get_patch_loc(h, w, h_num, w_num) for h_num, w_num in ((3, 4), (6, 8))], axis=0)
+        boxes = [grid.copy() for _ in range(n)]
+    elif fg == 'obj_det_with_motion':
+        boxes = _motion_bboxes(c, mode, os.path.join(ds_dir, 'bboxes_{}_obj_det.npy'.format(mode)), device, log)
+    else:
+        raise NotImplementedError(
+            '{}_bbox_saved = False with mode {!r}: the object detector (reference train.py:44-95: mmdet cascade R-CNN, '
+            'fore_det.get_ap_bboxes) is not part of this build; produce {} with the reference once.'.format(mode, fg, path))
+    save_nested(path, boxes, 1)
+    log('bboxes for {}ing data saved!'.format(mode))
+    return np.load(path, allow_pickle=True)
 
 
 def _datasets(c, mode, all_bboxes):

@@ -508,6 +508,27 @@ int vv_fusion_pack11(const float* x6, const float* img1, const float* s2_flow2, 
 int vv_crop_resize(const void* frames, int32_t is_f32, int32_t T, int32_t H, int32_t W, int32_t C, const int32_t* crops,
                    int32_t n, int32_t oh, int32_t ow, void* out, vv_stream stream);
 
+/* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
+ * vv_motion_mask: one launch for N windows of three frames.
+ *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats
+ *   frames; indices are clamped to [0, F)); ksize 3 | 5 = cv2.GaussianBlur(sigma 0): [1,2,1]/4 or [1,4,6,4,1]/16, separable,
+ *   BORDER_REFLECT_101, rounded half up once after both passes (H, W > ksize/2); per channel d = (|b0-b1| + |b1-b2|) mod 256,
+ *   set iff d > binary_thr; ap int32 [M][5] = window, x1, y1, x2, y2 (x2, y2 >= 0): every pixel of
+ *   [max(0,y1-extend), min(y2+extend,H)] x [max(0,x1-extend), min(x2+extend,W)] (inclusive) of that window is cleared;
+ *   mask uint8 [N][H][W] = 255 where any channel is set, else 0.  The blurred planes live in LDS only.
+ * vv_mask_boxes: cv2.findContours(RETR_EXTERNAL) + boundingRect + the reference's filter on mask uint8 [N][H][W] (non-zero =
+ *   foreground).  8-connected foreground components that touch the frame edge or are 4-adjacent to the 4-connected background
+ *   region reaching the frame edge; x, y, w, h = bounding rectangle; kept iff (w+1)*(h+1) > area_thr, w < 10 h and h < 10 w;
+ *   boxes int32 [N][cap][4] = max(0,x-extend), max(0,y-extend), min(x+w+extend,W), min(y+h+extend,H), in DESCENDING order of the
+ *   component's smallest linear pixel index; count int32 [N] = boxes found, which may exceed cap (the excess is not written).
+ *   workspace: vv_mask_boxes_workspace_bytes(N, H, W) bytes, 16-byte aligned (20 bytes per pixel).  Bit-identical run to run. */
+int vv_motion_mask(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* win, int32_t N,
+                   int32_t ksize, int32_t binary_thr, const int32_t* ap, int32_t M, int32_t extend, uint8_t* mask,
+                   vv_stream stream);
+int64_t vv_mask_boxes_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int vv_mask_boxes(const uint8_t* mask, int32_t N, int32_t H, int32_t W, int32_t area_thr, int32_t extend, int32_t cap,
+                  void* workspace, int64_t workspace_bytes, int32_t* count, int32_t* boxes, vv_stream stream);
+
 /* ---- score aggregation (test.py:330-358,387-399, utils.py:29-41) ----
  * vv_frame_scores: frame_scores[f] = max(frame_scores[f], max over cubes m in [frame_off[f], frame_off[f+1]) with
  *   paints[m] != 0 of  cube_stat[m] < 0 ? big : w_raw*(raw[m]-mu_r)/sd_r + w_of*(of[m]-mu_o)/sd_o ), float64;

@@ -15,8 +15,10 @@ What is different on purpose:
     nn.DataParallel; plain ``python train.py`` stays valid (1 GPU);
   * the epoch permutation is seeded (``[mi355x] shuffle_seed``) -- the reference shuffles unseeded.
 Cube extraction (train.py:102-226) runs through ``foreground.extract_train`` (crop + resize on the GPU) when
-``train_foreground_saved = False``; the detector stage that produces the boxes (train.py:44-95, mmdet) is outside the hot
-path -- keep ``train_bbox_saved = True``.
+``train_foreground_saved = False``.  With ``train_bbox_saved = False`` the boxes of the detector-free modes are computed first
+(``foreground.load_bboxes``: 'frame', 'simple_patch', and 'obj_det_with_motion' = the rows of ``bboxes_train_obj_det.npy``, if
+that file exists, plus the motion boxes found on the GPU); the mmdet detector itself (train.py:44-67) is not part of this build,
+so mode 'obj_det' needs its bbox file.
 """
 import os
 import sys
