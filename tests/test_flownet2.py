@@ -119,6 +119,69 @@ def test_conv2d_winograd_vs_torch_cpu(Cin, Cout, H, W, relu, monkeypatch):
     assert float(dst.t[..., :4].abs().max()) == 0 and float(dst.t[..., 4 + Cout:].abs().max()) == 0   # neighbours untouched
 
 
+# (precision, route, kind, R, stride, Cin, Cout, H, W): the smallest shapes that reach each route of the runner at batch 2 -- two-channel
+# deconv head, predict_flow head, row-K, direct on a K too short to split (fp16; fp32 splits it 3 ways) and split 8 (fp32) / 4 (fp16)
+# ways, direct deconv, Winograd
+REFRESH_CASES = [(p,) + c for p in ('fp32', 'fp16') for c in (
+    ('c2', 'deconv', 4, 2, 2, 2, 4, 6), ('n2', 'conv', 3, 1, 128, 2, 7, 9), ('rowk', 'conv', 7, 2, 3, 64, 16, 66),
+    ('direct', 'conv', 3, 1, 96, 64, 5, 13), ('splitk', 'conv', 1, 1, 256, 32, 16, 24), ('direct', 'deconv', 4, 2, 162, 16, 12, 20))] + \
+    [('fp32', 'wino', 'conv', 3, 1, 40, 64, 6, 64)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('prec,route,kind,R,stride,Cin,Cout,H,W', REFRESH_CASES)
+def test_runner_refreshes_panels_when_parameters_change(prec, route, kind, R, stride, Cin, Cout, H, W, monkeypatch):
+    """One _Runner, the same layer twice with its weight and bias changed in place in between: the second launch must read panels
+    of the changed parameters.  fp32 against the torch CPU op at the bar of test_conv2d_hip_vs_torch_cpu, fp16 against the half
+    graph at the one-ulp bar of test_conv2d_f16_within_one_ulp_of_half_graph."""
+    import torch.nn as nn
+    from vec_vad_amd import flownet2 as FN
+    from test_flownet2_fp16 import _half_layer_ref, _ulp16
+    if route == 'wino':
+        monkeypatch.setattr(FN, '_WINO_MIN_WGS', 1)
+    g = torch.Generator().manual_seed(R * 1000 + Cin + 3)
+    x = torch.randn(2, Cin, H, W, generator=g)
+    dt = torch.float16 if prec == 'fp16' else torch.float32
+    x = x.to(dt)
+    if kind == 'conv':
+        m = nn.Conv2d(Cin, Cout, R, stride=stride, padding=(R - 1) // 2)
+    else:
+        m = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1, bias=Cin != 2)
+    m = m.cuda()
+    src = FN._to_buf(x.cuda())
+    OH, OW = (2 * H, 2 * W) if kind == 'deconv' else ((H + 2 * ((R - 1) // 2) - R) // stride + 1, (W + 2 * ((R - 1) // 2) - R) // stride + 1)
+    r = FN._route(m, kind == 'deconv', 2, H, W, Cin, src.cs, FN._F16 if prec == 'fp16' else FN._F32, FN._cs(Cout + 12, dt))
+    assert r.kind == ('direct' if route == 'splitk' else route), r          # the case reaches the route it is here for
+    if route == 'splitk':
+        assert r.ks == (4 if prec == 'fp16' else 8), r
+    run = FN._Runner()
+    first = FN._Buf(2, OH, OW, Cout + 12, 'cuda', dt)
+    run(m, src, first, 8)
+    assert (('wino', id(m)) in run.cache) == (route == 'wino')
+    with torch.no_grad():
+        m.weight.mul_(-0.5)
+        if m.bias is not None:
+            m.bias.add_(1.0)
+    dst = FN._Buf(2, OH, OW, Cout + 12, 'cuda', dt)
+    run(m, src, dst, 8)
+    torch.cuda.synchronize()
+    out = dst.t[..., 8:8 + Cout].permute(0, 3, 1, 2).cpu()
+    w, b = m.weight.detach().cpu(), None if m.bias is None else m.bias.detach().cpu()
+    assert not torch.equal(out, first.t[..., 8:8 + Cout].permute(0, 3, 1, 2).cpu())
+    if prec == 'fp32':
+        ref = F.conv2d(x, w, b, stride=stride, padding=(R - 1) // 2) if kind == 'conv' else F.conv_transpose2d(x, w, b, stride=2, padding=1)
+        scale = float(ref.abs().max())
+        print('max |d| %.3g, bar %.3g' % (float((out - ref).abs().max()), 2e-5 * scale + 1e-6))
+        assert torch.allclose(out, ref, rtol=0, atol=2e-5 * scale + 1e-6), float((out - ref).abs().max())
+    else:
+        ref, absum = _half_layer_ref(kind, x, w, b, stride, R, False)
+        d = (out.double() - ref.double()).abs()
+        tol = _ulp16(ref.double()) + 2.0 ** -16 * absum
+        print('bit-equal fraction %.5f, max |d| / tol %.2f' % (float((out == ref).double().mean()), float((d / tol).max())))
+        assert bool(torch.isfinite(out).all())
+        assert float((d / tol).max()) <= 1.0, (float((d / tol).max()), float(d.max()))
+
+
 @pytest.mark.gpu
 def test_upsample4_vs_torch():
     from vec_vad_amd.flownet2 import _upsample4

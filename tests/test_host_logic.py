@@ -529,3 +529,101 @@ def test_wino44_routing_policy(monkeypatch):
     calls = ws.fwd[True].calls
     assert [c[2] for c in calls if c[2].startswith('pack')] == ['pack_wino', 'pack_tail', 'pack_wino_tail', 'pack_wino44']
     assert all(c[0] is b.lib.vv_conv_wino44 for c in calls if c[2].startswith('conv') and c[2][4:].isdigit())
+
+
+# (sub-networks, layer, input channels, H, W, fp32 route, fp16 route), route = (kind, KP, NP, ks): what every conv / deconv layer of
+# FlowNet2 launches on one 448 x 1024 pair, recorded from the launches of the runner as it was before _route existed (entry point and
+# Conv2dParams of each call; KP / NP of a head or a Winograd launch = the padded K and the N its kernel is given)
+FN2_ROUTES = [
+    ('flownetc', 'conv1', 3, 448, 1024, ('rowk', 32, 64, 1), ('rowk', 64, 64, 1)),
+    ('flownetc', 'conv3_1', 473, 56, 128, ('wino', 480, 256, 1), ('direct', 480, 256, 2)),
+    ('flownetc', 'conv_redir', 256, 56, 128, ('direct', 256, 32, 8), ('direct', 256, 32, 4)),
+    ('flownetc flownets_1 flownets_2', 'conv2', 64, 224, 512, ('direct', 64, 128, 1), ('direct', 64, 128, 1)),
+    ('flownetc flownets_1 flownets_2', 'predict_flow2', 194, 112, 256, ('n2', 224, 2, 1), ('n2', 224, 2, 1)),
+    ('flownetc flownets_1 flownets_2', 'predict_flow3', 386, 56, 128, ('n2', 416, 2, 1), ('n2', 416, 2, 1)),
+    ('flownetc flownets_1 flownets_2', 'predict_flow4', 770, 28, 64, ('n2', 800, 2, 1), ('n2', 800, 2, 1)),
+    ('flownetc flownets_1 flownets_2', 'predict_flow5', 1026, 14, 32, ('n2', 1056, 2, 1), ('n2', 1056, 2, 1)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv3', 128, 112, 256, ('direct', 128, 256, 2), ('direct', 128, 256, 2)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv4', 256, 56, 128, ('direct', 256, 512, 4), ('direct', 256, 512, 4)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv4_1', 512, 28, 64, ('wino', 512, 512, 1), ('direct', 512, 512, 4)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv5', 512, 28, 64, ('direct', 512, 512, 16), ('direct', 512, 512, 16)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv5_1', 512, 14, 32, ('direct', 512, 512, 16), ('direct', 512, 512, 8)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv6', 512, 14, 32, ('direct', 512, 1024, 16), ('direct', 512, 1024, 16)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'conv6_1', 1024, 7, 16, ('direct', 1024, 1024, 16), ('direct', 1024, 1024, 16)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'deconv2', 386, 56, 128, ('direct', 400, 64, 2), ('direct', 416, 64, 2)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'deconv3', 770, 28, 64, ('direct', 784, 128, 4), ('direct', 800, 128, 4)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'deconv4', 1026, 14, 32, ('direct', 1040, 256, 8), ('direct', 1056, 256, 8)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'deconv5', 1024, 7, 16, ('direct', 1024, 512, 8), ('direct', 1024, 512, 8)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'predict_flow6', 1024, 7, 16, ('n2', 1024, 2, 1), ('n2', 1024, 2, 1)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'upsampled_flow3_to_2', 2, 56, 128, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'upsampled_flow4_to_3', 2, 28, 64, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'upsampled_flow5_to_4', 2, 14, 32, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetc flownets_1 flownets_2 flownets_d', 'upsampled_flow6_to_5', 2, 7, 16, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetfusion', 'conv0', 11, 448, 1024, ('wino', 16, 64, 1), ('direct', 32, 64, 1)),
+    ('flownetfusion', 'deconv0', 162, 224, 512, ('direct', 176, 32, 1), ('direct', 192, 32, 1)),
+    ('flownetfusion', 'deconv1', 128, 112, 256, ('direct', 128, 32, 1), ('direct', 128, 32, 1)),
+    ('flownetfusion', 'inter_conv0', 82, 448, 1024, ('direct', 96, 32, 1), ('direct', 96, 32, 1)),
+    ('flownetfusion', 'inter_conv1', 162, 224, 512, ('wino', 168, 32, 1), ('direct', 192, 32, 1)),
+    ('flownetfusion', 'predict_flow0', 16, 448, 1024, ('n2', 32, 2, 1), ('n2', 32, 2, 1)),
+    ('flownetfusion', 'predict_flow1', 32, 224, 512, ('n2', 32, 2, 1), ('n2', 32, 2, 1)),
+    ('flownetfusion', 'predict_flow2', 128, 112, 256, ('n2', 128, 2, 1), ('n2', 128, 2, 1)),
+    ('flownetfusion', 'upsampled_flow1_to_0', 2, 224, 512, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetfusion', 'upsampled_flow2_to_1', 2, 112, 256, ('c2', 2, 2, 1), ('c2', 2, 2, 1)),
+    ('flownetfusion flownets_d', 'conv1', 64, 448, 1024, ('direct', 64, 64, 1), ('direct', 64, 64, 1)),
+    ('flownetfusion flownets_d', 'conv1_1', 64, 224, 512, ('wino', 64, 128, 1), ('direct', 64, 128, 1)),
+    ('flownetfusion flownets_d', 'conv2', 128, 224, 512, ('direct', 128, 128, 1), ('direct', 128, 128, 1)),
+    ('flownetfusion flownets_d', 'conv2_1', 128, 112, 256, ('wino', 128, 128, 1), ('direct', 128, 128, 1)),
+    ('flownets_1 flownets_2', 'conv1', 12, 448, 1024, ('direct', 16, 64, 1), ('direct', 32, 64, 1)),
+    ('flownets_1 flownets_2 flownets_d', 'conv3_1', 256, 56, 128, ('wino', 256, 256, 1), ('direct', 256, 256, 2)),
+    ('flownets_d', 'conv0', 6, 448, 1024, ('rowk', 24, 64, 1), ('rowk', 32, 64, 1)),
+    ('flownets_d', 'inter_conv2', 194, 112, 256, ('wino', 200, 64, 1), ('direct', 224, 64, 2)),
+    ('flownets_d', 'inter_conv3', 386, 56, 128, ('wino', 392, 128, 1), ('direct', 416, 128, 4)),
+    ('flownets_d', 'inter_conv4', 770, 28, 64, ('wino', 776, 256, 1), ('direct', 800, 256, 8)),
+    ('flownets_d', 'inter_conv5', 1026, 14, 32, ('direct', 1040, 512, 16), ('direct', 1056, 512, 16)),
+    ('flownets_d', 'predict_flow2', 64, 112, 256, ('n2', 64, 2, 1), ('n2', 64, 2, 1)),
+    ('flownets_d', 'predict_flow3', 128, 56, 128, ('n2', 128, 2, 1), ('n2', 128, 2, 1)),
+    ('flownets_d', 'predict_flow4', 256, 28, 64, ('n2', 256, 2, 1), ('n2', 256, 2, 1)),
+    ('flownets_d', 'predict_flow5', 512, 14, 32, ('n2', 512, 2, 1), ('n2', 512, 2, 1)),
+]
+
+
+def test_flownet2_route_table(monkeypatch):
+    """flownet2._route, the one place that decides what a layer launches, against the literal table above -- in both precisions --
+    and the three switches that move a route: VV_FN2_WINO, VV_FN2_ROWK, VV_FN2_KS_TARGET (module attributes, read at launch time)."""
+    from vec_vad_amd import flownet2 as FN
+    net = FN.FlowNet2()
+    convs = {n: m for n, m in net.named_modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))}
+    rows = [(s + '.' + lay, C, H, W, r32, r16) for subs, lay, C, H, W, r32, r16 in FN2_ROUTES for s in subs.split()]
+    assert len(rows) == len(set(r[0] for r in rows)) == len(convs)              # every conv / deconv of the network, once
+
+    def routes(prec, dtype):
+        out = {}
+        for name, C, H, W, _, _ in rows:
+            m = convs[name if name in convs else name + '.0']
+            out[name] = FN._route(m, isinstance(m, torch.nn.ConvTranspose2d), 1, H, W, C, FN._cs(C, dtype), prec)
+        return out
+    for prec, dtype, col in ((FN._F32, torch.float32, 4), (FN._F16, torch.float16, 5)):
+        got = {n: (r.kind, r.KP, r.NP, r.ks) for n, r in routes(prec, dtype).items()}
+        assert got == {r[0]: r[col] for r in rows}, [(n, got[n], r[col]) for r in rows for n in [r[0]] if got[n] != r[col]]
+    r32 = routes(FN._F32, torch.float32)
+    assert r32['flownetc.conv3_1'].label == 'conv3x3_s1_wino'                   # the bench hook's family names
+    assert r32['flownetc.predict_flow6'].label == 'conv3x3_s1_n2' and r32['flownets_1.upsampled_flow6_to_5'].label == 'deconv4x4_s2_n2'
+    assert r32['flownetc.conv1'].label == 'conv7x7_s2' and r32['flownets_d.deconv5'].label == 'deconv4x4_s2'
+    first = ('flownetc.conv1', 'flownets_1.conv1', 'flownets_d.conv0')          # the first layer of each encoder
+    monkeypatch.setattr(FN, '_WINO', False)
+    assert not any(r.kind == 'wino' for r in routes(FN._F32, torch.float32).values())
+    monkeypatch.setattr(FN, '_ROWK', False)
+    for prec, dtype in ((FN._F32, torch.float32), (FN._F16, torch.float16)):
+        r = routes(prec, dtype)
+        assert [(r[n].kind, r[n].KP, r[n].ks) for n in first] == [('direct', prec.kpad, 1)] * 3, [r[n] for n in first]
+    # row-K off alone: fp32 FlowNetSD conv0 (3x3 s1, 64 outputs, 448 x 1024) passes the Winograd gate, which comes next in the order of
+    # precedence -- as it did before _route existed; everything else as above
+    monkeypatch.setattr(FN, '_WINO', True)
+    r = routes(FN._F32, torch.float32)
+    assert not any(x.kind == 'rowk' for x in r.values())
+    assert [r[n].kind for n in first] == ['direct', 'direct', 'wino'] and r['flownets_d.conv0'].KP == 8
+    assert [x.kind for n, x in routes(FN._F16, torch.float16).items() if n in first] == ['direct'] * 3
+    monkeypatch.setattr(FN, '_ROWK', True)
+    monkeypatch.setattr(FN, '_KS_TARGET', 128)
+    for prec, dtype in ((FN._F32, torch.float32), (FN._F16, torch.float16)):
+        assert r32['flownetc.deconv5'].ks == 8 and routes(prec, dtype)['flownetc.deconv5'].ks == 4

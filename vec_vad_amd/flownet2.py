@@ -15,6 +15,7 @@ loading are unchanged) and are rounded to fp16 once, when their panels are packe
 (``vv_conv2d_f16``) with fp32 accumulation, the native ops and the plumbing widen fp16 inputs, compute in fp32 and round where
 the half graph materialises a tensor (no Winograd in this mode).
 """
+import collections
 import os
 import ctypes as C
 
@@ -30,27 +31,16 @@ from .flow_ops import Correlation, Resample2d, ChannelNorm, correlation, resampl
 _KS_TARGET = int(os.environ.get('VV_FN2_KS_TARGET', '256'))
 _WINO = os.environ.get('VV_FN2_WINO', '1') != '0'
 _WINO_MIN_WGS = int(os.environ.get('VV_FN2_WINO_MIN_WGS', '100'))
+_ROWK = os.environ.get('VV_FN2_ROWK', '1') != '0'
 
 
-def _c4(c):
-    return (c + 3) // 4 * 4
-
-
-def _c16(c):
-    return (c + 15) // 16 * 16
-
-
-def _c32(c):
-    return (c + 31) // 32 * 32
-
-
-def _c8(c):
-    return (c + 7) // 8 * 8
+def _ceil(c, q):
+    return (c + q - 1) // q * q
 
 
 def _cs(c, dtype):
     """channel stride of an NHWC activation buffer: 16-byte pixels groups (4 floats / 8 halves)."""
-    return _c8(c) if dtype == torch.float16 else _c4(c)
+    return _ceil(c, 8 if dtype == torch.float16 else 4)
 
 
 def conv(in_channels, out_channels, kernel_size=3, stride=1, bias=True, with_bn=False, with_relu=True):
@@ -143,202 +133,92 @@ class _Buf:
         return self.t[..., c0:c1].permute(0, 3, 1, 2).contiguous()
 
 
+class _Prec(collections.namedtuple('_Prec', 'tag dtype conv finish pack n2 c2 kpad chunk rowk rowk_pad half wino')):
+    """Everything that distinguishes the fp32 from the fp16 launch path: the entry points, the direct form's K padding (``kpad``)
+    and K chunk per split (``chunk(de, stride)``), the row-K gate (``rowk``: the (R, stride, channel stride) it takes, its K padded
+    to ``rowk_pad``), the panel dtype, whether bias / head weights are read as their ``.half()``-rounded copy, and Winograd."""
+
+
+_F32 = _Prec('', torch.float32, 'vv_conv2d_mfma', 'vv_conv2d_splitk_finish', 'vv_pack_conv2d', 'vv_conv3x3_n2', 'vv_deconv4x4_c2',
+             kpad=16, chunk=lambda de, stride: 16 if (de or stride == 1) else 8, rowk=((7, 2, 4), (3, 1, 8)), rowk_pad=8,
+             half=False, wino=True)
+_F16 = _Prec('f16', torch.float16, 'vv_conv2d_f16', 'vv_conv2d_splitk_finish_f16', 'vv_pack_conv2d_f16', 'vv_conv3x3_n2_f16',
+             'vv_deconv4x4_c2_f16', kpad=32, chunk=lambda de, stride: 16 if (not de and stride == 2) else 32,
+             rowk=((7, 2, 8), (3, 1, 8)), rowk_pad=16, half=True, wino=False)
+
+# kind: c2 | n2 | rowk | wino | direct.  K = the layer's input channels; KP / NP = the padded K / N of the panel that kind reads
+# (row-K: KP is the flattened (kx, c) run under one filter row); ks = split-K count (1: none); label = the bench hook's family name
+_Route = collections.namedtuple('_Route', 'kind de R stride OH OW K KP N NP ks label')
+
+
+def _route(m, de, B, H, W, C, cs, prec, dcs=None):
+    """What one conv (``de``: deconv) layer ``m`` launches on a [B,H,W,cs] input holding C channels, written into a buffer of
+    channel stride ``dcs`` (default: one of the layer's own width).  Pure: geometry, gates and the split-K policy, nothing else.
+    Precedence: two-channel head -> row-K -> Winograd -> direct."""
+    R, stride, K, N = m.kernel_size[0], m.stride[0], m.in_channels, m.out_channels
+    assert K == C, (K, C)
+    assert m.kernel_size == (R, R) and m.stride == (stride, stride)
+    if de:
+        assert (R, stride) == (4, 2) and m.padding == (1, 1)
+        OH, OW = 2 * H, 2 * W
+    else:
+        pad = (R - 1) // 2
+        assert m.padding == (pad, pad)
+        OH, OW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    label = '%s%dx%d_s%d' % ('deconv' if de else 'conv', R, R, stride) + ('_n2' if N == 2 else '')
+
+    def rt(kind, KP, NP, ks=1):
+        return _Route(kind, de, R, stride, OH, OW, K, KP, N, NP, ks, label + ('_wino' if kind == 'wino' else ''))
+    # two-channel layers (upsampled_flow 4x4 deconv, predict_flow 3x3 conv): dedicated bandwidth kernels; a two-output layer of
+    # another geometry takes the direct form
+    if N == 2 and de and K == 2:
+        return rt('c2', 2, 2)
+    if N == 2 and not de and (R, stride) == (3, 1):
+        return rt('n2', _ceil(K, 32), 2)
+    NP = _ceil(N, 32)
+    # few-channel first layers (FlowNetC conv1: 7x7 s2 on 3 channels; FlowNetSD conv0: 3x3 s1 on 6): kind 2 of the conv kernel,
+    # K = the flattened (kx, c) run under one filter row instead of taps x zero-padded channels.  VV_FN2_ROWK=0 switches it off
+    if not de and _ROWK and (R, stride, cs) in prec.rowk and C <= cs:
+        return rt('rowk', _ceil(R * cs, prec.rowk_pad), NP)
+    # large stride-1 3x3 layers in Winograd F(2x2,3x3) form (vv_conv2d_wino): the layers with at least VV_FN2_WINO_MIN_WGS (default
+    # 100) workgroups of 4 x 32 pixels x 32 channels -- where 2.25x fewer MFMAs is time (the H/32 and H/64 levels stay on the direct
+    # kernel with its split-K) -- on buffers below 2^31 bytes.  VV_FN2_WINO=0 switches it off
+    if prec.wino and _WINO and not de and (R, stride) == (3, 1) and N % 32 == 0 and H % 2 == 0 and W % 32 == 0 and \
+            B * ((H + 3) // 4) * (W // 32) * (N // 32) >= _WINO_MIN_WGS and \
+            B * H * W * max(cs, _ceil(N, 4) if dcs is None else dcs) * 4 < 2 ** 31:
+        return rt('wino', _ceil(K, 8), N)
+    # direct form; tiny-M / huge-K layers (the H/32 and H/64 levels) split the input-channel loop over workgroups
+    KP = _ceil(K, prec.kpad)
+    lh, lw = (H, W) if de else (OH, OW)
+    wgs = B * (4 if de else 1) * (NP // (64 if (NP % 64 == 0 and N > 32) else 32)) * ((lh + 7) // 8) * ((lw + 31) // 32)
+    nchunk = KP // prec.chunk(de, stride)
+    ks = 1
+    if wgs < 256 and nchunk >= 4:
+        ks = max(1, min(nchunk // 2, _KS_TARGET // wgs, 16))
+    return rt('direct', KP, NP, ks)
+
+
 class _Runner:
-    """Launches one conv / deconv layer; packed weight panels are cached per module and refreshed when the parameter
-    tensor changes (load_state_dict bumps ``_version``)."""
+    """Launches one conv / deconv layer as ``_route`` says; packed weight panels are cached per module and refreshed when the
+    parameter tensors change (load_state_dict bumps ``_version``)."""
 
     def __init__(self):
         self.lib = L.lib()
         self.cache = {}
         self.hook = None        # hook(label, flop, e0, e1): HIP events around every conv launch (bench diagnostics, eager mode only)
-        self.last_wino = False
-
-    def _packed(self, m):
-        key = id(m)
-        ver = (m.weight.data_ptr(), m.weight._version)
-        ent = self.cache.get(key)
-        if ent is not None and ent[0] == ver:
-            return ent[1]
-        w = m.weight.detach().contiguous().float()
-        transposed = isinstance(m, nn.ConvTranspose2d)
-        K, N = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
-        taps = w.shape[2] * w.shape[3]
-        KP, NP = _c16(K), _c32(N)
-        packed = torch.empty(taps * KP * NP, device=w.device, dtype=torch.float32)
-        L.check(self.lib.vv_pack_conv2d(w.data_ptr(), packed.data_ptr(), taps, K, KP, N, NP, 1 if transposed else 0,
-                                        torch.cuda.current_stream(w.device).cuda_stream), 'pack_conv2d')
-        self.cache[key] = (ver, packed, K, KP, N, NP)
-        return packed
-
-    def _flow_head(self, m, de, src, dst, dst_coff, slope, stream):
-        """Two-channel layers (predict_flow 3x3 conv, upsampled_flow 4x4 deconv): dedicated bandwidth kernels."""
-        bias = m.bias.data_ptr() if m.bias is not None else None
-        assert m.in_channels == src.C, (m.in_channels, src.C)
-        if de:
-            if m.in_channels != 2 or m.kernel_size != (4, 4) or m.stride != (2, 2) or m.padding != (1, 1):
-                return False
-            assert (dst.H, dst.W) == (2 * src.H, 2 * src.W) and dst_coff + 2 <= dst.cs
-            w = m.weight.detach()
-            assert w.is_contiguous() and w.dtype == torch.float32
-            L.check(self.lib.vv_deconv4x4_c2(src.t.data_ptr(), src.cs, src.B, src.H, src.W, w.data_ptr(), bias, slope,
-                                             dst.t.data_ptr(), dst.cs, dst_coff, stream), 'deconv4x4_c2')
-            return True
-        if m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1):
-            return False
-        assert (dst.H, dst.W) == (src.H, src.W) and dst_coff + 2 <= dst.cs
-        key = ('n2', id(m))
-        ver = (m.weight.data_ptr(), m.weight._version)
-        ent = self.cache.get(key)
-        if ent is None or ent[0] != ver:
-            w = m.weight.detach().float()                      # [2][Cin][3][3]
-            cin = w.shape[1]
-            cp = (cin + 31) // 32 * 32
-            wq = torch.zeros(9, cp // 4, 2, 4, device=w.device, dtype=torch.float32)
-            wp = torch.zeros(2, cp, 3, 3, device=w.device, dtype=torch.float32)
-            wp[:, :cin] = w
-            wq.copy_(wp.permute(2, 3, 1, 0).reshape(9, cp // 4, 4, 2).permute(0, 1, 3, 2))
-            ent = (ver, wq.contiguous(), cp // 4)
-            self.cache[key] = ent
-        L.check(self.lib.vv_conv3x3_n2(src.t.data_ptr(), src.cs, src.B, src.H, src.W, m.in_channels, ent[1].data_ptr(), ent[2],
-                                       bias, slope, dst.t.data_ptr(), dst.cs, dst_coff, stream), 'conv3x3_n2')
-        return True
-
-    def _wino(self, m, src, dst, dst_coff, slope, stream):
-        """Large stride-1 3x3 layers in Winograd F(2x2,3x3) form (vv_conv2d_wino): the layers with at least
-        VV_FN2_WINO_MIN_WGS (default 100) workgroups of 4 x 32 pixels x 32 channels -- where 2.25x fewer MFMAs is time (the H/32 and H/64 levels stay on the direct
-        kernel with its split-K).  VV_FN2_WINO=0 switches it off."""
-        if not _WINO or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.out_channels % 32:
-            return False
-        if src.H % 2 or src.W % 32 or src.B * ((src.H + 3) // 4) * (src.W // 32) * (m.out_channels // 32) < _WINO_MIN_WGS:
-            return False
-        if src.t.numel() * 4 >= 2 ** 31 or dst.t.numel() * 4 >= 2 ** 31:
-            return False
-        assert m.in_channels == src.C and (dst.H, dst.W) == (src.H, src.W) and dst_coff + m.out_channels <= dst.cs
-        key = ('wino', id(m))
-        ver = (m.weight.data_ptr(), m.weight._version)
-        ent = self.cache.get(key)
-        if ent is None or ent[0] != ver:
-            w = m.weight.detach().contiguous().float()          # [Cout][Cin][3][3]
-            N, K = w.shape[0], w.shape[1]
-            KP = (K + 7) // 8 * 8
-            panel = torch.empty(16 * KP * N, device=w.device, dtype=torch.float32)
-            tab = torch.frombuffer(bytearray(bytes((L.PackEntry * 1)(L.PackEntry(0, 0, 0, K, KP, N)))), dtype=torch.uint8).to(w.device)
-            L.check(self.lib.vv_pack_wino(tab.data_ptr(), 1, 1, w.data_ptr(), w.numel(), panel.data_ptr(), panel.numel(), KP * N, stream),
-                    'pack_wino')
-            ent = (ver, panel, KP, tab)
-            self.cache[key] = ent
-        bias = m.bias.data_ptr() if m.bias is not None else None
-        L.check(self.lib.vv_conv2d_wino(src.t.data_ptr(), src.cs, 0, src.t.numel(), ent[1].data_ptr(), bias, slope, dst.t.data_ptr(),
-                                        dst.cs, dst_coff, src.B, src.H, src.W, ent[2], m.out_channels, stream), 'conv2d_wino')
-        self.last_wino = True           # (bench diagnostics: this launch executed 16/36 of the direct form's multiply-adds)
-        return True
-
-    def _rowk(self, m, src, dst, dst_coff, slope, stream):
-        """Few-channel first layers (FlowNetC conv1: 7x7 s2 on 3 channels; FlowNetSD conv0: 3x3 s1 on 6): vv_conv2d_mfma kind 2,
-        K = the flattened (kx, c) run under one filter row instead of taps x 16 zero-padded channels."""
-        R, stride, cs = m.kernel_size[0], m.stride[0], src.cs
-        if os.environ.get('VV_FN2_ROWK', '1') == '0' or (R, stride, cs) not in ((7, 2, 4), (3, 1, 8)) or m.kernel_size[1] != R:
-            return False
-        pad = (R - 1) // 2
-        if m.padding != (pad, pad) or m.in_channels != src.C or src.C > cs:
-            return False
-        KF = (R * cs + 7) // 8 * 8
-        N = m.out_channels
-        NP = _c32(N)
-        key = ('rowk', id(m))
-        ver = (m.weight.data_ptr(), m.weight._version)
-        ent = self.cache.get(key)
-        if ent is None or ent[0] != ver:
-            w = m.weight.detach().float()                                  # [N][Cin][ky][kx]
-            wr = torch.zeros(N, KF, R, device=w.device, dtype=torch.float32)
-            wr[:, :R * cs].view(N, R, cs, R)[:, :, :m.in_channels] = w.permute(0, 3, 1, 2)      # [N][kx][c][ky]
-            packed = torch.empty(R * KF * NP, device=w.device, dtype=torch.float32)
-            L.check(self.lib.vv_pack_conv2d(wr.data_ptr(), packed.data_ptr(), R, KF, KF, N, NP, 0,
-                                            torch.cuda.current_stream(w.device).cuda_stream), 'pack_conv2d (row-K)')
-            ent = (ver, packed)
-            self.cache[key] = ent
-        OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
-        assert (dst.H, dst.W) == (OH, OW) and dst_coff + N <= dst.cs
-        bias = m.bias.data_ptr() if m.bias is not None else None
-        p = L.Conv2dParams(2, R, stride, src.B, src.H, src.W, KF, KF, N, NP, src.view(0), ent[1].data_ptr(), bias, slope, 0,
-                           dst.view(dst_coff))
-        L.check(self.lib.vv_conv2d_mfma(C.byref(p), stream), 'conv2d row-K %dx%d s%d %d->%d' % (R, R, stride, m.in_channels, N))
-        return True
 
     def __call__(self, layer, src, dst, dst_coff=0):
         if self.hook is None:
-            return self._launch(layer, src, dst, dst_coff)
-        m = layer[0] if isinstance(layer, nn.Sequential) else layer
-        de = isinstance(m, nn.ConvTranspose2d)
-        label = '%s%dx%d_s%d' % ('deconv' if de else 'conv', m.kernel_size[0], m.kernel_size[1], m.stride[0])
-        if m.out_channels == 2:
-            label += '_n2'
-        oh, ow = dst.H, dst.W
-        flop = 2.0 * src.B * (src.H * src.W if de else oh * ow) * m.in_channels * m.out_channels * m.kernel_size[0] * m.kernel_size[1]
+            self._launch(layer, src, dst, dst_coff)
+            return dst
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        self.last_wino = False
         e0.record()
         r = self._launch(layer, src, dst, dst_coff)
         e1.record()
-        self.hook(label + ('_wino' if self.last_wino else ''), flop, e0, e1)
-        return r
-
-    def _launch(self, layer, src, dst, dst_coff=0):
-        """layer: nn.Sequential(Conv2d|ConvTranspose2d[, LeakyReLU]) or a bare Conv2d / ConvTranspose2d."""
-        if isinstance(layer, nn.Sequential):
-            m = layer[0]
-            slope = 0.1 if len(layer) > 1 else 1.0
-        else:
-            m, slope = layer, 1.0
-        de = isinstance(m, nn.ConvTranspose2d)
-        stream = torch.cuda.current_stream(src.t.device).cuda_stream
-        if src.t.dtype == torch.float16:
-            assert dst.t.dtype == torch.float16
-            return self._launch_f16(m, de, slope, src, dst, dst_coff, stream)
-        if m.out_channels == 2 and self._flow_head(m, de, src, dst, dst_coff, slope, stream):
-            return dst
-        if not de and self._rowk(m, src, dst, dst_coff, slope, stream):
-            return dst
-        if not de and self._wino(m, src, dst, dst_coff, slope, stream):
-            return dst
-        packed = self._packed(m)
-        _, _, K, KP, N, NP = self.cache[id(m)]
-        assert K == src.C, (K, src.C)
-        if de:
-            assert m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)
-            OH, OW = 2 * src.H, 2 * src.W
-            R, stride = 4, 2
-        else:
-            R, stride = m.kernel_size[0], m.stride[0]
-            pad = (R - 1) // 2
-            assert m.padding == (pad, pad)
-            OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
-        assert (dst.H, dst.W) == (OH, OW), ((dst.H, dst.W), (OH, OW))
-        assert dst_coff + N <= dst.cs
-        bias = m.bias.data_ptr() if m.bias is not None else None
-        # tiny-M / huge-K layers (the H/32 and H/64 levels): split the input-channel loop over workgroups
-        lh, lw = (src.H, src.W) if de else (OH, OW)
-        wgs = src.B * (4 if de else 1) * (NP // (64 if (NP % 64 == 0 and N > 32) else 32)) * ((lh + 7) // 8) * ((lw + 31) // 32)
-        nchunk = KP // (16 if (de or stride == 1) else 8)
-        ks = 1
-        if wgs < 256 and nchunk >= 4:
-            ks = max(1, min(nchunk // 2, _KS_TARGET // wgs, 16))
-        if ks > 1:
-            M = src.B * OH * OW
-            ws = torch.empty(ks * M * NP, device=src.t.device, dtype=torch.float32)
-            p = L.Conv2dParams(1 if de else 0, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(),
-                               None, 1.0, ks, L.View(ws.data_ptr(), 0, NP, 0))
-            L.check(self.lib.vv_conv2d_mfma(C.byref(p), stream), 'conv2d split-k')
-            L.check(self.lib.vv_conv2d_splitk_finish(ws.data_ptr(), ks, M, N, NP, bias, slope, dst.t.data_ptr(), dst.cs, dst_coff,
-                                                     stream), 'conv2d split-k finish')
-            return dst
-        p = L.Conv2dParams(1 if de else 0, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(),
-                           bias, slope, 0, dst.view(dst_coff))
-        L.check(self.lib.vv_conv2d_mfma(C.byref(p), stream), 'conv2d %dx%d s%d %d->%d' % (R, R, stride, K, N))
+        # (a '_wino' launch executed 16/36 of these multiply-adds)
+        self.hook(r.label, 2.0 * src.B * (src.H * src.W if r.de else r.OH * r.OW) * r.K * r.N * r.R * r.R, e0, e1)
         return dst
 
-
-    # ---- fp16 activations: the panels hold the .half()-rounded parameters, cached apart from the fp32 ones
     def _cached(self, key, m, make):
         ver = (m.weight.data_ptr(), m.weight._version, None if m.bias is None else (m.bias.data_ptr(), m.bias._version))
         ent = self.cache.get(key)
@@ -347,101 +227,83 @@ class _Runner:
             self.cache[key] = ent
         return ent[1]
 
-    def _bias16(self, m):
-        if m.bias is None:
-            return None
-        return self._cached(('f16bias', id(m)), m, lambda: m.bias.detach().half().float().contiguous()).data_ptr()
+    def _param(self, m, name, prec):
+        """The bias / a head's weights as the kernels read them: the parameter's own storage, or its fp16-rounded copy (cached)."""
+        t = getattr(m, name)
+        if t is None or not prec.half:
+            return t
+        return self._cached((prec.tag + name, id(m)), m, lambda: t.detach().half().float().contiguous())
 
-    def _launch_f16(self, m, de, slope, src, dst, dst_coff, stream):
-        lib = self.lib
-        bias = self._bias16(m)
-        assert m.in_channels == src.C, (m.in_channels, src.C)
-        if m.out_channels == 2 and de and m.in_channels == 2:
-            assert m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)
-            assert (dst.H, dst.W) == (2 * src.H, 2 * src.W) and dst_coff + 2 <= dst.cs
-            w = self._cached(('f16c2', id(m)), m, lambda: m.weight.detach().half().float().contiguous())
-            L.check(lib.vv_deconv4x4_c2_f16(src.t.data_ptr(), src.cs, src.B, src.H, src.W, w.data_ptr(), bias, slope,
-                                            dst.t.data_ptr(), dst.cs, dst_coff, stream), 'deconv4x4_c2_f16')
-            return dst
-        if m.out_channels == 2 and not de and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1):
-            assert (dst.H, dst.W) == (src.H, src.W) and dst_coff + 2 <= dst.cs
+    def _panel(self, m, r, prec, cs, stream):
+        """The weights of ``m`` in the layout the kernel of ``r.kind`` reads (``cs``: the input's channel stride).  In fp16 mode this
+        is where they are rounded to fp16, once."""
+        w = m.weight.detach().contiguous().float()
+        if r.kind == 'n2':                                  # [2][Cin][3][3] -> [tap][Cin / 4][2][4]
+            wp = torch.zeros(2, r.KP, 3, 3, device=w.device, dtype=torch.float32)
+            wp[:, :r.K] = w.half().float() if prec.half else w
+            return wp.permute(2, 3, 1, 0).reshape(9, r.KP // 4, 4, 2).permute(0, 1, 3, 2).contiguous()
+        if r.kind == 'wino':
+            panel = torch.empty(16 * r.KP * r.N, device=w.device, dtype=torch.float32)
+            tab = torch.frombuffer(bytearray(bytes((L.PackEntry * 1)(L.PackEntry(0, 0, 0, r.K, r.KP, r.N)))), dtype=torch.uint8).to(w.device)
+            L.check(self.lib.vv_pack_wino(tab.data_ptr(), 1, 1, w.data_ptr(), w.numel(), panel.data_ptr(), panel.numel(), r.KP * r.N,
+                                          stream), 'pack_wino')
+            return panel
+        taps, K = r.R * r.R, r.K
+        if r.kind == 'rowk':                                # R "taps" (the filter rows) of K = KP: [N][Cin][ky][kx] -> [N][kx][c][ky]
+            wr = torch.zeros(r.N, r.KP, r.R, device=w.device, dtype=torch.float32)
+            wr[:, :r.R * cs].view(r.N, r.R, cs, r.R)[:, :, :r.K] = w.permute(0, 3, 1, 2)
+            w, taps, K = wr, r.R, r.KP
+        panel = torch.empty(taps * r.KP * r.NP, device=w.device, dtype=prec.dtype)
+        L.check(getattr(self.lib, prec.pack)(w.data_ptr(), panel.data_ptr(), taps, K, r.KP, r.N, r.NP, 1 if r.de else 0, stream),
+                '%s (%s)' % (prec.pack, r.kind))
+        return panel
 
-            def make_n2():
-                w = m.weight.detach().half().float()                     # [2][Cin][3][3]
-                cin = w.shape[1]
-                cp = _c32(cin)
-                wp = torch.zeros(2, cp, 3, 3, device=w.device, dtype=torch.float32)
-                wp[:, :cin] = w
-                return wp.permute(2, 3, 1, 0).reshape(9, cp // 4, 4, 2).permute(0, 1, 3, 2).contiguous()
-            wq = self._cached(('f16n2', id(m)), m, make_n2)
-            L.check(lib.vv_conv3x3_n2_f16(src.t.data_ptr(), src.cs, src.B, src.H, src.W, m.in_channels, wq.data_ptr(), wq.shape[1],
-                                          bias, slope, dst.t.data_ptr(), dst.cs, dst_coff, stream), 'conv3x3_n2_f16')
-            return dst
-        R = m.kernel_size[0]
-        stride = m.stride[0]
-        N, NP = m.out_channels, _c32(m.out_channels)
-        if not de and (R, stride, src.cs) in ((7, 2, 8), (3, 1, 8)) and m.kernel_size[1] == R and src.C <= 8 and \
-                os.environ.get('VV_FN2_ROWK', '1') != '0':
-            # row-K (few-channel first layers): K = the (kx, c) run of 8-half pixels under one filter row, padded to 16
-            KF = (R * 8 + 15) // 16 * 16
-
-            def make_rowk():
-                w = m.weight.detach().float()                                  # [N][Cin][ky][kx]
-                wr = torch.zeros(N, KF, R, device=w.device, dtype=torch.float32)
-                wr[:, :R * 8].view(N, R, 8, R)[:, :, :m.in_channels] = w.permute(0, 3, 1, 2)      # [N][kx][c][ky]
-                packed = torch.empty(R * KF * NP, device=w.device, dtype=torch.float16)
-                L.check(lib.vv_pack_conv2d_f16(wr.data_ptr(), packed.data_ptr(), R, KF, KF, N, NP, 0, stream), 'pack_conv2d_f16 (row-K)')
-                return packed
-            packed = self._cached(('f16rowk', id(m)), m, make_rowk)
-            pad = (R - 1) // 2
-            OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
-            assert (dst.H, dst.W) == (OH, OW) and dst_coff + N <= dst.cs
-            p = L.Conv2dParams(2, R, stride, src.B, src.H, src.W, KF, KF, N, NP, src.view(0), packed.data_ptr(), bias, slope, 0,
-                               dst.view(dst_coff))
-            L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 row-K %dx%d s%d %d->%d' % (R, R, stride, m.in_channels, N))
-            return dst
-        K = m.in_channels
-        KP = _c32(K)
-        taps = m.kernel_size[0] * m.kernel_size[1]
-
-        def make_panel():
-            w = m.weight.detach().contiguous().float()
-            packed = torch.empty(taps * KP * NP, device=w.device, dtype=torch.float16)
-            L.check(lib.vv_pack_conv2d_f16(w.data_ptr(), packed.data_ptr(), taps, K, KP, N, NP, 1 if de else 0, stream),
-                    'pack_conv2d_f16')
-            return packed
-        packed = self._cached(('f16', id(m)), m, make_panel)
-        if de:
-            assert m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)
-            OH, OW = 2 * src.H, 2 * src.W
-            R, stride = 4, 2
+    def _launch(self, layer, src, dst, dst_coff=0):
+        """layer: nn.Sequential(Conv2d|ConvTranspose2d[, LeakyReLU]) or a bare Conv2d / ConvTranspose2d.  Returns its route."""
+        if isinstance(layer, nn.Sequential):
+            m = layer[0]
+            slope = 0.1 if len(layer) > 1 else 1.0
         else:
-            pad = (R - 1) // 2
-            assert m.padding == (pad, pad)
-            OH, OW = (src.H + 2 * pad - R) // stride + 1, (src.W + 2 * pad - R) // stride + 1
-        assert (dst.H, dst.W) == (OH, OW), ((dst.H, dst.W), (OH, OW))
-        assert dst_coff + N <= dst.cs
-        # split-K on the tiny-M / huge-K levels, the policy of the fp32 path
-        lh, lw = (src.H, src.W) if de else (OH, OW)
-        wgs = src.B * (4 if de else 1) * (NP // (64 if (NP % 64 == 0 and N > 32) else 32)) * ((lh + 7) // 8) * ((lw + 31) // 32)
-        nchunk = KP // (16 if (not de and stride == 2) else 32)
-        ks = 1
-        if wgs < 256 and nchunk >= 4:
-            ks = max(1, min(nchunk // 2, _KS_TARGET // wgs, 16))
-        kind = 1 if de else 0
-        if ks > 1:
-            M = src.B * OH * OW
-            ws = torch.empty(ks * M * NP, device=src.t.device, dtype=torch.float32)
-            p = L.Conv2dParams(kind, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(), None, 1.0, ks,
-                               L.View(ws.data_ptr(), 0, NP, 0))
-            L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 split-k')
-            L.check(lib.vv_conv2d_splitk_finish_f16(ws.data_ptr(), ks, M, N, NP, bias, slope, dst.t.data_ptr(), dst.cs, dst_coff,
-                                                    stream), 'conv2d_f16 split-k finish')
-            return dst
-        p = L.Conv2dParams(kind, R, stride, src.B, src.H, src.W, K, KP, N, NP, src.view(0), packed.data_ptr(), bias, slope, 0,
-                           dst.view(dst_coff))
-        L.check(lib.vv_conv2d_f16(C.byref(p), stream), 'conv2d_f16 %dx%d s%d %d->%d' % (R, R, stride, K, N))
-        return dst
+            m, slope = layer, 1.0
+        prec = _F16 if src.t.dtype == torch.float16 else _F32
+        assert dst.t.dtype == prec.dtype
+        r = _route(m, isinstance(m, nn.ConvTranspose2d), src.B, src.H, src.W, src.C, src.cs, prec, dst.cs)
+        assert (dst.H, dst.W) == (r.OH, r.OW), ((dst.H, dst.W), (r.OH, r.OW))
+        assert dst_coff + r.N <= dst.cs
+        lib, stream = self.lib, torch.cuda.current_stream(src.t.device).cuda_stream
+        bias = self._param(m, 'bias', prec)
+        bias = None if bias is None else bias.data_ptr()
+        what = '%s %s %dx%d s%d %d->%d' % (prec.conv, r.kind, r.R, r.R, r.stride, r.K, r.N)
+        if r.kind == 'c2':
+            w = self._param(m, 'weight', prec).detach()
+            assert w.is_contiguous() and w.dtype == torch.float32
+            L.check(getattr(lib, prec.c2)(src.t.data_ptr(), src.cs, src.B, src.H, src.W, w.data_ptr(), bias, slope,
+                                          dst.t.data_ptr(), dst.cs, dst_coff, stream), what)
+            return r
+        panel = self._cached((prec.tag + r.kind, id(m)), m, lambda: self._panel(m, r, prec, src.cs, stream)).data_ptr()
+        if r.kind == 'n2':
+            L.check(getattr(lib, prec.n2)(src.t.data_ptr(), src.cs, src.B, src.H, src.W, r.K, panel, r.KP // 4, bias, slope,
+                                          dst.t.data_ptr(), dst.cs, dst_coff, stream), what)
+            return r
+        if r.kind == 'wino':
+            L.check(lib.vv_conv2d_wino(src.t.data_ptr(), src.cs, 0, src.t.numel(), panel, bias, slope, dst.t.data_ptr(),
+                                       dst.cs, dst_coff, src.B, src.H, src.W, r.KP, r.N, stream), what)
+            return r
+        # the conv kernel: direct (kind 0 / 1: conv / deconv) or row-K (kind 2); under split-K it writes partial sums to a workspace
+        # and vv_conv2d_splitk_finish adds them up, with the bias and the activation
+        kind, K = (2, r.KP) if r.kind == 'rowk' else (1 if r.de else 0, r.K)
+        if r.ks > 1:
+            M = src.B * r.OH * r.OW
+            ws = torch.empty(r.ks * M * r.NP, device=src.t.device, dtype=torch.float32)
+            epilogue = (None, 1.0, r.ks, L.View(ws.data_ptr(), 0, r.NP, 0))
+        else:
+            epilogue = (bias, slope, 0, dst.view(dst_coff))
+        p = L.Conv2dParams(kind, r.R, r.stride, src.B, src.H, src.W, K, r.KP, r.N, r.NP, src.view(0), panel, *epilogue)
+        L.check(getattr(lib, prec.conv)(C.byref(p), stream), what)
+        if r.ks > 1:
+            L.check(getattr(lib, prec.finish)(ws.data_ptr(), r.ks, M, r.N, r.NP, bias, slope, dst.t.data_ptr(), dst.cs, dst_coff,
+                                              stream), what + ' split-k finish')
+        return r
 
 
 def _upsample4(x_nchw, bilinear, scale, align_corners=False):
@@ -461,38 +323,48 @@ def _to_buf(x_nchw, device=None):
     return b
 
 
-class _Decoder:
-    """The refinement ladder shared by FlowNetC / FlowNetS (predict_flow on the concat buffers, FlowNetC.py:104-127)."""
+def _tail(net, run, nb, H, W, cat3, cat2, inter=False):
+    """conv4 ... conv6_1 on the first 256 channels of ``cat3`` (conv3_1's output), then the refinement ladder: the part FlowNetC,
+    FlowNetS and FlowNetSD share.  ``nb(h, w, c)`` allocates a buffer of the caller's batch / device / dtype."""
+    t4, cat4 = nb(H // 16, W // 16, 512), nb(H // 16, W // 16, 770)
+    run(net.conv4, _SliceView(cat3, 0, 256), t4); run(net.conv4_1, t4, cat4, 0)
+    t5, cat5 = nb(H // 32, W // 32, 512), nb(H // 32, W // 32, 1026)
+    run(net.conv5, _SliceView(cat4, 0, 512), t5); run(net.conv5_1, t5, cat5, 0)
+    t6, c6 = nb(H // 64, W // 64, 1024), nb(H // 64, W // 64, 1024)
+    run(net.conv6, _SliceView(cat5, 0, 512), t6); run(net.conv6_1, t6, c6)
+    return _decode(net, run, c6, cat5, cat4, cat3, cat2, inter)
 
-    @staticmethod
-    def run(net, run, out_conv6, cat5, cat4, cat3, cat2, inter=False):
-        dev, dt = out_conv6.t.device, out_conv6.t.dtype
-        B = out_conv6.B
 
-        def flow_of(pred, src):
-            f = _Buf(B, src.H, src.W, 2, dev, dt)
-            run(pred, src, f)
-            return f
+def _decode(net, run, out_conv6, cat5, cat4, cat3, cat2, inter=False):
+    """The refinement ladder shared by FlowNetC / FlowNetS / FlowNetSD (predict_flow on the concat buffers, FlowNetC.py:104-127;
+    ``inter``: FlowNetSD's inter_conv in front of every predict_flow)."""
+    dev, dt = out_conv6.t.device, out_conv6.t.dtype
+    B = out_conv6.B
 
-        flow6 = flow_of(net.predict_flow6, out_conv6)
-        run(net.upsampled_flow6_to_5, flow6, cat5, cat5.C - 2)
-        run(net.deconv5, out_conv6, cat5, cat5.C - 2 - net.deconv5[0].out_channels)
-        cats = [(cat5, 5, cat4), (cat4, 4, cat3), (cat3, 3, cat2)]
-        for cat, lvl, nxt in cats:
-            src = cat
-            if inter:
-                ic = getattr(net, 'inter_conv%d' % lvl)
-                src = _Buf(B, cat.H, cat.W, ic[0].out_channels, dev, dt)
-                run(ic, cat, src)
-            flow = flow_of(getattr(net, 'predict_flow%d' % lvl), src)
-            run(getattr(net, 'upsampled_flow%d_to_%d' % (lvl, lvl - 1)), flow, nxt, nxt.C - 2)
-            d = getattr(net, 'deconv%d' % (lvl - 1))
-            run(d, cat, nxt, nxt.C - 2 - d[0].out_channels)
-        src = cat2
+    def flow_of(pred, src):
+        f = _Buf(B, src.H, src.W, 2, dev, dt)
+        run(pred, src, f)
+        return f
+
+    flow6 = flow_of(net.predict_flow6, out_conv6)
+    run(net.upsampled_flow6_to_5, flow6, cat5, cat5.C - 2)
+    run(net.deconv5, out_conv6, cat5, cat5.C - 2 - net.deconv5[0].out_channels)
+    cats = [(cat5, 5, cat4), (cat4, 4, cat3), (cat3, 3, cat2)]
+    for cat, lvl, nxt in cats:
+        src = cat
         if inter:
-            src = _Buf(B, cat2.H, cat2.W, net.inter_conv2[0].out_channels, dev, dt)
-            run(net.inter_conv2, cat2, src)
-        return flow_of(net.predict_flow2, src)
+            ic = getattr(net, 'inter_conv%d' % lvl)
+            src = _Buf(B, cat.H, cat.W, ic[0].out_channels, dev, dt)
+            run(ic, cat, src)
+        flow = flow_of(getattr(net, 'predict_flow%d' % lvl), src)
+        run(getattr(net, 'upsampled_flow%d_to_%d' % (lvl, lvl - 1)), flow, nxt, nxt.C - 2)
+        d = getattr(net, 'deconv%d' % (lvl - 1))
+        run(d, cat, nxt, nxt.C - 2 - d[0].out_channels)
+    src = cat2
+    if inter:
+        src = _Buf(B, cat2.H, cat2.W, net.inter_conv2[0].out_channels, dev, dt)
+        run(net.inter_conv2, cat2, src)
+    return flow_of(net.predict_flow2, src)
 
 
 _TOWER_STREAMS = {}
@@ -572,15 +444,7 @@ class FlowNetC(nn.Module):
         run(self.conv_redir, c3a, in31, 0)
         cat3 = nb(H // 8, W // 8, 386)
         run(self.conv3_1, in31, cat3, 0)
-        cat4 = nb(H // 16, W // 16, 770)
-        t4 = nb(H // 16, W // 16, 512)
-        run(self.conv4, _SliceView(cat3, 0, 256), t4); run(self.conv4_1, t4, cat4, 0)
-        cat5 = nb(H // 32, W // 32, 1026)
-        t5 = nb(H // 32, W // 32, 512)
-        run(self.conv5, _SliceView(cat4, 0, 512), t5); run(self.conv5_1, t5, cat5, 0)
-        t6, c6 = nb(H // 64, W // 64, 1024), nb(H // 64, W // 64, 1024)
-        run(self.conv6, _SliceView(cat5, 0, 512), t6); run(self.conv6_1, t6, c6)
-        return _Decoder.run(self, run, c6, cat5, cat4, cat3, cat2)
+        return _tail(self, run, nb, H, W, cat3, cat2)
 
 
 class _SliceView:
@@ -633,13 +497,7 @@ class FlowNetS(nn.Module):
         run(self.conv2, c1, cat2, 0)
         t3, cat3 = nb(H // 8, W // 8, 256), nb(H // 8, W // 8, 386)
         run(self.conv3, _SliceView(cat2, 0, 128), t3); run(self.conv3_1, t3, cat3, 0)
-        t4, cat4 = nb(H // 16, W // 16, 512), nb(H // 16, W // 16, 770)
-        run(self.conv4, _SliceView(cat3, 0, 256), t4); run(self.conv4_1, t4, cat4, 0)
-        t5, cat5 = nb(H // 32, W // 32, 512), nb(H // 32, W // 32, 1026)
-        run(self.conv5, _SliceView(cat4, 0, 512), t5); run(self.conv5_1, t5, cat5, 0)
-        t6, c6 = nb(H // 64, W // 64, 1024), nb(H // 64, W // 64, 1024)
-        run(self.conv6, _SliceView(cat5, 0, 512), t6); run(self.conv6_1, t6, c6)
-        return _Decoder.run(self, run, c6, cat5, cat4, cat3, cat2)
+        return _tail(self, run, nb, H, W, cat3, cat2)
 
 
 class FlowNetSD(nn.Module):
@@ -690,13 +548,7 @@ class FlowNetSD(nn.Module):
         run(self.conv2, c1, t2); run(self.conv2_1, t2, cat2, 0)
         t3, cat3 = nb(H // 8, W // 8, 256), nb(H // 8, W // 8, 386)
         run(self.conv3, _SliceView(cat2, 0, 128), t3); run(self.conv3_1, t3, cat3, 0)
-        t4, cat4 = nb(H // 16, W // 16, 512), nb(H // 16, W // 16, 770)
-        run(self.conv4, _SliceView(cat3, 0, 256), t4); run(self.conv4_1, t4, cat4, 0)
-        t5, cat5 = nb(H // 32, W // 32, 512), nb(H // 32, W // 32, 1026)
-        run(self.conv5, _SliceView(cat4, 0, 512), t5); run(self.conv5_1, t5, cat5, 0)
-        t6, c6 = nb(H // 64, W // 64, 1024), nb(H // 64, W // 64, 1024)
-        run(self.conv6, _SliceView(cat5, 0, 512), t6); run(self.conv6_1, t6, c6)
-        return _Decoder.run(self, run, c6, cat5, cat4, cat3, cat2, inter=True)
+        return _tail(self, run, nb, H, W, cat3, cat2, inter=True)
 
 
 class FlowNetFusion(nn.Module):
@@ -861,9 +713,7 @@ class FlowNet2(nn.Module):
         L.check((lib.vv_fusion_pack11_f16 if f16 else lib.vv_fusion_pack11)(
             x6.t.data_ptr(), img1.t.data_ptr(), s2_flow2.t.data_ptr(), s2_flow2.cs, sd_flow2.t.data_ptr(), sd_flow2.cs, B, H, W,
             float(self.div_flow), cat3.t.data_ptr(), st), 'fusion_pack11')
-        if f16:
-            return self.flownetfusion.run(run, cat3).nchw(0, 2, out_dtype=self._out_dtype)
-        return self.flownetfusion.run(run, cat3).nchw(0, 2)
+        return self.flownetfusion.run(run, cat3).nchw(0, 2, out_dtype=self._out_dtype)
 
     @torch.no_grad()
     def forward_graphed(self, inputs):
