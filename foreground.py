@@ -6,6 +6,10 @@ frame instead of one ``cv2.resize`` call per box per frame), drop boxes whose fl
 the cubes under the grid block(s) the box falls in.  Outputs use the reference's file names and nesting so that either
 implementation can consume the other's files.
 
+``extract_device`` is the test stage without those files (``[mi355x] direct_test``): many consecutive frames per launch, every
+frame decoded and uploaded once per chunk, the motion test on the device (``vv_cube_energy``), and the kept cubes cut straight
+into a device-resident store (``vv_cube_cut``) that test.py's ``score_store`` scores through index lists.
+
 The bounding boxes themselves come from ``raw_datasets/<ds>/bboxes_{train,test}_<mode>.npy``.  ``load_bboxes`` writes that
 file for the detector-free modes when it is absent (train.py:44-99): 'frame', 'simple_patch' and 'obj_det_with_motion', whose
 motion stage runs on the GPU (vec_vad_amd/motion.py) on top of whatever detector output ``bboxes_<mode>_obj_det.npy`` holds.
@@ -225,3 +229,134 @@ def extract_test(c, device='cuda', log=print):
         labels = np.array([bool(np.asarray(raw_ds._gt(i)).max() > 0) for i in range(n)])
         np.save(base + 'frame_labels_test.npy', labels)
     log('foreground for testing data saved!')
+
+
+def block_groups(cube_frame, cube_blocks, n_frames, scene_idx=None):
+    """Index lists of a cube store (pure, no GPU).  ``cube_frame[s]`` = frame of store cube ``s`` (cubes are stored in frame
+    order), ``cube_blocks[s]`` = the ``(hi, wi)`` grid cells its box falls in (``calc_block_idx``).  Returns ``{(scene, hi, wi):
+    (idx int64 [m], off int32 [n_frames + 1])}``: the cubes of that block, by frame and then in store order, with CSR offsets --
+    the cubes of frame ``f`` are ``idx[off[f]:off[f+1]]``.  ``scene`` is ``scene_idx[f] - 1`` (ShanghaiTech: one model per scene)
+    or None.  A box that lies in two blocks is one cube named by two lists."""
+    lists = {}
+    last = -1
+    for s, (f, blocks) in enumerate(zip(cube_frame, cube_blocks)):
+        if f < last:
+            raise ValueError('store cubes must be in frame order (cube %d: frame %d after frame %d)' % (s, f, last))
+        last = f
+        key = None if scene_idx is None else int(scene_idx[f]) - 1
+        for (hi, wi) in sorted(blocks):
+            idx, cnt = lists.setdefault((key, hi, wi), ([], np.zeros(n_frames, np.int64)))
+            idx.append(s)
+            cnt[f] += 1
+    return {k: (np.asarray(idx, np.int64), np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32))
+            for k, (idx, cnt) in lists.items()}
+
+
+def extract_device(c, mode='test', device='cuda', log=print):
+    """The extraction of ``extract_test`` without cube files: returns ``(info, parts)``.
+
+    ``info``: ``n_frames``, ``scene_idx`` (ShanghaiTech, also written to ``<ds>_scene_idx.npy``; else None) and ``labels`` (also
+    written to ``<ds>_frame_labels_test.npy`` when the test set has ground truth; else None) -- known before any frame is cut.
+    ``parts``: a generator.  Frames are visited in order, ``[mi355x] direct_frames_per_chunk`` at a time: the union of the chunk's
+    context windows (the datasets' own ``context_range``) is decoded and uploaded once, ``vv_cube_energy`` applies the motion test,
+    its ``keep`` bytes come to the host (the one sync of a chunk), the kept boxes get store slots in frame and box order, and
+    ``vv_cube_cut`` writes their raw and flow cubes into one device store in ``CubeStore`` layout.  Each yielded part is a dict:
+    ``raw`` / ``flow`` (the store, of which the first ``n`` cubes are valid), ``groups`` (``block_groups`` over all ``n_frames``),
+    ``boxes`` (float64 ``[n,4]``, per cube) and ``frames`` = the ``(first, end)`` frame range the part covers; the ranges of
+    successive parts tile ``[0, n_frames)``.  The store holds ``min([mi355x] direct_max_cubes, number of boxes)`` cubes; when the
+    next frame's cubes would not fit, the part collected so far is yielded and the store is reused, so the consumer must be done
+    with a part before it asks for the next one.  A frame's cubes are never split between two parts.
+    No ``foreground_test_*`` / ``foreground_bbox_test_*`` file is written."""
+    from vec_vad_amd.extract import boxes_to_crops, chunk_windows, cube_cut, cube_energy
+    cp, ds, root, mod = c['cp'], c['dataset_name'], c['data_root_dir'], c['modality']
+    hb, wb = c['h_block'], c['w_block']
+    all_bboxes = load_bboxes(c, mode)
+    raw_ds, flow_ds = _datasets(c, mode, all_bboxes)
+    os.makedirs(os.path.join(root, mod), exist_ok=True)
+    base = os.path.join(root, mod, ds + '_')
+    n = len(raw_ds)
+    info = dict(n_frames=n, scene_idx=None, labels=None)
+    if ds == 'ShanghaiTech':
+        info['scene_idx'] = np.asarray(raw_ds.scene_idx)
+        np.save(base + 'scene_idx.npy', raw_ds.scene_idx)
+    if mode == 'test' and raw_ds.return_gt:
+        info['labels'] = np.array([bool(np.asarray(raw_ds._gt(i)).max() > 0) for i in range(n)])
+        np.save(base + 'frame_labels_test.npy', info['labels'])
+    h_step, w_step = frame_size[ds][0] / hb, frame_size[ds][1] / wb
+    motion_thr, block_mode = cp.getfloat(ds, 'motionThr'), cp.getint(ds, '{}_block_mode'.format(mode))
+    per_chunk, max_cubes = max(1, c['direct_frames_per_chunk']), max(1, c['direct_max_cubes'])
+    P = cp.getint(ds, 'patch_size')
+
+    def window(dataset, i):
+        return [i] if dataset.context_frame_num == 0 else dataset.context_range(i)
+
+    def upload(dataset, used):
+        fr = np.stack([get_inputs(dataset.all_frame_addr[f]) for f in used])            # [F,H,W,C], each frame once
+        return torch.from_numpy(np.ascontiguousarray(fr)).to(device)
+
+    def parts():
+        cap = max(1, min(max_cubes, int(sum(len(b) for b in all_bboxes))))
+        store = None
+        used_slots, first = 0, 0
+        cube_frame, cube_blocks, cube_boxes = [], [], []
+
+        def part(end):
+            return dict(raw=store[0], flow=store[1], n=used_slots, frames=(first, end),
+                        groups=block_groups(cube_frame, cube_blocks, n, info['scene_idx']),
+                        boxes=np.asarray(cube_boxes, np.float64).reshape(-1, 4))
+
+        for s in range(0, n, per_chunk):
+            e = min(s + per_chunk, n)
+            idxs = [i for i in range(s, e) if len(all_bboxes[i]) > 0]
+            log('Extracting foreground of frames {}-{}, {} in total'.format(s + 1, e, n))
+            if not idxs:
+                continue
+            used_r, win_r = chunk_windows([window(raw_ds, i) for i in idxs])
+            used_f, win_f = chunk_windows([window(flow_ds, i) for i in idxs])
+            fr_raw, fr_flow = upload(raw_ds, used_r), upload(flow_ds, used_f)
+            H, W = fr_raw.shape[1], fr_raw.shape[2]
+            counts = [len(all_bboxes[i]) for i in idxs]
+            crops = np.concatenate([boxes_to_crops(all_bboxes[i], H, W) for i in idxs])
+            rows = np.repeat(np.arange(len(idxs)), counts)                    # chunk-local frame of every box
+            wr, wf = win_r[rows], win_f[rows]                  # host tables: cube_energy / cube_cut check them without a sync
+            _, keep = cube_energy(fr_flow, crops, wf, P, motion_thr)
+            keep = keep.cpu().numpy().astype(bool)
+            if store is None:
+                store = (torch.empty((cap, win_r.shape[1], P, P, fr_raw.shape[3]), dtype=fr_raw.dtype, device=device),
+                         torch.empty((cap, win_f.shape[1], P, P, fr_flow.shape[3]), dtype=torch.float32, device=device))
+            slot = np.full(len(crops), -1, np.int32)
+
+            def cut():
+                if (slot >= 0).any():
+                    cube_cut(fr_raw, crops, wr, slot, P, store[0])
+                    cube_cut(fr_flow, crops, wf, slot, P, store[1])
+
+            p = 0
+            for k, i in enumerate(idxs):
+                kept = np.nonzero(keep[p:p + counts[k]])[0]
+                if len(kept) > cap:
+                    raise ValueError('frame {} has {} cubes, [mi355x] direct_max_cubes holds {}'.format(i, len(kept), cap))
+                if used_slots + len(kept) > cap:           # the store is full: hand over what it holds, then reuse it
+                    cut()
+                    yield part(i)
+                    slot[:] = -1
+                    used_slots, first = 0, i
+                    cube_frame, cube_blocks, cube_boxes = [], [], []
+                for b in kept:
+                    bb = all_bboxes[i][b]
+                    blocks = calc_block_idx(bb[0], bb[2], bb[1], bb[3], h_step, w_step, mode=block_mode)
+                    if any(not (0 <= hi < hb and 0 <= wi < wb) for hi, wi in blocks):
+                        raise IndexError('box {} of frame {} falls outside the {}x{} block grid'.format(b, i, hb, wb))
+                    slot[p + b] = used_slots
+                    used_slots += 1
+                    cube_frame.append(i)
+                    cube_blocks.append(blocks)
+                    cube_boxes.append(np.asarray(bb, np.float64)[:4])
+                p += counts[k]
+            cut()
+        if store is None:
+            store = (torch.empty((0, 1, P, P, 3), dtype=torch.uint8, device=device),
+                     torch.empty((0, 1, P, P, 2), dtype=torch.float32, device=device))
+        yield part(n)
+
+    return info, parts()

@@ -508,6 +508,29 @@ int vv_fusion_pack11(const float* x6, const float* img1, const float* s2_flow2, 
 int vv_crop_resize(const void* frames, int32_t is_f32, int32_t T, int32_t H, int32_t W, int32_t C, const int32_t* crops,
                    int32_t n, int32_t oh, int32_t ow, void* out, vv_stream stream);
 
+/* ---- cubes of many frames per launch (test.py's direct path, foreground.extract_device): every box brings its own frame window ----
+ * vv_cube_cut: the arithmetic of vv_crop_resize per output value (one shared device function), for N boxes of a chunk of F decoded
+ *   frames that are each held once.
+ *   frames [F][H][W][C] uint8 (is_f32 = 0) or float32 (is_f32 = 1)
+ *   crops  int32 [N][4] as for vv_crop_resize
+ *   win    int32 [N][T] = the frames of box i's temporal context as indices into the chunk, each in [0, F); repeats allowed
+ *          (border modes repeat frames)
+ *   slot   int32 [N] = the cube of the store that box i fills, < out_slots; boxes with slot < 0 are skipped; distinct boxes
+ *          must name distinct slots, in any order
+ *   The tables live in device memory, so the entry points cannot read them: the caller checks them (vec_vad_amd/extract.py
+ *   check_tables raises on a bad one).  Against a table that breaks these rules the kernels only protect memory: such a crop or
+ *   slot is skipped, such a window index is clamped, and the outputs for that box mean nothing.
+ *   out    [out_slots][T][P][P][C], same dtype (the CubeStore / *_foreground_*.npy layout); untouched outside the named slots
+ * vv_cube_energy: energy[i] = sum of squares of box i's resized float32 patch [T][P][P][C] (no patch is written), each value widened
+ *   to float64 before squaring, divided by T (train.py:159-170: the mean over the context frames); keep[i] = energy[i] > thr.
+ *   One workgroup per box, fixed summation order (strided per-thread sums, LDS tree), no atomics: bit-identical run to run.
+ *   P <= 1024 and T * P * P <= INT32_MAX, else VV_ERR_BAD_ARG. */
+int vv_cube_cut(const void* frames, int32_t is_f32, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* crops,
+                const int32_t* win, const int32_t* slot, int32_t n, int32_t T, int32_t P, void* out, int64_t out_slots,
+                vv_stream stream);
+int vv_cube_energy(const float* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* crops, const int32_t* win,
+                   int32_t n, int32_t T, int32_t P, double thr, double* energy, uint8_t* keep, vv_stream stream);
+
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.
  *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats

@@ -13,6 +13,11 @@ batch independent, so many frames are scored per launch (``[mi355x] score_batch`
 ``unified_dataset_interface(..., mode='test')`` targets, test.py:366-392); without that file the evaluation step is
 skipped.  Cube errors never leave HBM between the UNet bank and the frame score (``vv_frame_scores``); the h x w masks are
 only painted when ``[mi355x] save_score_masks`` asks for the reference's ``score_mask/<frame>`` files.
+
+``[mi355x] direct_test = True`` (default False) scores straight from frames and boxes: ``foreground.extract_device`` cuts the
+cubes of many frames per launch into a device-resident store and ``score_store`` scores them through per-block index lists, so no
+``foreground_test_*`` / ``foreground_bbox_test_*`` file is written or read and every frame is decoded once per chunk.  The frame
+scores, score masks and the evaluation are those of the staged path.
 """
 import os
 import sys
@@ -165,6 +170,30 @@ def paint_frame(scores, bboxes, h, w):
     return res
 
 
+def _mask_scores(r, o, stats, w_raw, w_of, trained):
+    """Host copy of the per-cube scores that ``paint_frame`` paints (test.py:338-348): z-normalised and weighted, ``BIG`` for a
+    block without a trained model."""
+    if not trained:
+        return np.ones(r.numel()) * BIG
+    sc = w_raw * ((r.cpu().numpy().astype(np.float32) - stats[0, 0]) / stats[0, 1])
+    if o is not None:
+        sc = sc + w_of * ((o.cpu().numpy().astype(np.float32) - stats[0, 2]) / stats[0, 3])
+    return sc
+
+
+def _save_masks(result_dir, frames, mask_groups, h, w):
+    """``<result_dir>/<frame>`` for every frame of ``frames``: one h x w float64 mask alive at a time, like the reference
+    (test.py:350-358).  mask_groups: (off indexed by frame, host cube scores, boxes) per scored group."""
+    os.makedirs(result_dir, exist_ok=True)
+    for f in frames:
+        fmap = -1.0 * np.ones((h, w)) * BIG
+        for off, sc, boxes in mask_groups:
+            if off[f + 1] > off[f]:
+                sl = slice(off[f], off[f + 1])
+                np.maximum(fmap, paint_frame(sc[sl], boxes[sl], h, w), out=fmap)
+        torch.save(fmap, os.path.join(result_dir, '{}'.format(f)))
+
+
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
                  device, score_batch=2048, scene_idx=None, result_dir=None, log=print, return_device=False):
     """Per-frame anomaly scores.  ``net_set[(s,)hh][ww]`` is a list with 0 or 1 eval-mode networks;
@@ -210,23 +239,111 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
                     cube_stat = np.full(n, -1, np.int32)
                 scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(boxes, h, w), w_raw, w_of, out=fs_dev)
                 if mask_groups is not None:
-                    if len(models) > 0:
-                        sc = w_raw * ((r.cpu().numpy().astype(np.float32) - stats[0, 0]) / stats[0, 1])
-                        if o is not None:
-                            sc = sc + w_of * ((o.cpu().numpy().astype(np.float32) - stats[0, 2]) / stats[0, 3])
-                    else:
-                        sc = np.ones(n) * BIG
+                    sc = _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0)
                     mask_groups.append((off, sc, boxes))           # off is indexed by frame: cubes of frame f = [off[f], off[f+1])
     if result_dir:
-        os.makedirs(result_dir, exist_ok=True)
-        for f in range(n_frames):       # one h x w float64 mask alive at a time, like the reference (test.py:350-358)
-            fmap = -1.0 * np.ones((h, w)) * BIG
-            for off, sc, boxes in mask_groups:
-                if off[f + 1] > off[f]:
-                    sl = slice(off[f], off[f + 1])
-                    np.maximum(fmap, paint_frame(sc[sl], boxes[sl], h, w), out=fmap)
-            torch.save(fmap, os.path.join(result_dir, '{}'.format(f)))
+        _save_masks(result_dir, range(n_frames), mask_groups, h, w)
     return fs_dev if return_device else fs_dev.cpu().numpy()
+
+
+def score_index_list(trainer, raw_store, flow_store, idx, score_batch):
+    """Scores of the store cubes named by ``idx`` (int64 ``[n]``, n > 0, repeats allowed), in the launch shapes of
+    ``score_cubes_device``: launches of exactly ``score_batch`` cubes (of ``n`` when the list is shorter than one launch), the tail
+    launch padded by repeating the last index.  Returns the DEVICE tensors (raw [n], of [n] | None) in list order."""
+    dev = trainer.bank.device
+    n = len(idx)
+    B = n if n < score_batch else int(score_batch)
+    idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+    r_all, o_all = torch.empty(n, device=dev), None
+    for s0 in range(0, n, B):
+        m = min(B, n - s0)
+        sel = idx_d[s0:s0 + m]
+        if m < B:
+            sel = torch.cat([sel, sel[-1:].expand(B - m)])
+        r, o = trainer.score_cubes(raw_store, flow_store, sel)
+        r_all[s0:s0 + m] = r[:m]
+        if o is not None:
+            if o_all is None:
+                o_all = torch.empty(n, device=dev)
+            o_all[s0:s0 + m] = o[:m]
+    return r_all, o_all
+
+
+def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw, w_of, useFlow, device, score_batch=2048,
+                scene_idx=None, result_dir=None, out=None, frame_range=None, trainers=None, return_device=False):
+    """``score_frames`` for a device-resident cube store (``foreground.extract_device``).  ``store`` = (raw uint8 ``[N,5,32,32,3]``,
+    flow float32 ``[N,Tf,32,32,2]``) CUDA tensors in ``CubeStore`` layout; ``groups`` = ``{(scene, hh, ww): (idx, off)}`` as built by
+    ``foreground.block_groups`` (scene = ``scene_idx[f] - 1`` when ``scene_idx`` is given, else None; ``off`` CSR over all frames);
+    ``boxes`` float ``[N,>=4]``, one row per store cube.  A cube named by two index lists is stored once and scored once per list.
+
+    Every group feeds ``scoring.frame_scores`` with the statistics, ``cube_stat`` and paints that ``score_frames`` gives it, and
+    the launches have the shapes ``score_cubes_device`` uses, so the frame scores and the masks under ``result_dir`` are the
+    staged path's.  ``out`` (CUDA float64 ``[n_frames]``, initialised to ``-BIG``) is max-accumulated into: a test set that comes
+    in several parts (``[mi355x] direct_max_cubes``) is scored part by part, with ``frame_range`` = the ``(first, end)`` frames whose
+    masks this call writes (default: all) and ``trainers`` = a dict that keeps the engines between calls."""
+    raw_store, flow_store = store
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(len(boxes), -1)[:, :4]
+    if out is not None:
+        n_frames = out.numel()
+    elif groups:
+        n_frames = len(next(iter(groups.values()))[1]) - 1
+    elif frame_range is not None:
+        n_frames = frame_range[1]
+    else:
+        raise ValueError('score_store: no group, no out and no frame_range to tell the number of frames')
+    fs_dev = out if out is not None else torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
+    trainers = {} if trainers is None else trainers
+    mask_groups = [] if result_dir else None
+    for gk in sorted(groups, key=lambda k: (k[1], k[2], -1 if k[0] is None else k[0])):
+        key, hh, ww = gk
+        if (key is None) != (scene_idx is None):
+            raise ValueError('group %r does not fit scene_idx %s' % (gk, 'given' if scene_idx is not None else 'absent'))
+        idx, off = groups[gk]
+        n = len(idx)
+        if n == 0:
+            continue
+        models = net_set[key][hh][ww] if key is not None else net_set[hh][ww]
+        gboxes = boxes[idx]
+        if len(models) > 0:
+            net = models[0]
+            if id(net) not in trainers:
+                trainers[id(net)] = FusedTrainer(net)
+            st_r = stats_raw[key][hh][ww] if key is not None else stats_raw[hh][ww]
+            st_o = (stats_of[key][hh][ww] if key is not None else stats_of[hh][ww]) if useFlow else (0.0, 1.0)
+            r, o = score_index_list(trainers[id(net)], raw_store, flow_store, idx, score_batch)
+            o = o if useFlow else None
+            stats = np.array([[st_r[0], st_r[1], st_o[0], st_o[1]]], np.float64)
+            cube_stat = np.zeros(n, np.int32)
+        else:        # anomaly: no object in the training set in this block (test.py:346-348)
+            r, o = torch.zeros(n, device=device), None
+            stats = np.array([[0.0, 1.0, 0.0, 1.0]])
+            cube_stat = np.full(n, -1, np.int32)
+        scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(gboxes, h, w), w_raw, w_of, out=fs_dev)
+        if mask_groups is not None:
+            mask_groups.append((off, _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0), gboxes))
+    if result_dir:
+        first, end = frame_range if frame_range is not None else (0, n_frames)
+        _save_masks(result_dir, range(first, end), mask_groups, h, w)
+    return fs_dev if return_device else fs_dev.cpu().numpy()
+
+
+def score_direct(c, device, mask_dir=None, log=print):
+    """``[mi355x] direct_test``: frames and boxes in, frame scores out.  The parts of ``foreground.extract_device`` are scored as
+    they come and max-accumulated into one device vector; the store, the engines and their captured launches serve every part."""
+    from foreground import extract_device
+    ds, fg, method = c['dataset_name'], c['mode_fg'], c['method']
+    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+    h, w, _, _ = frame_size[ds]
+    info, parts = extract_device(c, 'test', device, log)
+    net_set, st_r, st_o = load_artifacts(base, fg, method, ds == 'ShanghaiTech', lambda: build_network(c), device, c['h_block'],
+                                         c['w_block'])
+    fs_dev = torch.full((info['n_frames'],), -float(BIG), dtype=torch.float64, device=device)
+    trainers = {}
+    for part in parts:
+        score_store(net_set, st_r, st_o, (part['raw'], part['flow']), part['groups'], part['boxes'], h, w, c['w_raw'], c['w_of'],
+                    c['useFlow'], device, c['score_batch'], info['scene_idx'], mask_dir, out=fs_dev, frame_range=part['frames'],
+                    trainers=trainers, return_device=True)
+    return fs_dev.cpu().numpy()
 
 
 def main(config_path='config.cfg'):
@@ -234,7 +351,8 @@ def main(config_path='config.cfg'):
     cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
-    if not cp.getboolean(ds, 'test_foreground_saved') and not cp.getboolean(ds, 'scores_saved'):   # test.py:98-176
+    direct = c['direct_test'] and not cp.getboolean(ds, 'scores_saved')       # frames -> scores without cube files
+    if not direct and not cp.getboolean(ds, 'test_foreground_saved') and not cp.getboolean(ds, 'scores_saved'):   # test.py:98-176
         from foreground import extract_test
         extract_test(c, device)
     base = os.path.join(root, mod, ds + '_')
@@ -242,7 +360,11 @@ def main(config_path='config.cfg'):
     results_dir = 'results'
     shanghai = ds == 'ShanghaiTech'
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
-    if not cp.getboolean(ds, 'scores_saved'):
+    if direct:
+        fs = score_direct(c, device, os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None)
+        os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
+        np.save(frame_scores_path, fs)
+    elif not cp.getboolean(ds, 'scores_saved'):
         fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
         fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
         bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)

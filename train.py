@@ -52,6 +52,11 @@ class AverageMeter:
         return float(self.sum) / max(1, self.count)
 
 
+# [mi355x] direct_max_cubes default.  A cube of the 5raw+5of bank is 5*32*32*3 B (uint8 raw) + 5*32*32*2*4 B (float32 flow) =
+# 15 360 + 40 960 = 56 320 B; 524 288 cubes are 29.5e9 B (27.5 GiB), below 32 GB.  (5raw+1of: 23 552 B per cube, 12.3e9 B.)
+DIRECT_MAX_CUBES = 524288
+
+
 def read_config(path='config.cfg'):
     cp = ConfigParser()
     if not cp.read(path):
@@ -83,7 +88,10 @@ def read_config(path='config.cfg'):
              score_batch=cp.getint('mi355x', 'score_batch', fallback=2048),
              save_score_masks=cp.getboolean('mi355x', 'save_score_masks', fallback=True),
              overlap_wgrad=cp.getboolean('mi355x', 'overlap_wgrad', fallback=False),
-             precision=cp.get('mi355x', 'precision', fallback='fp32').strip().lower())
+             precision=cp.get('mi355x', 'precision', fallback='fp32').strip().lower(),
+             direct_test=cp.getboolean('mi355x', 'direct_test', fallback=False),
+             direct_frames_per_chunk=cp.getint('mi355x', 'direct_frames_per_chunk', fallback=64),
+             direct_max_cubes=cp.getint('mi355x', 'direct_max_cubes', fallback=DIRECT_MAX_CUBES))
     assert c['modality'] == 'raw2flow'
     return c
 

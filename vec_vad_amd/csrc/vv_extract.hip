@@ -1,5 +1,6 @@
 // Cube extraction: crop + cv2.resize(INTER_LINEAR) of n boxes out of T decoded frames in one launch
-// (reference vad_datasets.py:70-93 get_foreground; calc_optical_flow.py:46-59,82 whole-frame resizes).
+// (reference vad_datasets.py:70-93 get_foreground; calc_optical_flow.py:46-59,82 whole-frame resizes); vv_cube_cut / vv_cube_energy
+// do the same for the boxes of many consecutive frames at once, every box with its own frame window (test.py's direct path).
 // HBM-bound gather: every output element reads <= 4 source elements that neighbouring lanes share through L2/TCP.
 // The uint8 path is bit-exact fixed point; the float path rounds every product and sum to fp32 (no FMA contraction, see
 // the pragma below) like the C++ it replaces.
@@ -47,33 +48,23 @@ __device__ inline int fixed11(float w) {
   return min(max(v, -32768), 32767);
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) crop_resize_kernel(const T* __restrict__ frames, int nT, int H, int W, int C,
-                                                          const int32_t* __restrict__ crops, int n, int oh, int ow,
-                                                          T* __restrict__ out) {
-  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)n * nT * oh * ow;
-  if (gid >= total) return;
-  int dx = (int)(gid % ow);
-  int dy = (int)((gid / ow) % oh);
-  int t = (int)((gid / ((int64_t)ow * oh)) % nT);
-  int i = (int)(gid / ((int64_t)ow * oh * nT));
-  int x_min = crops[4 * i + 0], y_min = crops[4 * i + 1];
-  int cw = crops[4 * i + 2] - x_min, ch = crops[4 * i + 3] - y_min;
-  const T* src = frames + (((int64_t)t * H + y_min) * W + x_min) * C;
-  int64_t rs = (int64_t)W * C;
-  T* dst = out + gid * C;
+// One output pixel (all C channels) of cv::resize(crop, (ow, oh)): src = the crop's top-left element inside its frame, rs = the
+// frame's row stride in elements.  emit(c, v) receives each channel value -- a store (vv_crop_resize, vv_cube_cut) or a sum
+// (vv_cube_energy) -- so every caller shares one arithmetic.
+template <typename T, typename Emit>
+__device__ inline void resize_pixel(const T* __restrict__ src, int64_t rs, int C, int cw, int ch, int oh, int ow, int dy, int dx,
+                                    Emit emit) {
   if (cw == ow && ch == oh) {                       // same size: plain copy
-    for (int c = 0; c < C; ++c) dst[c] = src[dy * rs + (int64_t)dx * C + c];
+    for (int c = 0; c < C; ++c) emit(c, src[dy * rs + (int64_t)dx * C + c]);
     return;
   }
   if (cw == 2 * ow && ch == 2 * oh) {               // exact 2x decimation -> INTER_AREA
     const T* p = src + (2 * dy) * rs + (int64_t)(2 * dx) * C;
     for (int c = 0; c < C; ++c) {
       if constexpr (sizeof(T) == 1) {
-        dst[c] = (T)(((int)p[c] + (int)p[C + c] + (int)p[rs + c] + (int)p[rs + C + c] + 2) >> 2);
+        emit(c, (T)(((int)p[c] + (int)p[C + c] + (int)p[rs + c] + (int)p[rs + C + c] + 2) >> 2));
       } else {
-        dst[c] = (((p[c] + p[C + c]) + p[rs + c]) + p[rs + C + c]) * 0.25f;
+        emit(c, (((p[c] + p[C + c]) + p[rs + c]) + p[rs + C + c]) * 0.25f);
       }
     }
     return;
@@ -88,14 +79,97 @@ __global__ void __launch_bounds__(256) crop_resize_kernel(const T* __restrict__ 
       int h0 = (int)r0[o0 + c] * a0 + (int)r0[o1 + c] * a1;
       int h1 = (int)r1[o0 + c] * a0 + (int)r1[o1 + c] * a1;
       int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-      dst[c] = (T)min(max(v, 0), 255);
+      emit(c, (T)min(max(v, 0), 255));
     }
   } else {
     for (int c = 0; c < C; ++c) {
       float h0 = r0[o0 + c] * tx.w0 + r0[o1 + c] * tx.w1;
       float h1 = r1[o0 + c] * tx.w0 + r1[o1 + c] * tx.w1;
-      dst[c] = h0 * ty.w0 + h1 * ty.w1;
+      emit(c, h0 * ty.w0 + h1 * ty.w1);
     }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) crop_resize_kernel(const T* __restrict__ frames, int nT, int H, int W, int C,
+                                                          const int32_t* __restrict__ crops, int n, int oh, int ow,
+                                                          T* __restrict__ out) {
+  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t total = (int64_t)n * nT * oh * ow;
+  if (gid >= total) return;
+  int dx = (int)(gid % ow);
+  int dy = (int)((gid / ow) % oh);
+  int t = (int)((gid / ((int64_t)ow * oh)) % nT);
+  int i = (int)(gid / ((int64_t)ow * oh * nT));
+  int x_min = crops[4 * i + 0], y_min = crops[4 * i + 1];
+  int cw = crops[4 * i + 2] - x_min, ch = crops[4 * i + 3] - y_min;
+  const T* src = frames + (((int64_t)t * H + y_min) * W + x_min) * C;
+  T* dst = out + gid * C;
+  resize_pixel(src, (int64_t)W * C, C, cw, ch, oh, ow, dy, dx, [dst](int c, T v) { dst[c] = v; });
+}
+
+// a crop that does not lie inside the frame reads nothing.  The Python wrappers refuse such a table before they launch
+// (extract.check_tables); this guard, the slot guard and the window clamp below only keep a caller of the bare C ABI with a wrong
+// table from touching memory outside its buffers.
+__device__ inline bool crop_ok(int x0, int y0, int x1, int y1, int H, int W) {
+  return 0 <= x0 && x0 < x1 && x1 <= W && 0 <= y0 && y0 < y1 && y1 <= H;
+}
+
+// vv_cube_cut: one thread per output pixel of (box i, context frame t); every box brings its own frame window and store slot.
+template <typename T>
+__global__ void __launch_bounds__(256) cube_cut_kernel(const T* __restrict__ frames, int F, int H, int W, int C,
+                                                       const int32_t* __restrict__ crops, const int32_t* __restrict__ win,
+                                                       const int32_t* __restrict__ slot, int n, int nT, int P, int64_t slots,
+                                                       T* __restrict__ out) {
+  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t total = (int64_t)n * nT * P * P;
+  if (gid >= total) return;
+  int dx = (int)(gid % P);
+  int dy = (int)((gid / P) % P);
+  int t = (int)((gid / ((int64_t)P * P)) % nT);
+  int i = (int)(gid / ((int64_t)P * P * nT));
+  int64_t s = slot[i];
+  if (s < 0 || s >= slots) return;
+  int x_min = crops[4 * i + 0], y_min = crops[4 * i + 1], x_max = crops[4 * i + 2], y_max = crops[4 * i + 3];
+  if (!crop_ok(x_min, y_min, x_max, y_max, H, W)) return;
+  int f = min(max(win[(int64_t)i * nT + t], 0), F - 1);
+  const T* src = frames + (((int64_t)f * H + y_min) * W + x_min) * C;
+  T* dst = out + (((s * nT + t) * P + dy) * P + dx) * C;
+  resize_pixel(src, (int64_t)W * C, C, x_max - x_min, y_max - y_min, P, P, dy, dx, [dst](int c, T v) { dst[c] = v; });
+}
+
+// vv_cube_energy: one workgroup per box.  Thread j sums the squares of pixels j, j + 256, ... of the [Tf][P][P] patch in that order
+// (channels in order inside a pixel), the 256 partial sums meet in a fixed LDS tree: the same bits on every run.
+__global__ void __launch_bounds__(256) cube_energy_kernel(const float* __restrict__ frames, int F, int H, int W, int C,
+                                                          const int32_t* __restrict__ crops, const int32_t* __restrict__ win,
+                                                          int n, int nT, int P, double thr, double* __restrict__ energy,
+                                                          uint8_t* __restrict__ keep) {
+  __shared__ double part[256];
+  int i = blockIdx.x;
+  int x_min = crops[4 * i + 0], y_min = crops[4 * i + 1], x_max = crops[4 * i + 2], y_max = crops[4 * i + 3];
+  double acc = 0.0;
+  if (crop_ok(x_min, y_min, x_max, y_max, H, W)) {       // the same for every thread of the workgroup
+    int per = nT * P * P;                                // fits: vv_cube_energy refuses T * P * P > INT32_MAX
+    for (int j = threadIdx.x; j < per; j += 256) {
+      int dx = j % P, dy = (j / P) % P, t = j / (P * P);
+      int f = min(max(win[(int64_t)i * nT + t], 0), F - 1);
+      const float* src = frames + (((int64_t)f * H + y_min) * W + x_min) * C;
+      resize_pixel(src, (int64_t)W * C, C, x_max - x_min, y_max - y_min, P, P, dy, dx, [&acc](int, float v) {
+        double d = (double)v;
+        acc = acc + d * d;
+      });
+    }
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double e = part[0] / (double)nT;
+    energy[i] = e;
+    keep[i] = e > thr ? 1 : 0;
   }
 }
 
@@ -116,6 +190,39 @@ extern "C" int vv_crop_resize(const void* frames, int32_t is_f32, int32_t T, int
     VV_LAUNCH(crop_resize_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
               (const uint8_t*)frames, T, H, W, C, crops, n, oh, ow, (uint8_t*)out);
   }
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_cube_cut(const void* frames, int32_t is_f32, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* crops,
+                           const int32_t* win, const int32_t* slot, int32_t n, int32_t T, int32_t P, void* out, int64_t out_slots,
+                           vv_stream stream) {
+  if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || n < 0 || T <= 0 || P <= 0 || out_slots < 0) return VV_ERR_BAD_ARG;
+  if (n == 0) return VV_OK;
+  if (!frames || !crops || !win || !slot || !out) return VV_ERR_BAD_ARG;
+  int64_t total = (int64_t)n * T * P * P;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffff) return VV_ERR_BAD_ARG;
+  if (is_f32) {
+    VV_LAUNCH(cube_cut_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)frames, F, H, W, C,
+              crops, win, slot, n, T, P, out_slots, (float*)out);
+  } else {
+    VV_LAUNCH(cube_cut_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)frames, F, H, W,
+              C, crops, win, slot, n, T, P, out_slots, (uint8_t*)out);
+  }
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_cube_energy(const float* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* crops,
+                              const int32_t* win, int32_t n, int32_t T, int32_t P, double thr, double* energy, uint8_t* keep,
+                              vv_stream stream) {
+  if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || n < 0 || T <= 0 || P <= 0 || P > 1024) return VV_ERR_BAD_ARG;
+  if ((int64_t)T * P * P > 0x7fffffff) return VV_ERR_BAD_ARG;      // the kernel indexes a box's patch with an int
+  if (n == 0) return VV_OK;
+  if (!frames || !crops || !win || !energy || !keep) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(cube_energy_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, frames, F, H, W, C, crops, win, n, T, P, thr,
+            energy, keep);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

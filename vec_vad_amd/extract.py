@@ -1,6 +1,8 @@
 """Cube extraction on the GPU: crop + cv2-style bilinear resize of every box of a frame stack
 in ONE launch of ``vv_crop_resize`` (reference vad_datasets.py:70-93 ``get_foreground`` does one ``cv2.resize`` call per
 box per frame on the host), and the whole-frame resizes of calc_optical_flow.py:46-59,82.
+``cube_cut`` / ``cube_energy`` (``vv_cube_cut`` / ``vv_cube_energy``) do the boxes of many consecutive frames per launch, every box
+with its own frame window, for test.py's direct path (foreground.extract_device).
 
 There is no CPU fallback: without libvecvad_hip.so / a gfx950 device these functions raise.
 """
@@ -80,3 +82,106 @@ def foreground_cubes(frames, bboxes, patch_size):
     ``*_foreground_*.npy`` cube files and of ``CubeStore``), no host round trip."""
     crops = boxes_to_crops(bboxes, frames.shape[1], frames.shape[2])
     return crop_resize(frames, crops, patch_size, patch_size)
+
+
+def chunk_windows(ranges):
+    """Bookkeeping of one chunk of consecutive frames (pure, no GPU): ``ranges`` = the ``context_range`` of each frame of the
+    chunk (global frame indices; a border mode repeats a frame inside a window).  Returns (``used``: every frame some window
+    names, once, ascending -- what the chunk decodes and uploads; ``win``: int32 ``[len(ranges), T]``, the windows as indices
+    into ``used``)."""
+    used = sorted({f for r in ranges for f in r})
+    local = {f: k for k, f in enumerate(used)}
+    win = np.array([[local[f] for f in r] for r in ranges], np.int32).reshape(len(ranges), -1)
+    return used, win
+
+
+def check_tables(crops, win, F, H, W, slot=None, slots=None):
+    """The tables of a ``cube_cut`` / ``cube_energy`` launch against the chunk they index (pure, no GPU; numpy int32 arrays): every
+    crop non-empty and inside the ``H x W`` frame, every window index in ``[0, F)``, one window row per crop, and with ``slot`` one
+    entry per crop, each below ``slots``, no slot >= 0 named twice.  Raises ValueError on the first rule a table breaks: the
+    kernels would skip such a box or clamp such an index without a word, and a skipped box leaves its cube of the store unwritten."""
+    crops, win = np.asarray(crops).reshape(-1, 4), np.asarray(win)
+    n = crops.shape[0]
+    if win.ndim != 2 or win.shape[0] != n or win.shape[1] < 1:
+        raise ValueError('win must be [n,T] with one row per crop and T >= 1, got %s for %d crops' % (tuple(win.shape), n))
+    x0, y0, x1, y1 = crops[:, 0], crops[:, 1], crops[:, 2], crops[:, 3]
+    bad = np.nonzero(~((0 <= x0) & (x0 < x1) & (x1 <= W) & (0 <= y0) & (y0 < y1) & (y1 <= H)))[0]
+    if len(bad):
+        raise ValueError('crop %d (%s) is empty or does not lie inside the %dx%d frame' % (bad[0], crops[bad[0]].tolist(), H, W))
+    bad = np.nonzero(((win < 0) | (win >= F)).any(1))[0]
+    if len(bad):
+        raise ValueError('window %d (%s) names a frame outside the chunk of %d frames' % (bad[0], win[bad[0]].tolist(), F))
+    if slot is not None:
+        slot = np.asarray(slot).reshape(-1)
+        if slot.shape[0] != n:
+            raise ValueError('slot must have one entry per crop, got %d for %d crops' % (slot.shape[0], n))
+        bad = np.nonzero(slot >= slots)[0]
+        if len(bad):
+            raise ValueError('box %d names slot %d of a store of %d cubes' % (bad[0], slot[bad[0]], slots))
+        named = slot[slot >= 0]
+        if len(np.unique(named)) != len(named):
+            raise ValueError('two boxes name the same slot')
+
+
+def _chunk_args(frames, crops, win, slot=None, slots=None):
+    """Checks the tables on the host and returns them as int32 device tensors next to the frames.  A table that is already a
+    device tensor is read back for the check (a sync), so hand numpy arrays over where that matters."""
+    if not frames.is_cuda:
+        raise _lib.VecVadHipError('the frames of a chunk must be in HBM (CUDA tensor); vec_vad_amd has no CPU path')
+    if frames.dim() != 4 or not frames.is_contiguous():
+        raise ValueError('frames must be a contiguous [F,H,W,C] tensor')
+
+    def host(a):
+        return a.cpu().numpy() if torch.is_tensor(a) else np.ascontiguousarray(a, dtype=np.int32)
+
+    def dv(a):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+        return t.to(device=frames.device, dtype=torch.int32).contiguous()
+
+    check_tables(host(crops), host(win), frames.shape[0], frames.shape[1], frames.shape[2],
+                 None if slot is None else host(slot), slots)
+    return dv(crops).reshape(-1, 4), dv(win), None if slot is None else dv(slot).reshape(-1)
+
+
+def cube_cut(frames, crops, win, slot, patch_size, out):
+    """``vv_cube_cut``: the boxes of many frames in one launch.  frames: CUDA ``[F,H,W,C]`` uint8 | float32, the decoded frames
+    of a chunk, each once; crops int32 ``[n,4]``; win int32 ``[n,T]`` = each box's context frames as indices into the chunk;
+    slot int32 ``[n]`` = the cube of ``out`` (CUDA ``[slots,T,P,P,C]``, same dtype, contiguous) that the box fills, ``< 0`` =
+    skip.  Every written value equals ``crop_resize(frames[win[i]], crops[i:i+1], P, P)`` bit for bit.  A table that breaks
+    ``check_tables`` raises before anything is launched."""
+    if out.dim() != 5:
+        raise ValueError('out must be a [slots,T,P,P,C] tensor')
+    crops, win, slot = _chunk_args(frames, crops, win, slot, out.shape[0])
+    n, T = win.shape
+    F, H, W, C = frames.shape
+    P = int(patch_size)
+    if frames.dtype not in (torch.uint8, torch.float32) or out.dtype != frames.dtype:
+        raise TypeError('cube_cut handles uint8 and float32 frames and writes the same dtype, got %s -> %s' % (frames.dtype, out.dtype))
+    if not out.is_contiguous() or out.device != frames.device or tuple(out.shape[1:]) != (T, P, P, C):
+        raise ValueError('out must be a contiguous [slots,%d,%d,%d,%d] tensor next to the frames' % (T, P, P, C))
+    if n:
+        _lib.check(_lib.lib().vv_cube_cut(frames.data_ptr(), int(frames.dtype == torch.float32), F, H, W, C, crops.data_ptr(),
+                                         win.data_ptr(), slot.data_ptr(), n, T, P, out.data_ptr(), out.shape[0],
+                                         torch.cuda.current_stream(frames.device).cuda_stream), 'vv_cube_cut')
+    return out
+
+
+def cube_energy(frames, crops, win, patch_size, thr):
+    """``vv_cube_energy``: the motion test of train.py:159-170 without writing a patch.  frames: CUDA float32 ``[F,H,W,C]`` flow
+    fields of a chunk (C = 2); crops / win as for ``cube_cut``, checked in the same way.  Returns CUDA (energy float64 ``[n]`` =
+    sum of squares of the resized patch, mean over the context frames; keep uint8 ``[n]`` = energy > thr)."""
+    crops, win, _ = _chunk_args(frames, crops, win)
+    if frames.dtype != torch.float32:
+        raise TypeError('cube_energy works on float32 flow fields, got %s' % frames.dtype)
+    n, T = win.shape
+    F, H, W, C = frames.shape
+    P = int(patch_size)
+    if not 0 < P <= 1024 or T * P * P > 0x7fffffff:
+        raise ValueError('cube_energy needs 0 < patch_size <= 1024 and T * patch_size^2 below 2^31, got T = %d, patch_size = %d' % (T, P))
+    energy = torch.empty(n, dtype=torch.float64, device=frames.device)
+    keep = torch.empty(n, dtype=torch.uint8, device=frames.device)
+    if n:
+        _lib.check(_lib.lib().vv_cube_energy(frames.data_ptr(), F, H, W, C, crops.data_ptr(), win.data_ptr(), n, T, P,
+                                            float(thr), energy.data_ptr(), keep.data_ptr(),
+                                            torch.cuda.current_stream(frames.device).cuda_stream), 'vv_cube_energy')
+    return energy, keep
