@@ -8,15 +8,19 @@ vectors, to ``./optical_flow/<same sub-path as the frame>/<frame name>.npy`` as 
 What runs where: decoded frames are uploaded once per frame triple; both cv2-style resizes (``vv_crop_resize``), the
 whole FlowNet2 forward (``vv_conv2d_mfma`` + correlation / resample2d / channelnorm kernels, replayed from a hipGraph)
 and the layout changes stay on the GPU; only the final ``[h,w,2]`` field comes back for ``np.save``.
+
+``flow_pairs`` / ``chunk_flows`` are the same computation for test.py's direct path (``[mi355x] direct_flow``): the flow of many frames
+of a chunk that is already on the device, written into a device tensor -- ``vv_flow_pairs_prep`` fills the captured graph's input,
+the graph is replayed, ``vv_flow_resize_back`` reads its output; no file, no host copy, no framework kernel in between.
 """
 import os
 
 import numpy as np
 import torch
 
-from vad_datasets import unified_dataset_interface
+from vad_datasets import context_range, unified_dataset_interface
 from FlowNet2_src import FlowNet2
-from vec_vad_amd.extract import crop_resize
+from vec_vad_amd.extract import crop_resize, flow_pairs_prep, flow_resize_back
 
 FLOW_W, FLOW_H = 512, 384                    # cv2.resize(..., (512, 384)), calc_optical_flow.py:46-58
 CHECKPOINT = 'FlowNet2_src/pretrained/FlowNet2_checkpoint.pth.tar'
@@ -85,6 +89,62 @@ def flows_of_frames(flownet2, items, graphed=True):
     for k, (H, W) in enumerate(sizes):
         f = flow[k].permute(1, 2, 0).contiguous()[None]
         out.append(crop_resize(f, np.array([[0, 0, FLOW_W, FLOW_H]], np.int32), H, W)[0, 0])
+    return out
+
+
+def flow_pairs(dataset_or_frame_video_idx, frames):
+    """Pure, no GPU: for every global frame index ``f`` of ``frames`` the ``(first, second)`` frame whose flow ``calc_optical_flow``
+    stores as ``<f>.npy`` -- ``pair_of`` applied to the 'hard' context of one frame each side: (f, f + 1) inside a video, (f, f) on a
+    video's first frame, (f - 1, f) on its last, (f, f) when the dataset is one single frame.  The first argument is a dataset (any context and border
+    mode: only its video structure is read) or its ``frame_video_idx`` list.  Raises NotImplementedError where ``context_range``
+    does (a one-frame video next to another video), like the staged driver."""
+    fvi = getattr(dataset_or_frame_video_idx, 'frame_video_idx', dataset_or_frame_video_idx)
+    n = len(fvi)
+    out = []
+    for f in frames:
+        r = context_range(int(f), 'hard', 1, n, fvi)
+        a, b = pair_of(r)
+        out.append((r[a], r[b]))
+    return out
+
+
+def launch_tables(pairs, rows, pairs_per_launch):
+    """Pure, no GPU: ``pairs`` ``[n,2]`` and their output ``rows`` ``[n]`` cut into launches of exactly ``pairs_per_launch`` pairs, as
+    a list of (int32 ``[P,2]``, int32 ``[P]``).  The tail launch repeats its last pair with row -1 (computed, not written), so one
+    captured graph serves any number of pairs."""
+    P = int(pairs_per_launch)
+    if P < 1:
+        raise ValueError('pairs_per_launch must be at least 1, got %d' % P)
+    pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+    rows = np.asarray(rows, np.int32).reshape(-1)
+    if len(rows) != len(pairs):
+        raise ValueError('one row per pair: %d rows for %d pairs' % (len(rows), len(pairs)))
+    out = []
+    for s in range(0, len(pairs), P):
+        p, r = pairs[s:s + P], rows[s:s + P]
+        pad = P - len(p)
+        if pad:
+            p = np.concatenate([p, np.repeat(p[-1:], pad, axis=0)])
+            r = np.concatenate([r, np.full(pad, -1, np.int32)])
+        out.append((np.ascontiguousarray(p), np.ascontiguousarray(r)))
+    return out
+
+
+def chunk_flows(flownet2, frames_u8, pairs, rows, out, pairs_per_launch=4):
+    """``out[rows[i]]`` (CUDA float32 ``[R,H,W,2]``) = the flow of ``pairs[i]``, what ``flow_of_frames`` returns for that pair.
+    frames_u8: CUDA uint8 ``[F,H,W,C]``, the decoded frames of a chunk; pairs ``[n,2]`` index it.  Every launch carries exactly
+    ``pairs_per_launch`` pairs at 512x384 (``launch_tables``): ``vv_flow_pairs_prep`` writes the input buffer of the graph captured
+    for that shape (``FlowNet2.graph_entry``), the graph is replayed, ``vv_flow_resize_back`` reads its output buffer.  A flow
+    depends on its two frames and on ``pairs_per_launch`` (a layer's split-K choice depends on the batch), not on the chunk."""
+    H, W = frames_u8.shape[1], frames_u8.shape[2]
+    tables = launch_tables(pairs, rows, pairs_per_launch)
+    if not tables:
+        return out
+    static_in, static_out, graph = flownet2.graph_entry((int(pairs_per_launch), 3, 2, FLOW_H, FLOW_W))
+    for p, r in tables:
+        flow_pairs_prep(frames_u8, p, FLOW_H, FLOW_W, out=static_in)
+        graph.replay()
+        flow_resize_back(static_out, r, H, W, out)
     return out
 
 

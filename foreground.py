@@ -117,14 +117,21 @@ def load_bboxes(c, mode, dataset=None, device='cuda', log=print):
     return np.load(path, allow_pickle=True)
 
 
-def _datasets(c, mode, all_bboxes):
+def _datasets(c, mode, all_bboxes, direct_flow=False):
+    """The raw and the flow dataset of the stage.  ``direct_flow``: the flow dataset indexes the RAW tree (same videos, same frame
+    numbering, the flow context's windows) -- its frames stand for the flow fields ``calc_optical_flow.chunk_flows`` computes, and
+    nothing under ``optical_flow/`` is globbed."""
     cp, ds, method = c['cp'], c['dataset_name'], c['method']
     kw = dict(dataset_name=ds, mode=mode, border_mode=cp.get(method, 'border_mode'), all_bboxes=all_bboxes,
               patch_size=cp.getint(ds, 'patch_size'))
     raw = unified_dataset_interface(dir=os.path.join('raw_datasets', ds), file_format=frame_size[ds][2],
                                     context_frame_num=cp.getint(method, 'context_frame_num'), **kw)
-    flow = unified_dataset_interface(dir=os.path.join('optical_flow', ds), file_format='.npy',
-                                     context_frame_num=cp.getint(method, 'context_of_num'), **kw)
+    if direct_flow:
+        flow = unified_dataset_interface(dir=os.path.join('raw_datasets', ds), file_format=frame_size[ds][2],
+                                         context_frame_num=cp.getint(method, 'context_of_num'), **kw)
+    else:
+        flow = unified_dataset_interface(dir=os.path.join('optical_flow', ds), file_format='.npy',
+                                         context_frame_num=cp.getint(method, 'context_of_num'), **kw)
     return raw, flow
 
 
@@ -252,7 +259,7 @@ def block_groups(cube_frame, cube_blocks, n_frames, scene_idx=None):
             for k, (idx, cnt) in lists.items()}
 
 
-def extract_device(c, mode='test', device='cuda', log=print):
+def extract_device(c, mode='test', device='cuda', log=print, flownet2=None):
     """The extraction of ``extract_test`` without cube files: returns ``(info, parts)``.
 
     ``info``: ``n_frames``, ``scene_idx`` (ShanghaiTech, also written to ``<ds>_scene_idx.npy``; else None) and ``labels`` (also
@@ -266,12 +273,24 @@ def extract_device(c, mode='test', device='cuda', log=print):
     successive parts tile ``[0, n_frames)``.  The store holds ``min([mi355x] direct_max_cubes, number of boxes)`` cubes; when the
     next frame's cubes would not fit, the part collected so far is yielded and the store is reused, so the consumer must be done
     with a part before it asks for the next one.  A frame's cubes are never split between two parts.
-    No ``foreground_test_*`` / ``foreground_bbox_test_*`` file is written."""
+    No ``foreground_test_*`` / ``foreground_bbox_test_*`` file is written.
+
+    ``c['direct_flow']`` (``[mi355x] direct_flow``): no ``optical_flow/`` file is read either.  The flow windows come from a dataset
+    over the raw tree; per chunk the frames of the raw windows and of the flow pairs (``calc_optical_flow.flow_pairs``) are decoded
+    and uploaded once, and ``calc_optical_flow.chunk_flows`` computes the flow field of every frame some flow window names,
+    ``[mi355x] direct_flow_pairs`` pairs per FlowNet2 launch, straight into the chunk's flow tensor.  A flow shared by two chunks is
+    computed in both.  ``flownet2``: the network to use; None loads ``[mi355x] flownet2_checkpoint`` (``direct_flow_fp16``: in fp16 mode)."""
     from vec_vad_amd.extract import boxes_to_crops, chunk_windows, cube_cut, cube_energy
     cp, ds, root, mod = c['cp'], c['dataset_name'], c['data_root_dir'], c['modality']
     hb, wb = c['h_block'], c['w_block']
+    direct_flow = bool(c.get('direct_flow', False))
+    if direct_flow:
+        from calc_optical_flow import chunk_flows, flow_pairs, load_flownet2
+        if flownet2 is None:
+            flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
+        flow_pairs_per_launch = max(1, c['direct_flow_pairs'])
     all_bboxes = load_bboxes(c, mode)
-    raw_ds, flow_ds = _datasets(c, mode, all_bboxes)
+    raw_ds, flow_ds = _datasets(c, mode, all_bboxes, direct_flow)
     os.makedirs(os.path.join(root, mod), exist_ok=True)
     base = os.path.join(root, mod, ds + '_')
     n = len(raw_ds)
@@ -313,7 +332,17 @@ def extract_device(c, mode='test', device='cuda', log=print):
                 continue
             used_r, win_r = chunk_windows([window(raw_ds, i) for i in idxs])
             used_f, win_f = chunk_windows([window(flow_ds, i) for i in idxs])
-            fr_raw, fr_flow = upload(raw_ds, used_r), upload(flow_ds, used_f)
+            if direct_flow:
+                pairs = flow_pairs(flow_ds, used_f)
+                used = sorted(set(used_r) | {f for p in pairs for f in p})
+                local = {f: k for k, f in enumerate(used)}
+                fr_raw = upload(raw_ds, used)                  # the raw windows' frames and the pairs' frames, each once
+                win_r = np.array([local[f] for f in used_r], np.int32)[win_r]
+                fr_flow = torch.empty((len(used_f),) + tuple(fr_raw.shape[1:3]) + (2,), dtype=torch.float32, device=device)
+                chunk_flows(flownet2, fr_raw, [(local[a], local[b]) for a, b in pairs], np.arange(len(used_f)), fr_flow,
+                            flow_pairs_per_launch)
+            else:
+                fr_raw, fr_flow = upload(raw_ds, used_r), upload(flow_ds, used_f)
             H, W = fr_raw.shape[1], fr_raw.shape[2]
             counts = [len(all_bboxes[i]) for i in idxs]
             crops = np.concatenate([boxes_to_crops(all_bboxes[i], H, W) for i in idxs])

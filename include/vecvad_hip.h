@@ -531,6 +531,27 @@ int vv_cube_cut(const void* frames, int32_t is_f32, int32_t F, int32_t H, int32_
 int vv_cube_energy(const float* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* crops, const int32_t* win,
                    int32_t n, int32_t T, int32_t P, double thr, double* energy, uint8_t* keep, vv_stream stream);
 
+/* ---- optical flow of a chunk of decoded frames (test.py's direct path with [mi355x] direct_flow; calc_optical_flow.chunk_flows) ----
+ * The two whole-frame resizes of calc_optical_flow.py:46-59,82 around FlowNet2, each value that of vv_crop_resize (the same device
+ * function), written in the layout the neighbour wants; one thread per output pixel, no framework op in between.
+ * vv_flow_pairs_prep: FlowNet2's input for N frame pairs.
+ *   frames uint8 [F][H][W][C], C = 1 | 3 (else VV_ERR_BAD_ARG)
+ *   pairs  int32 [N][2] = (first, second) frame of pair n as indices into the chunk, each in [0, F); the caller checks them
+ *          (vec_vad_amd/extract.py flow_pairs_prep raises), the kernel only clamps
+ *   out    float32 [N][3][2][oh][ow]: out[n][c][k][y][x] = (float) resize_u8(frames[pairs[n][k]] -> oh x ow)[y][x][c]; with C = 1 the
+ *          one plane is written three times
+ * vv_flow_resize_back: FlowNet2's output back at frame size, vectors not rescaled.
+ *   flow   float32 planar [N][2][fh][fw]
+ *   rows   int32 [N] = the field of `out` that pair n fills; rows[n] < 0 skips pair n; a row >= out_rows is refused by the caller
+ *          and skipped by the kernel; distinct pairs must name distinct rows
+ *   out    float32 [out_rows][H][W][2], 8-byte aligned: out[rows[n]][y][x][c] = resize_f32(flow[n][c] -> H x W)[y][x]; untouched
+ *          outside the named rows
+ * N = 0 returns VV_OK and writes nothing (null tables allowed). */
+int vv_flow_pairs_prep(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* pairs, int32_t N,
+                       int32_t oh, int32_t ow, float* out, vv_stream stream);
+int vv_flow_resize_back(const float* flow, int32_t N, int32_t fh, int32_t fw, const int32_t* rows, int32_t H, int32_t W,
+                        float* out, int64_t out_rows, vv_stream stream);
+
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.
  *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats

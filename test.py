@@ -18,6 +18,10 @@ only painted when ``[mi355x] save_score_masks`` asks for the reference's ``score
 cubes of many frames per launch into a device-resident store and ``score_store`` scores them through per-block index lists, so no
 ``foreground_test_*`` / ``foreground_bbox_test_*`` file is written or read and every frame is decoded once per chunk.  The frame
 scores, score masks and the evaluation are those of the staged path.
+
+``[mi355x] direct_flow = True`` (default False; needs ``direct_test``) also computes the optical flow of every chunk on the GPU
+(``calc_optical_flow.chunk_flows``: FlowNet2 from a captured graph between two HIP resize kernels), so the test stage reads nothing
+under ``optical_flow/``.  ``main(config_path, flownet2=None)`` takes the network to use; None loads ``[mi355x] flownet2_checkpoint``.
 """
 import os
 import sys
@@ -327,14 +331,15 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
-def score_direct(c, device, mask_dir=None, log=print):
+def score_direct(c, device, mask_dir=None, log=print, flownet2=None):
     """``[mi355x] direct_test``: frames and boxes in, frame scores out.  The parts of ``foreground.extract_device`` are scored as
-    they come and max-accumulated into one device vector; the store, the engines and their captured launches serve every part."""
+    they come and max-accumulated into one device vector; the store, the engines and their captured launches serve every part.
+    ``flownet2``: the FlowNet2 that ``[mi355x] direct_flow`` computes the flow with (None: loaded from the configured checkpoint)."""
     from foreground import extract_device
     ds, fg, method = c['dataset_name'], c['mode_fg'], c['method']
     base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
     h, w, _, _ = frame_size[ds]
-    info, parts = extract_device(c, 'test', device, log)
+    info, parts = extract_device(c, 'test', device, log, flownet2=flownet2)
     net_set, st_r, st_o = load_artifacts(base, fg, method, ds == 'ShanghaiTech', lambda: build_network(c), device, c['h_block'],
                                          c['w_block'])
     fs_dev = torch.full((info['n_frames'],), -float(BIG), dtype=torch.float64, device=device)
@@ -346,9 +351,11 @@ def score_direct(c, device, mask_dir=None, log=print):
     return fs_dev.cpu().numpy()
 
 
-def main(config_path='config.cfg'):
+def main(config_path='config.cfg', flownet2=None):
     c = read_config(config_path)
     cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
+    if c['direct_flow'] and not c['direct_test']:
+        raise ValueError('[mi355x] direct_flow = True needs direct_test = True: only the direct test path computes the flow on the GPU')
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
     direct = c['direct_test'] and not cp.getboolean(ds, 'scores_saved')       # frames -> scores without cube files
@@ -361,7 +368,8 @@ def main(config_path='config.cfg'):
     shanghai = ds == 'ShanghaiTech'
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
     if direct:
-        fs = score_direct(c, device, os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None)
+        fs = score_direct(c, device, os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None,
+                          flownet2=flownet2)
         os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
         np.save(frame_scores_path, fs)
     elif not cp.getboolean(ds, 'scores_saved'):

@@ -91,7 +91,14 @@ def read_config(path='config.cfg'):
              precision=cp.get('mi355x', 'precision', fallback='fp32').strip().lower(),
              direct_test=cp.getboolean('mi355x', 'direct_test', fallback=False),
              direct_frames_per_chunk=cp.getint('mi355x', 'direct_frames_per_chunk', fallback=64),
-             direct_max_cubes=cp.getint('mi355x', 'direct_max_cubes', fallback=DIRECT_MAX_CUBES))
+             direct_max_cubes=cp.getint('mi355x', 'direct_max_cubes', fallback=DIRECT_MAX_CUBES),
+             direct_flow=cp.getboolean('mi355x', 'direct_flow', fallback=False),
+             direct_flow_pairs=cp.getint('mi355x', 'direct_flow_pairs', fallback=4),
+             direct_flow_fp16=cp.getboolean('mi355x', 'direct_flow_fp16', fallback=False),
+             flownet2_checkpoint=cp.get('mi355x', 'flownet2_checkpoint', fallback=None))
+    if c['flownet2_checkpoint'] is None:
+        from calc_optical_flow import CHECKPOINT
+        c['flownet2_checkpoint'] = CHECKPOINT
     assert c['modality'] == 'raw2flow'
     return c
 

@@ -173,6 +173,57 @@ __global__ void __launch_bounds__(256) cube_energy_kernel(const float* __restric
   }
 }
 
+// vv_flow_pairs_prep: one thread per output pixel (x fastest) of frame k of pair n; the C = 1 | 3 channel values of that pixel, the
+// uint8 arithmetic of vv_crop_resize on the whole frame, go as floats into the 3 planes of FlowNet2's [N][3][2][oh][ow] input (a
+// grey frame's one plane three times).  Writes are coalesced along x inside a plane.
+__global__ void __launch_bounds__(256) flow_pairs_prep_kernel(const uint8_t* __restrict__ frames, int F, int H, int W, int C,
+                                                              const int32_t* __restrict__ pairs, int N, int oh, int ow,
+                                                              float* __restrict__ out) {
+  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t plane = (int64_t)oh * ow;
+  if (gid >= (int64_t)N * 2 * plane) return;
+  int dx = (int)(gid % ow);
+  int dy = (int)((gid / ow) % oh);
+  int k = (int)((gid / plane) % 2);
+  int n = (int)(gid / (2 * plane));
+  int f = min(max(pairs[2 * n + k], 0), F - 1);
+  const uint8_t* src = frames + (int64_t)f * H * W * C;
+  float* dst = out + ((int64_t)n * 6 + k) * plane + (int64_t)dy * ow + dx;        // plane (n, c, k) = (n * 3 + c) * 2 + k
+  int64_t cstep = 2 * plane;
+  if (C == 1) {
+    resize_pixel(src, (int64_t)W, 1, W, H, oh, ow, dy, dx, [dst, cstep](int, uint8_t v) {
+      float x = (float)v;
+      dst[0] = x;
+      dst[cstep] = x;
+      dst[2 * cstep] = x;
+    });
+  } else {
+    resize_pixel(src, (int64_t)W * 3, 3, W, H, oh, ow, dy, dx, [dst, cstep](int c, uint8_t v) { dst[c * cstep] = (float)v; });
+  }
+}
+
+// vv_flow_resize_back: one thread per output pixel (x fastest) of pair n; each of the two planes of FlowNet2's planar [N][2][fh][fw]
+// output goes through the float path with C = 1 (the per-channel arithmetic of vv_crop_resize on the interleaved field), and the
+// two values leave as one 8-byte store into the [H][W][2] field of row rows[n].
+__global__ void __launch_bounds__(256) flow_resize_back_kernel(const float* __restrict__ flow, int N, int fh, int fw,
+                                                               const int32_t* __restrict__ rows, int H, int W,
+                                                               float* __restrict__ out, int64_t out_rows) {
+  int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t field = (int64_t)H * W;
+  if (gid >= (int64_t)N * field) return;
+  int dx = (int)(gid % W);
+  int dy = (int)((gid / W) % H);
+  int n = (int)(gid / field);
+  int64_t r = rows[n];
+  if (r < 0 || r >= out_rows) return;
+  int64_t plane = (int64_t)fh * fw;
+  const float* src = flow + (int64_t)n * 2 * plane;
+  float2 v;
+  resize_pixel(src, (int64_t)fw, 1, fw, fh, H, W, dy, dx, [&v](int, float x) { v.x = x; });
+  resize_pixel(src + plane, (int64_t)fw, 1, fw, fh, H, W, dy, dx, [&v](int, float x) { v.y = x; });
+  *reinterpret_cast<float2*>(out + ((r * H + dy) * W + dx) * 2) = v;
+}
+
 }  // namespace
 
 extern "C" int vv_crop_resize(const void* frames, int32_t is_f32, int32_t T, int32_t H, int32_t W, int32_t C,
@@ -223,6 +274,34 @@ extern "C" int vv_cube_energy(const float* frames, int32_t F, int32_t H, int32_t
   if (!frames || !crops || !win || !energy || !keep) return VV_ERR_BAD_ARG;
   VV_LAUNCH(cube_energy_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, frames, F, H, W, C, crops, win, n, T, P, thr,
             energy, keep);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_flow_pairs_prep(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t C, const int32_t* pairs, int32_t N,
+                                  int32_t oh, int32_t ow, float* out, vv_stream stream) {
+  if (F <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3) || N < 0 || oh <= 0 || ow <= 0) return VV_ERR_BAD_ARG;
+  if (N == 0) return VV_OK;
+  if (!frames || !pairs || !out) return VV_ERR_BAD_ARG;
+  int64_t total = (int64_t)N * 2 * oh * ow;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffff) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(flow_pairs_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, F, H, W, C, pairs, N, oh, ow,
+            out);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_flow_resize_back(const float* flow, int32_t N, int32_t fh, int32_t fw, const int32_t* rows, int32_t H, int32_t W,
+                                   float* out, int64_t out_rows, vv_stream stream) {
+  if (N < 0 || fh <= 0 || fw <= 0 || H <= 0 || W <= 0 || out_rows < 0) return VV_ERR_BAD_ARG;
+  if (N == 0) return VV_OK;
+  if (!flow || !rows || !out || ((uintptr_t)out & 7)) return VV_ERR_BAD_ARG;          // the kernel stores float2
+  int64_t total = (int64_t)N * H * W;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffff) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(flow_resize_back_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, flow, N, fh, fw, rows, H, W, out,
+            out_rows);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

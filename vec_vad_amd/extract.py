@@ -2,7 +2,9 @@
 in ONE launch of ``vv_crop_resize`` (reference vad_datasets.py:70-93 ``get_foreground`` does one ``cv2.resize`` call per
 box per frame on the host), and the whole-frame resizes of calc_optical_flow.py:46-59,82.
 ``cube_cut`` / ``cube_energy`` (``vv_cube_cut`` / ``vv_cube_energy``) do the boxes of many consecutive frames per launch, every box
-with its own frame window, for test.py's direct path (foreground.extract_device).
+with its own frame window, for test.py's direct path (foreground.extract_device); ``flow_pairs_prep`` / ``flow_resize_back``
+(``vv_flow_pairs_prep`` / ``vv_flow_resize_back``) are the two whole-frame resizes around FlowNet2 for many frame pairs per launch
+(calc_optical_flow.chunk_flows).
 
 There is no CPU fallback: without libvecvad_hip.so / a gfx950 device these functions raise.
 """
@@ -185,3 +187,70 @@ def cube_energy(frames, crops, win, patch_size, thr):
                                             float(thr), energy.data_ptr(), keep.data_ptr(),
                                             torch.cuda.current_stream(frames.device).cuda_stream), 'vv_cube_energy')
     return energy, keep
+
+
+def _host_i32(a):
+    return a.cpu().numpy().astype(np.int32) if torch.is_tensor(a) else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def flow_pairs_prep(frames, pairs, out_h, out_w, out=None):
+    """``vv_flow_pairs_prep``: FlowNet2's input for many frame pairs in one launch.  frames: CUDA uint8 ``[F,H,W,C]`` (C = 1 | 3), the
+    decoded frames of a chunk; pairs int32 ``[N,2]`` = (first, second) frame of each pair as indices into the chunk.  Returns (or
+    fills ``out``, CUDA float32 ``[N,3,2,out_h,out_w]`` contiguous) ``out[n,c,k] = float(resize(frames[pairs[n,k]])[..., c])``, the
+    values of ``crop_resize`` on the whole frame; a grey frame's plane is written three times.  A pair that names a frame outside
+    the chunk raises before anything is launched (the kernel alone would clamp the index without a word)."""
+    pairs_h = _host_i32(pairs)
+    if pairs_h.ndim != 2 or pairs_h.shape[1] != 2:
+        raise ValueError('pairs must be [N,2], got %s' % (tuple(pairs_h.shape),))
+    if frames.dim() != 4:
+        raise ValueError('frames must be a contiguous [F,H,W,C] tensor')
+    F, H, W, C = frames.shape
+    bad = np.nonzero(((pairs_h < 0) | (pairs_h >= F)).any(1))[0]
+    if len(bad):
+        raise ValueError('pair %d (%s) names a frame outside the chunk of %d frames' % (bad[0], pairs_h[bad[0]].tolist(), F))
+    if not frames.is_cuda:
+        raise _lib.VecVadHipError('the frames of a chunk must be in HBM (CUDA tensor); vec_vad_amd has no CPU path')
+    if frames.dtype != torch.uint8 or not frames.is_contiguous() or C not in (1, 3):
+        raise TypeError('flow_pairs_prep handles contiguous uint8 frames of 1 or 3 channels, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    N, oh, ow = pairs_h.shape[0], int(out_h), int(out_w)
+    if out is None:
+        out = torch.empty((N, 3, 2, oh, ow), dtype=torch.float32, device=frames.device)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != frames.device
+          or tuple(out.shape) != (N, 3, 2, oh, ow)):
+        raise ValueError('out must be a contiguous float32 [%d,3,2,%d,%d] tensor next to the frames' % (N, oh, ow))
+    if N:
+        pairs_d = torch.from_numpy(pairs_h).to(frames.device)
+        _lib.check(_lib.lib().vv_flow_pairs_prep(frames.data_ptr(), F, H, W, C, pairs_d.data_ptr(), N, oh, ow, out.data_ptr(),
+                                                torch.cuda.current_stream(frames.device).cuda_stream), 'vv_flow_pairs_prep')
+    return out
+
+
+def flow_resize_back(flow, rows, H, W, out):
+    """``vv_flow_resize_back``: FlowNet2's planar output back at frame size, vectors not rescaled.  flow: CUDA float32 ``[N,2,fh,fw]``
+    contiguous; rows int32 ``[N]`` = the field of ``out`` (CUDA float32 ``[R,H,W,2]`` contiguous) that pair n fills, ``< 0`` = skip.
+    Every written field equals ``crop_resize(flow[n].permute(1,2,0).contiguous()[None], whole, H, W)[0,0]`` bit for bit.  A row
+    ``>= R``, or one named twice, raises before anything is launched."""
+    rows_h = _host_i32(rows).reshape(-1)
+    if flow.dim() != 4 or flow.shape[1] != 2 or rows_h.shape[0] != flow.shape[0]:
+        raise ValueError('flow must be [N,2,fh,fw] with one row per pair, got %s for %d rows' % (tuple(flow.shape), rows_h.shape[0]))
+    if out.dim() != 4 or tuple(out.shape[1:]) != (int(H), int(W), 2):
+        raise ValueError('out must be a [R,%d,%d,2] tensor, got %s' % (H, W, tuple(out.shape)))
+    bad = np.nonzero(rows_h >= out.shape[0])[0]
+    if len(bad):
+        raise ValueError('pair %d names row %d of an output of %d fields' % (bad[0], rows_h[bad[0]], out.shape[0]))
+    named = rows_h[rows_h >= 0]
+    if len(np.unique(named)) != len(named):
+        raise ValueError('two pairs name the same row')
+    if not flow.is_cuda:
+        raise _lib.VecVadHipError('the flow must be in HBM (CUDA tensor); vec_vad_amd has no CPU path')
+    if flow.dtype != torch.float32 or out.dtype != torch.float32:
+        raise TypeError('flow_resize_back works on float32 fields, got %s -> %s' % (flow.dtype, out.dtype))
+    if not flow.is_contiguous() or not out.is_contiguous() or out.device != flow.device:
+        raise ValueError('flow and out must be contiguous tensors on one device')
+    N, _, fh, fw = flow.shape
+    if N:
+        rows_d = torch.from_numpy(rows_h).to(flow.device)
+        _lib.check(_lib.lib().vv_flow_resize_back(flow.data_ptr(), N, fh, fw, rows_d.data_ptr(), int(H), int(W), out.data_ptr(),
+                                                 out.shape[0], torch.cuda.current_stream(flow.device).cuda_stream),
+                   'vv_flow_resize_back')
+    return out

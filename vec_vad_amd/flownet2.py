@@ -715,6 +715,40 @@ class FlowNet2(nn.Module):
             float(self.div_flow), cat3.t.data_ptr(), st), 'fusion_pack11')
         return self.flownetfusion.run(run, cat3).nchw(0, 2, out_dtype=self._out_dtype)
 
+    def _capture(self, static_in):
+        """Warm up on ``static_in`` and capture one forward on it: the ``_graphs`` entry (graph, static_in, static_out)."""
+        dev = static_in.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):               # warm-up: packs the weights, fills the allocator
+                self.forward(static_in)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            static_out = self.forward(static_in)
+        return graph, static_in, static_out
+
+    @torch.no_grad()
+    def graph_entry(self, shape):
+        """The captured forward of a float32 input of ``shape`` ``(B,3,2,H,W)`` as ``(static_in, static_out, graph)``: write the input
+        into ``static_in``, ``graph.replay()``, read the flow ``[B,2,H,W]`` from ``static_out`` (overwritten by the next replay) -- all
+        on the current stream.  Captured on first use like ``forward_graphed`` does, warmed up on a zero input; the entry is the one
+        ``forward_graphed`` uses for this shape, and a second call returns the same buffers.  A producer kernel that writes
+        ``static_in`` and a consumer that reads ``static_out`` leave no framework kernel between them and the network."""
+        key = tuple(int(d) for d in shape)
+        ent = self._graphs.get(key)
+        if ent is None:
+            dev = next(self.parameters()).device
+            if dev.type != 'cuda':
+                raise L.VecVadHipError('FlowNet2 runs on the GPU only (no CPU fallback)')
+            ent = self._graphs[key] = self._capture(torch.zeros(key, dtype=torch.float32, device=dev))
+        graph, static_in, static_out = ent
+        if static_in.dtype != torch.float32 or static_out.dtype != torch.float32:
+            raise TypeError('the graph of shape %s was captured by forward_graphed on a %s input; graph_entry hands out float32 '
+                            'buffers only' % (key, static_in.dtype))
+        return static_in, static_out, graph
+
     @torch.no_grad()
     def forward_graphed(self, inputs):
         """Same result as forward(), replayed from a hipGraph captured once per input shape: the ~250 launches of one
@@ -722,18 +756,7 @@ class FlowNet2(nn.Module):
         key = tuple(inputs.shape)
         ent = self._graphs.get(key)
         if ent is None:
-            static_in = inputs.clone()
-            side = torch.cuda.Stream(device=inputs.device)
-            side.wait_stream(torch.cuda.current_stream(inputs.device))
-            with torch.cuda.stream(side):
-                for _ in range(2):               # warm-up: packs the weights, fills the allocator
-                    self.forward(static_in)
-            torch.cuda.current_stream(inputs.device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = self.forward(static_in)
-            ent = (graph, static_in, static_out)
-            self._graphs[key] = ent
+            ent = self._graphs[key] = self._capture(inputs.clone())
         graph, static_in, static_out = ent
         static_in.copy_(inputs)
         graph.replay()
