@@ -6,7 +6,8 @@ frame instead of one ``cv2.resize`` call per box per frame), drop boxes whose fl
 the cubes under the grid block(s) the box falls in.  Outputs use the reference's file names and nesting so that either
 implementation can consume the other's files.
 
-``extract_device`` is the test stage without those files (``[mi355x] direct_test``): many consecutive frames per launch, every
+``extract_train_device`` is the training stage without cube files (``[mi355x] direct_train``): ``extract_device`` in train mode, the
+whole split in one store.  ``extract_device`` is the test stage without those files (``[mi355x] direct_test``): many consecutive frames per launch, every
 frame decoded and uploaded once per chunk, the motion test on the device (``vv_cube_energy``), and the kept cubes cut straight
 into a device-resident store (``vv_cube_cut``) that test.py's ``score_store`` scores through index lists.
 
@@ -389,3 +390,30 @@ def extract_device(c, mode='test', device='cuda', log=print, flownet2=None):
         yield part(n)
 
     return info, parts()
+
+
+def extract_train_device(c, device='cuda', log=print, flownet2=None):
+    """The extraction of ``extract_train`` without cube files (``[mi355x] direct_train``; UCSDped2 / avenue): ``extract_device`` with
+    ``mode='train'`` (``train_block_mode``, the boxes of ``load_bboxes(c, 'train')``, no labels), the kept cubes of the WHOLE split
+    in one device store -- the trainer visits every cube every epoch.  Returns a dict: ``raw`` / ``flow`` (the store, of which the
+    first ``n`` cubes are valid, in frame and then box order), ``groups`` = ``{(None, hi, wi): (idx, off)}`` (``block_groups``;
+    ``store[idx]`` are the arrays ``extract_train`` files under block ``(hi, wi)``, in their order; a box in two blocks is one cube
+    named by two lists) and ``n_frames``.  No ``foreground_train_*`` file is written; with ``c['direct_flow']`` nothing under
+    ``optical_flow/`` is read (``flownet2`` as for ``extract_device``).
+
+    A split whose kept cubes do not fit ``[mi355x] direct_max_cubes`` raises ValueError (the rest of the split is still visited,
+    without keeping its cubes, so that the message can tell the number needed): no partial set is returned.  ShanghaiTech (one
+    model per scene, randomly ordered ``saveSegNum`` segments) raises NotImplementedError before any GPU work."""
+    if c['dataset_name'] == 'ShanghaiTech':
+        from train import DIRECT_TRAIN_SHANGHAI
+        raise NotImplementedError(DIRECT_TRAIN_SHANGHAI)
+    info, parts = extract_device(c, 'train', device, log, flownet2=flownet2)
+    first = next(parts)
+    out = dict(raw=first['raw'], flow=first['flow'], n=first['n'], groups=first['groups'], n_frames=info['n_frames'])
+    later = [p['n'] for p in parts]          # the store is reused from here on: ``out`` is not handed to anybody
+    if later:
+        raise ValueError('[mi355x] direct_max_cubes = {}: the training split keeps {} cubes, and direct_train needs all of them in '
+                         'one store (raise direct_max_cubes, or train from cube files with direct_train = False)'.format(
+                             c['direct_max_cubes'], out['n'] + sum(later)))
+    log('foreground for training data cut: {} cubes of {} frames in the device store'.format(out['n'], out['n_frames']))
+    return out

@@ -19,6 +19,16 @@ Cube extraction (train.py:102-226) runs through ``foreground.extract_train`` (cr
 (``foreground.load_bboxes``: 'frame', 'simple_patch', and 'obj_det_with_motion' = the rows of ``bboxes_train_obj_det.npy``, if
 that file exists, plus the motion boxes found on the GPU); the mmdet detector itself (train.py:44-67) is not part of this build,
 so mode 'obj_det' needs its bbox file.
+
+``[mi355x] direct_train = True`` (default False; UCSDped2 / avenue) trains straight from frames and boxes:
+``foreground.extract_train_device`` cuts the kept cubes of the whole training split into ONE device-resident store
+(``foreground.extract_device`` with ``mode='train'``: many frames per launch, every frame decoded once per chunk) and every (h, w)
+block trains from ``(store_raw, store_flow, block_idx)`` -- its index list of ``foreground.block_groups`` -- through the same loop.
+No ``foreground_train_*`` file is written or read; the three output files are, bit for bit, those of the staged route with the same
+``shuffle_seed``.  With ``direct_flow = True`` as well the flow of every chunk is computed on the GPU and nothing under
+``optical_flow/<ds>/Train...`` is read (``main(config_path, flownet2=None)`` takes the network; None loads
+``[mi355x] flownet2_checkpoint``).  Under ``torchrun`` every rank runs that extraction itself and holds the full store: no
+side-group barrier, no shared filesystem, but every rank decodes every frame (cost not measured).
 """
 import os
 import sys
@@ -55,6 +65,8 @@ class AverageMeter:
 # [mi355x] direct_max_cubes default.  A cube of the 5raw+5of bank is 5*32*32*3 B (uint8 raw) + 5*32*32*2*4 B (float32 flow) =
 # 15 360 + 40 960 = 56 320 B; 524 288 cubes are 29.5e9 B (27.5 GiB), below 32 GB.  (5raw+1of: 23 552 B per cube, 12.3e9 B.)
 DIRECT_MAX_CUBES = 524288
+DIRECT_TRAIN_SHANGHAI = ('[mi355x] direct_train = True does not cover ShanghaiTech (one model per scene, training cubes in randomly '
+                         'ordered saveSegNum segments): set it to False to train from the staged segment files')
 
 
 def read_config(path='config.cfg'):
@@ -90,6 +102,7 @@ def read_config(path='config.cfg'):
              overlap_wgrad=cp.getboolean('mi355x', 'overlap_wgrad', fallback=False),
              precision=cp.get('mi355x', 'precision', fallback='fp32').strip().lower(),
              direct_test=cp.getboolean('mi355x', 'direct_test', fallback=False),
+             direct_train=cp.getboolean('mi355x', 'direct_train', fallback=False),
              direct_frames_per_chunk=cp.getint('mi355x', 'direct_frames_per_chunk', fallback=64),
              direct_max_cubes=cp.getint('mi355x', 'direct_max_cubes', fallback=DIRECT_MAX_CUBES),
              direct_flow=cp.getboolean('mi355x', 'direct_flow', fallback=False),
@@ -129,6 +142,25 @@ def _dist():
         torch.cuda.set_device(local)
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     return dist, dist.get_rank(), dist.get_world_size()
+
+
+class StoreView:
+    """The cubes ``idx`` (int64 list, repeats between views allowed) of a device-resident store, seen as a cube set of its own:
+    ``len`` cubes, ``take(sel)`` = the store indices of the view's cubes ``sel``.  ``CubeStore`` is the view of a whole store."""
+
+    def __init__(self, raw, flow, idx, device='cuda'):
+        self.raw, self.flow = raw, flow
+        idx = idx if torch.is_tensor(idx) else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+        self.idx = idx.to(device=device, dtype=torch.int64)
+        if self.idx.numel() and not 0 <= int(self.idx.min()) <= int(self.idx.max()) < raw.shape[0]:
+            raise IndexError('block index list names cube %d / %d of a store of %d cubes'
+                             % (int(self.idx.min()), int(self.idx.max()), raw.shape[0]))
+
+    def __len__(self):
+        return int(self.idx.numel())
+
+    def take(self, sel):
+        return self.idx[sel]
 
 
 def _extract_once(c, device, dist=None, timeout_h=48.0):
@@ -177,7 +209,10 @@ def train_block(net, segments, epochs, batch_size, lambda_raw=1.0, lambda_of=1.0
     """The loop of train.py:375-427 for one (h, w) block.
 
     ``segments``: list of callables returning (raw uint8 [N,5,32,32,3], flow fp32 [N,(Tf,)32,32,2]) -- one entry for
-    UCSDped2 / avenue, ``totSegNum`` entries for ShanghaiTech (train.py:292-299).
+    UCSDped2 / avenue, ``totSegNum`` entries for ShanghaiTech (train.py:292-299).  An entry may instead be a tuple
+    ``(store_raw, store_flow, block_idx)``: the block's cubes are ``store[block_idx]`` of a device-resident store in ``CubeStore``
+    layout (``[mi355x] direct_train``); ``block_idx`` (int64, numpy or device tensor) is uploaded once, the epoch permutation
+    indexes it and the scoring pass walks it in order, so the steps see the cubes a callable returning ``store[block_idx]`` gives.
     Returns (state_dict with 'module.' prefixed keys, raw_scores [N_total], of_scores [N_total])."""
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist is not None else (0, 1)
     net = net.to(device)
@@ -189,6 +224,10 @@ def train_block(net, segments, epochs, batch_size, lambda_raw=1.0, lambda_of=1.0
     stores = [None] * len(segments)
 
     def store(i):
+        if not callable(segments[i]):
+            if stores[i] is None:
+                stores[i] = StoreView(*segments[i], device=device)
+            return stores[i]
         if stores[i] is None or len(segments) > 1:
             if len(segments) > 1:
                 trainer.release_graphs()      # the captured steps pin the previous segment's store: free it before the next upload
@@ -207,7 +246,7 @@ def train_block(net, segments, epochs, batch_size, lambda_raw=1.0, lambda_of=1.0
             perm = torch.from_numpy(perm).to(device)
             nb = (n + batch_size - 1) // batch_size
             for idx in range(nb):
-                bidx = perm[idx * batch_size:(idx + 1) * batch_size]          # the last partial batch is kept (train.py:373)
+                bidx = st.take(perm[idx * batch_size:(idx + 1) * batch_size])   # the last partial batch is kept (train.py:373)
                 n_glob = int(bidx.numel())
                 if world > 1:
                     if n_glob % world == 0:
@@ -241,7 +280,7 @@ def train_block(net, segments, epochs, batch_size, lambda_raw=1.0, lambda_of=1.0
         lo, hi = (rank * n) // world, ((rank + 1) * n) // world
         r_loc, o_loc = [], []
         for s in range(lo, hi, batch_size):
-            idx = torch.arange(s, min(hi, s + batch_size), device=device)
+            idx = st.take(torch.arange(s, min(hi, s + batch_size), device=device))
             r, o = trainer.score_cubes(st.raw, st.flow, idx)
             r_loc.append(r.clone())
             if o is not None:
@@ -282,19 +321,30 @@ def _gather_var(dist, t, n, world, present=True):
     return torch.cat(parts)
 
 
-def main(config_path='config.cfg'):
+def main(config_path='config.cfg', flownet2=None):
+    """``flownet2``: the network ``[mi355x] direct_flow`` computes the training split's flow with (only with ``direct_train``);
+    None loads ``[mi355x] flownet2_checkpoint``."""
     c = read_config(config_path)
     cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
+    shanghai = ds == 'ShanghaiTech'
+    direct = c['direct_train']
+    if direct and shanghai:                                     # before any GPU work
+        raise NotImplementedError(DIRECT_TRAIN_SHANGHAI)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
     dist, rank, world = _dist()
-    if not cp.getboolean(ds, 'train_foreground_saved'):      # train.py:102-226, cubes cut on the GPU (vv_crop_resize)
+    if not direct and not cp.getboolean(ds, 'train_foreground_saved'):      # train.py:102-226, cubes cut on the GPU (vv_crop_resize)
         _extract_once(c, device, dist)
     net = build_network(c)
     base = os.path.join(root, mod, ds + '_')
-    shanghai = ds == 'ShanghaiTech'
+    hb, wb = c['h_block'], c['w_block']
 
-    if shanghai:
+    if direct:          # every rank cuts the whole split into its own store: nothing to wait for, nothing on a shared disk
+        # (after build_network: loading FlowNet2 must not move the random state the initial weights are drawn from)
+        from foreground import extract_train_device
+        store = extract_train_device(c, device, log=print if rank == 0 else (lambda *a: None), flownet2=flownet2)
+        grid = [(None, h, w) for h in range(hb) for w in range(wb)]
+    elif shanghai:
         save_seg = cp.getint(ds, 'saveSegNum')
         names = sorted(f for f in os.listdir(os.path.join(root, mod))
                        if f.startswith('%s_foreground_train_%s_seg_' % (ds, fg)) and f.endswith('-raw.npy'))
@@ -311,6 +361,8 @@ def main(config_path='config.cfg'):
         if shanghai:
             ns = max(g[0] for g in grid) + 1
             return [[[fill() for _ in range(c['w_block'])] for _ in range(c['h_block'])] for _ in range(ns)]
+        if direct:
+            return [[fill() for _ in range(wb)] for _ in range(hb)]
         return [[fill() for _ in range(len(fset[h]))] for h in range(len(fset))]
 
     model_set, raw_scores_set, of_scores_set = nested(list), nested(list), nested(list)
@@ -321,6 +373,11 @@ def main(config_path='config.cfg'):
                 b = np.load(base + 'foreground_train_{}_seg_{}-flow.npy'.format(fg, k), allow_pickle=True)
                 return np.asarray(a[s][h][w]), np.asarray(b[s][h][w])
             segments = [lambda k=k: seg_loader(k) for k in range(tot_seg)]
+        elif direct:
+            block_idx = store['groups'][(None, h, w)][0] if (None, h, w) in store['groups'] else np.zeros(0, np.int64)
+            if len(block_idx) <= 1:     # as below
+                continue
+            segments = [(store['raw'], store['flow'], block_idx)]
         else:
             data = np.asarray(fset[h][w])
             if len(data) <= 1:          # train.py:370 "num > 1 for data parallel"

@@ -122,6 +122,10 @@ class CubeStore:
     def __len__(self):
         return self.n
 
+    def take(self, sel):
+        """Store indices of the set's cubes ``sel``: the set is the whole store."""
+        return sel
+
 
 def context_range(indice, border_mode, context_frame_num, tot_frame_num, frame_video_idx):
     """Frame indices of the temporal context of frame ``indice`` (reference vad_datasets.py:277-356; the three dataset
