@@ -116,7 +116,9 @@ typedef struct vv_conv_params {
   const float* bias; /* [G][Cout] or NULL */
   int64_t bias_gstride;
   vv_view out;       /* output */
-  float* stats;      /* NULL or [G][ntiles][2][Cout] partial sums (sum, sum of squares) over valid pixels */
+  float* stats;      /* NULL or [G][ntiles][2][Cout] partial sums (sum, sum of squares) over valid pixels; ntiles = vv_conv_ntiles2 of
+                        the launch's kind / pad0.  VV_CONVT_FWD keeps no column sums: such a launch with stats != NULL returns
+                        VV_ERR_UNSUPPORTED (fp32 and bf16) */
   /* vv_conv_wino only, data-gradient launches: the first reduction pass of the BatchNorm backward that consumes this output
    * (vv_bn_bwd_reduce) done in the epilogue.  out = dA of the producing layer's activation relu(a z + b); with z that layer's
    * conv output [G][B*H*W][Cout] (pixel stride Cout) the kernel also leaves  sum dz, sum dz * xhat  per pixel tile, dz = dA [a z + b > 0],
@@ -140,11 +142,12 @@ typedef struct vv_conv_params {
 int vv_conv_mfma(const vv_conv_params* p, vv_stream stream);
 /* number of pixel tiles the kernel uses for this (B,H,W): rows of the `stats` partial array */
 int vv_conv_ntiles(int32_t B, int32_t H, int32_t W);
-/* the same for a launch with these `kind` / pad0 `flags` (the bf16 3x3 kernels use 128-pixel tiles on the 8x8 / 4x4 levels) */
+/* the same for a launch with these `kind` / pad0 `flags`: the bf16 3x3 kernels use 128-pixel tiles on the 8x8 / 4x4 levels; the fp32
+ * VV_CONVT_DGRAD kernel uses them on the 16x16 / 8x8 / 4x4 levels, where this returns vv_convt_dgrad_ntiles(B, H, W, 0) */
+int vv_conv_ntiles2(int32_t B, int32_t H, int32_t W, int32_t kind, int32_t flags);
 /* pixel tiles of a VV_CONVT_DGRAD launch of vv_conv_mfma (H x W = its output = the transposed conv's INPUT resolution; flags: the
  * launch's pad0, only VV_CONV_BF16 matters) = the rows of bn_partial such a launch leaves; -1 for an unsupported size */
 int vv_convt_dgrad_ntiles(int32_t B, int32_t H, int32_t W, int32_t flags);
-int vv_conv_ntiles2(int32_t B, int32_t H, int32_t W, int32_t kind, int32_t flags);
 
 /* Weight-gradient (autograd of nn.Conv2d / nn.ConvTranspose2d wrt weight; cuDNN in the reference).
  * dW[tap][ci][co] = sum_pixels act[pixel+tap][ci] * dy[pixel][co]  (CONV3)

@@ -560,6 +560,8 @@ extern "C" int vv_conv_ntiles2(int32_t B, int32_t H, int32_t W, int32_t kind, in
   if (vv_gemm16_flags(kind, flags)) return vv_conv_ntiles(B, H, W);          // vv_conv_bf16.hip: 256-pixel tiles everywhere
   if ((flags & VV_CONV_BF16) && kind == VV_CONV3 && H == W && H == 16) return B * 2;
   if ((flags & VV_CONV_BF16) && kind == VV_CONV3 && H == W && (H == 8 || H == 4)) return (B + (H == 8 ? 1 : 7)) / (H == 8 ? 2 : 8);
+  // fp32 stride-2 gather: dispatch<VV_CONVT_DGRAD, .., false> runs 128-pixel tiles on the 16x16 / 8x8 / 4x4 levels
+  if (!(flags & VV_CONV_BF16) && kind == VV_CONVT_DGRAD && H == W && (H == 16 || H == 8 || H == 4)) return vv_convt_dgrad_ntiles(B, H, W, 0);
   return vv_conv_ntiles(B, H, W);
 }
 
@@ -575,6 +577,7 @@ extern "C" int vv_conv_mfma(const vv_conv_params* p, vv_stream stream) {
   if ((p->pad0 & VV_CONV_OUT_BF16) && !bf) return VV_ERR_BAD_ARG;
   if ((p->pad0 & VV_CONV_ALLSRC_BF16) && (!bf || p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE)) return VV_ERR_BAD_ARG;
   if (p->CinP % 8) return VV_ERR_BAD_ARG;
+  if (p->kind == VV_CONVT_FWD && p->stats) return VV_ERR_UNSUPPORTED;   // the four-phase store keeps no column sums: refuse, do not store zeros
   if (p->bn_partial && !bf && p->kind == VV_CONVT_DGRAD) {
     // fp32 stride-2 gather (the transposed conv's data gradient = dA of the conv layer in front of it): sums per 128-pixel tile,
     // rows = vv_convt_dgrad_ntiles(B, H, W, 0)
