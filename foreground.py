@@ -17,6 +17,7 @@ motion stage runs on the GPU (vec_vad_amd/motion.py) on top of whatever detector
 The mmdet detector itself is not part of this build.
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -136,6 +137,36 @@ def _datasets(c, mode, all_bboxes, direct_flow=False):
     return raw, flow
 
 
+def _stage(c, mode, direct_flow=False):
+    """What every extractor starts from: the split's boxes and datasets, the ``<root>/<modality>/<ds>_`` prefix of its files (the
+    directory is made), the block grid and its steps, ``motionThr``, ``<mode>_block_mode`` and the patch size."""
+    cp, ds, hb, wb = c['cp'], c['dataset_name'], c['h_block'], c['w_block']
+    boxes = load_bboxes(c, mode)
+    raw_ds, flow_ds = _datasets(c, mode, boxes, direct_flow)
+    os.makedirs(os.path.join(c['data_root_dir'], c['modality']), exist_ok=True)
+    return SimpleNamespace(boxes=boxes, raw_ds=raw_ds, flow_ds=flow_ds, base=os.path.join(c['data_root_dir'], c['modality'], ds + '_'),
+                           hb=hb, wb=wb, h_step=frame_size[ds][0] / hb, w_step=frame_size[ds][1] / wb, patch=cp.getint(ds, 'patch_size'),
+                           motion_thr=cp.getfloat(ds, 'motionThr'), block_mode=cp.getint(ds, '{}_block_mode'.format(mode)))
+
+
+def _blocks(st, bb):
+    """The ``(hi, wi)`` grid cells box ``bb`` is filed under."""
+    return calc_block_idx(bb[0], bb[2], bb[1], bb[3], st.h_step, st.w_step, mode=st.block_mode)
+
+
+def _write_frame_index(st, ds, mode):
+    """Writes and returns ``scene_idx`` (ShanghaiTech, else None) and the frame-level ``labels`` the evaluation step reads (test
+    split with ground truth, else None; test.py:376-392 gets them through the dataset)."""
+    scene_idx = labels = None
+    if ds == 'ShanghaiTech':
+        scene_idx = np.asarray(st.raw_ds.scene_idx)
+        np.save(st.base + 'scene_idx.npy', st.raw_ds.scene_idx)
+    if mode == 'test' and st.raw_ds.return_gt:
+        labels = np.array([bool(np.asarray(st.raw_ds._gt(i)).max() > 0) for i in range(len(st.raw_ds))])
+        np.save(st.base + 'frame_labels_test.npy', labels)
+    return scene_idx, labels
+
+
 def frame_cubes(raw_ds, flow_ds, idx, motion_thr, device='cuda'):
     """Cubes of frame ``idx`` that pass the motion test: (raw ``[m,(T,)P,P,3]`` uint8, flow ``[m,(Tf,)P,P,2]`` float32,
     kept box indices).  Flow energy per box = sum of squares over the patch (mean over the context frames when there is a
@@ -155,15 +186,10 @@ def frame_cubes(raw_ds, flow_ds, idx, motion_thr, device='cuda'):
 def extract_train(c, device='cuda', log=print):
     """train.py:102-226 for modality raw2flow.  Writes ``<root>/raw2flow/<ds>_foreground_train_<fg>-{raw,flow}.npy``
     (ShanghaiTech: ``..._seg_<k>-{raw,flow}.npy`` every ``saveSegNum`` frames, frames visited in a random order)."""
-    cp, ds, fg, root, mod = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality']
-    hb, wb = c['h_block'], c['w_block']
-    all_bboxes = load_bboxes(c, 'train')
-    raw_ds, flow_ds = _datasets(c, 'train', all_bboxes)
-    h_step, w_step = frame_size[ds][0] / hb, frame_size[ds][1] / wb
-    motion_thr, block_mode = cp.getfloat(ds, 'motionThr'), cp.getint(ds, 'train_block_mode')
-    shanghai = ds == 'ShanghaiTech'
-    os.makedirs(os.path.join(root, mod), exist_ok=True)
-    base = os.path.join(root, mod, ds + '_foreground_train_{}'.format(fg))
+    st = _stage(c, 'train')
+    all_bboxes, raw_ds, flow_ds, hb, wb = st.boxes, st.raw_ds, st.flow_ds, st.hb, st.wb
+    shanghai = c['dataset_name'] == 'ShanghaiTech'
+    base = st.base + 'foreground_train_{}'.format(c['mode_fg'])
 
     def empty():
         def grid():
@@ -177,18 +203,17 @@ def extract_train(c, device='cuda', log=print):
         save_nested(base + suffix + '-flow.npy', pick(1), 3 if shanghai else 2)
 
     order = np.random.default_rng(c['shuffle_seed']).permutation(len(raw_ds)) if shanghai else np.arange(len(raw_ds))
-    seg_num = cp.getint(ds, 'saveSegNum') if shanghai else 0
+    seg_num = c['cp'].getint(c['dataset_name'], 'saveSegNum') if shanghai else 0
     sets, count, seg = empty(), 0, 0
     for it, idx in enumerate(order):
         idx = int(idx)
         log('Extracting foreground in {}-th batch, {} in total'.format(it + 1, len(raw_ds)))
         boxes = all_bboxes[idx]
         if len(boxes) > 0:
-            raw, flow, keep = frame_cubes(raw_ds, flow_ds, idx, motion_thr, device)
+            raw, flow, keep = frame_cubes(raw_ds, flow_ds, idx, st.motion_thr, device)
             grid = sets[raw_ds.scene_idx[idx] - 1] if shanghai else sets
             for k, b in enumerate(keep):
-                bb = boxes[b]
-                for (hi, wi) in calc_block_idx(bb[0], bb[2], bb[1], bb[3], h_step, w_step, mode=block_mode):
+                for (hi, wi) in _blocks(st, boxes[b]):
                     grid[hi][wi][0].append(raw[k])
                     grid[hi][wi][1].append(flow[k])
         count += 1
@@ -206,36 +231,24 @@ def extract_train(c, device='cuda', log=print):
 def extract_test(c, device='cuda', log=print):
     """test.py:98-176: per-frame, per-block cubes + their boxes ->
     ``<ds>_foreground_test_<fg>-{raw,flow}.npy``, ``<ds>_foreground_bbox_test_<fg>.npy`` (+ ``<ds>_scene_idx.npy``)."""
-    cp, ds, fg, root, mod = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality']
-    hb, wb = c['h_block'], c['w_block']
-    all_bboxes = load_bboxes(c, 'test')
-    raw_ds, flow_ds = _datasets(c, 'test', all_bboxes)
-    os.makedirs(os.path.join(root, mod), exist_ok=True)
-    base = os.path.join(root, mod, ds + '_')
-    if ds == 'ShanghaiTech':
-        np.save(base + 'scene_idx.npy', raw_ds.scene_idx)
-    h_step, w_step = frame_size[ds][0] / hb, frame_size[ds][1] / wb
-    motion_thr, block_mode = cp.getfloat(ds, 'motionThr'), cp.getint(ds, 'test_block_mode')
-    n = len(raw_ds)
-    sets = [[[([], [], []) for _ in range(wb)] for _ in range(hb)] for _ in range(n)]
+    st = _stage(c, 'test')
+    _write_frame_index(st, c['dataset_name'], 'test')
+    n = len(st.raw_ds)
+    sets = [[[([], [], []) for _ in range(st.wb)] for _ in range(st.hb)] for _ in range(n)]
     for idx in range(n):
         log('Extracting foreground in {}-th batch, {} in total'.format(idx + 1, n))
-        boxes = all_bboxes[idx]
+        boxes = st.boxes[idx]
         if len(boxes) > 0:
-            raw, flow, keep = frame_cubes(raw_ds, flow_ds, idx, motion_thr, device)
+            raw, flow, keep = frame_cubes(st.raw_ds, st.flow_ds, idx, st.motion_thr, device)
             for k, b in enumerate(keep):
                 bb = boxes[b]
-                for (hi, wi) in calc_block_idx(bb[0], bb[2], bb[1], bb[3], h_step, w_step, mode=block_mode):
+                for (hi, wi) in _blocks(st, bb):
                     cell = sets[idx][hi][wi]
                     cell[0].append(raw[k])
                     cell[1].append(flow[k])
                     cell[2].append(bb)
     for k, name in ((0, 'foreground_test_{}-raw.npy'), (1, 'foreground_test_{}-flow.npy'), (2, 'foreground_bbox_test_{}.npy')):
-        save_nested(base + name.format(fg), [[[np.array(cell[k]) for cell in row] for row in fr] for fr in sets], 3)
-    # frame-level ground truth for the evaluation step (test.py:376-392 reads it through the dataset at evaluation time)
-    if raw_ds.return_gt:
-        labels = np.array([bool(np.asarray(raw_ds._gt(i)).max() > 0) for i in range(n)])
-        np.save(base + 'frame_labels_test.npy', labels)
+        save_nested(st.base + name.format(c['mode_fg']), [[[np.array(cell[k]) for cell in row] for row in fr] for fr in sets], 3)
     log('foreground for testing data saved!')
 
 
@@ -282,30 +295,18 @@ def extract_device(c, mode='test', device='cuda', log=print, flownet2=None):
     ``[mi355x] direct_flow_pairs`` pairs per FlowNet2 launch, straight into the chunk's flow tensor.  A flow shared by two chunks is
     computed in both.  ``flownet2``: the network to use; None loads ``[mi355x] flownet2_checkpoint`` (``direct_flow_fp16``: in fp16 mode)."""
     from vec_vad_amd.extract import boxes_to_crops, chunk_windows, cube_cut, cube_energy
-    cp, ds, root, mod = c['cp'], c['dataset_name'], c['data_root_dir'], c['modality']
-    hb, wb = c['h_block'], c['w_block']
     direct_flow = bool(c.get('direct_flow', False))
     if direct_flow:
         from calc_optical_flow import chunk_flows, flow_pairs, load_flownet2
         if flownet2 is None:
             flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
         flow_pairs_per_launch = max(1, c['direct_flow_pairs'])
-    all_bboxes = load_bboxes(c, mode)
-    raw_ds, flow_ds = _datasets(c, mode, all_bboxes, direct_flow)
-    os.makedirs(os.path.join(root, mod), exist_ok=True)
-    base = os.path.join(root, mod, ds + '_')
+    st = _stage(c, mode, direct_flow)
+    all_bboxes, raw_ds, flow_ds, hb, wb, motion_thr, P = st.boxes, st.raw_ds, st.flow_ds, st.hb, st.wb, st.motion_thr, st.patch
     n = len(raw_ds)
-    info = dict(n_frames=n, scene_idx=None, labels=None)
-    if ds == 'ShanghaiTech':
-        info['scene_idx'] = np.asarray(raw_ds.scene_idx)
-        np.save(base + 'scene_idx.npy', raw_ds.scene_idx)
-    if mode == 'test' and raw_ds.return_gt:
-        info['labels'] = np.array([bool(np.asarray(raw_ds._gt(i)).max() > 0) for i in range(n)])
-        np.save(base + 'frame_labels_test.npy', info['labels'])
-    h_step, w_step = frame_size[ds][0] / hb, frame_size[ds][1] / wb
-    motion_thr, block_mode = cp.getfloat(ds, 'motionThr'), cp.getint(ds, '{}_block_mode'.format(mode))
+    scene_idx, labels = _write_frame_index(st, c['dataset_name'], mode)
+    info = dict(n_frames=n, scene_idx=scene_idx, labels=labels)
     per_chunk, max_cubes = max(1, c['direct_frames_per_chunk']), max(1, c['direct_max_cubes'])
-    P = cp.getint(ds, 'patch_size')
 
     def window(dataset, i):
         return [i] if dataset.context_frame_num == 0 else dataset.context_range(i)
@@ -374,7 +375,7 @@ def extract_device(c, mode='test', device='cuda', log=print, flownet2=None):
                     cube_frame, cube_blocks, cube_boxes = [], [], []
                 for b in kept:
                     bb = all_bboxes[i][b]
-                    blocks = calc_block_idx(bb[0], bb[2], bb[1], bb[3], h_step, w_step, mode=block_mode)
+                    blocks = _blocks(st, bb)
                     if any(not (0 <= hi < hb and 0 <= wi < wb) for hi, wi in blocks):
                         raise IndexError('box {} of frame {} falls outside the {}x{} block grid'.format(b, i, hb, wb))
                     slot[p + b] = used_slots

@@ -54,7 +54,8 @@ def load_model(net, state_dict, device):
 def load_artifacts(base, fg, method, shanghai, build_net, device, h_block=1, w_block=1):
     """test.py:230-266: the three files train.py wrote (torch pickles despite the .npy suffix, train.py:432-436) -> (net_set,
     raw statistics, flow statistics) with the reference's nesting -- [h][w] for UCSDped2 / avenue, [scene][h][w] for ShanghaiTech;
-    a block without a trained model is an empty list (train.py:370 skips blocks with <= 1 cube).  Works on files written by the
+    a block without a trained model is an empty list (train.py:370 skips blocks with <= 1 cube).  The nesting of all three results
+    follows the model FILE: ``h_block`` / ``w_block`` are accepted for compatibility and ignored.  Works on files written by the
     reference itself (tests/test_ref_written_files.py): 'module.'-prefixed keys, aliased storages, int64 num_batches_tracked."""
     weights = torch.load(base + 'model_{}_{}.npy'.format(fg, method), map_location='cpu', weights_only=False)
     raw_tr = torch.load(base + 'raw_training_scores_{}_{}.npy'.format(fg, method), weights_only=False)
@@ -67,28 +68,20 @@ def load_artifacts(base, fg, method, shanghai, build_net, device, h_block=1, w_b
         a = np.asarray(a)
         return (np.mean(a), np.std(a)) if a.size else (0.0, 1.0)      # population std, test.py:264-266
 
-    if shanghai:
-        net_set = [[[build(weights[s][hh][ww]) for ww in range(len(weights[s][hh]))] for hh in range(len(weights[s]))]
-                   for s in range(len(weights))]
-        # (the statistics' nesting follows the FILE like the networks' does: h_block / w_block are accepted for compatibility only)
-        st_r = [[[stat(raw_tr[s][hh][ww]) for ww in range(len(weights[s][hh]))] for hh in range(len(weights[s]))]
-                for s in range(len(weights))]
-        st_o = [[[stat(of_tr[s][hh][ww]) for ww in range(len(weights[s][hh]))] for hh in range(len(weights[s]))]
-                for s in range(len(weights))]
-    else:
-        net_set = [[build(weights[hh][ww]) for ww in range(len(weights[hh]))] for hh in range(len(weights))]
-        st_r = [[stat(raw_tr[hh][ww]) for ww in range(len(weights[hh]))] for hh in range(len(weights))]
-        st_o = [[stat(of_tr[hh][ww]) for ww in range(len(weights[hh]))] for hh in range(len(weights))]
-    return net_set, st_r, st_o
+    def over(fn, src, like, depth):
+        return fn(src) if depth == 0 else [over(fn, src[i], like[i], depth - 1) for i in range(len(like))]
+
+    depth = 3 if shanghai else 2
+    return over(build, weights, weights, depth), over(stat, raw_tr, weights, depth), over(stat, of_tr, weights, depth)
 
 
 def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=None):
     """cube_list / flow_list: per-frame arrays [n_i,5,32,32,3] uint8 / [n_i,(Tf,)32,32,2] fp32 (n_i may be 0).
     The cubes go to the GPU in bounded super-chunks (``chunk_cubes``, default 32 launches' worth, >= 4096: ~55 KB per cube for the
     5raw+5of bank, so host and device staging stay at a few hundred MB whatever the size of the test set) through ONE fixed device
-    staging buffer, and are scored in launches of exactly ``score_batch`` cubes (the tail launch re-scores the chunk's last cube
-    as padding: eval-mode scores do not depend on the batch) -- one workspace, one launch plan and one captured hipGraph serve
-    the whole test set.  Returns the DEVICE tensors (raw [n], of [n] | None) of all cubes in frame order -- they feed
+    staging buffer, and every chunk is scored by ``score_index_list`` in launches of exactly ``score_batch`` cubes (the tail launch
+    re-scores the chunk's last cube as padding: eval-mode scores do not depend on the batch) -- one workspace, one launch plan and
+    one captured hipGraph serve the whole test set.  Returns the DEVICE tensors (raw [n], of [n] | None) of all cubes in frame order -- they feed
     vv_frame_scores without visiting the host."""
     dev = trainer.bank.device
     keep = [k for k in range(len(cube_list)) if len(cube_list[k])]
@@ -122,15 +115,13 @@ def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=N
             return
         rawd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_r))))
         flowd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_f))))
-        for s0 in range(0, m_tot, B):
-            idx = torch.arange(s0, s0 + B, device=dev).clamp_(max=m_tot - 1)
-            r, o = trainer.score_cubes(rawd, flowd, idx)
-            m = min(B, m_tot - s0)
-            r_all[done + s0:done + s0 + m] = r[:m]
-            if o is not None:
-                if o_all is None:
-                    o_all = torch.empty(n, device=dev)
-                o_all[done + s0:done + s0 + m] = o[:m]
+        # launches of B cubes whatever the chunk holds: B comes from the whole list, and the bank picks its kernels by it
+        r, o = score_index_list(trainer, rawd, flowd, torch.arange(m_tot, device=dev), score_batch, batch=B)
+        r_all[done:done + m_tot] = r
+        if o is not None:
+            if o_all is None:
+                o_all = torch.empty(n, device=dev)
+            o_all[done:done + m_tot] = o
         done += m_tot
         pend_r, pend_f, pend_n = [], [], 0
 
@@ -198,6 +189,35 @@ def _save_masks(result_dir, frames, mask_groups, h, w):
         torch.save(fmap, os.path.join(result_dir, '{}'.format(f)))
 
 
+def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups):
+    """The per-group body of ``score_frames`` and ``score_store``.  The returned ``group(key, hh, ww, n, off, boxes, score)`` scores
+    the ``n`` cubes of block ``(hh, ww)`` (of scene ``key``, or None) with ``score(trainer)`` -> device (raw [n], of [n] | None),
+    max-accumulates their frame scores into ``fs_dev`` (``off``: CSR over the frames, ``boxes`` float64 ``[n,4]``) and, when
+    ``mask_groups`` is a list, appends the group's (off, host cube scores, boxes) for ``_save_masks``."""
+    def group(key, hh, ww, n, off, boxes, score):
+        def pick(nested):
+            return nested[key][hh][ww] if key is not None else nested[hh][ww]
+        models = pick(net_set)
+        if len(models) > 0:
+            net = models[0]
+            if id(net) not in trainers:
+                trainers[id(net)] = FusedTrainer(net)
+            st_r = pick(stats_raw)
+            st_o = pick(stats_of) if useFlow else (0.0, 1.0)
+            r, o = score(trainers[id(net)])
+            o = o if useFlow else None
+            stats = np.array([[st_r[0], st_r[1], st_o[0], st_o[1]]], np.float64)
+            cube_stat = np.zeros(n, np.int32)
+        else:        # anomaly: no object in the training set in this block (test.py:346-348)
+            r, o = torch.zeros(n, device=device), None
+            stats = np.array([[0.0, 1.0, 0.0, 1.0]])
+            cube_stat = np.full(n, -1, np.int32)
+        scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(boxes, h, w), w_raw, w_of, out=fs_dev)
+        if mask_groups is not None:
+            mask_groups.append((off, _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0), boxes))
+    return group
+
+
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
                  device, score_batch=2048, scene_idx=None, result_dir=None, log=print, return_device=False):
     """Per-frame anomaly scores.  ``net_set[(s,)hh][ww]`` is a list with 0 or 1 eval-mode networks;
@@ -210,7 +230,7 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
     mask_groups = [] if result_dir else None      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
     fs_dev = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
     hb, wb = len(foreground_set[0]), len(foreground_set[0][0])
-    trainers = {}
+    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups)
     keys = sorted(set(scene_idx[f] - 1 for f in range(n_frames))) if scene_idx is not None else [None]
     for hh in range(hb):
         for ww in range(wb):
@@ -222,42 +242,24 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
                 if counts.sum() == 0:
                     continue
                 frames = [f for f in frames if counts[f]]
-                models = net_set[key][hh][ww] if key is not None else net_set[hh][ww]
                 boxes = np.concatenate([np.asarray(bbox_set[f][hh][ww], dtype=np.float64)[:, :4] for f in frames])
-                off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-                n = int(off[-1])
-                if len(models) > 0:
-                    net = models[0]
-                    if id(net) not in trainers:
-                        trainers[id(net)] = FusedTrainer(net)
-                    st_r = stats_raw[key][hh][ww] if key is not None else stats_raw[hh][ww]
-                    st_o = (stats_of[key][hh][ww] if key is not None else stats_of[hh][ww]) if useFlow else (0.0, 1.0)
-                    r, o = score_cubes_device(trainers[id(net)], [foreground_set[f][hh][ww] for f in frames],
-                                              [foreground_set2[f][hh][ww] for f in frames], score_batch)
-                    o = o if useFlow else None
-                    stats = np.array([[st_r[0], st_r[1], st_o[0], st_o[1]]], np.float64)
-                    cube_stat = np.zeros(n, np.int32)
-                else:        # anomaly: no object in the training set in this block (test.py:346-348)
-                    r, o = torch.zeros(n, device=device), None
-                    stats = np.array([[0.0, 1.0, 0.0, 1.0]])
-                    cube_stat = np.full(n, -1, np.int32)
-                scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(boxes, h, w), w_raw, w_of, out=fs_dev)
-                if mask_groups is not None:
-                    sc = _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0)
-                    mask_groups.append((off, sc, boxes))           # off is indexed by frame: cubes of frame f = [off[f], off[f+1])
+                off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)      # indexed by frame: cubes of frame f = [off[f], off[f+1])
+                group(key, hh, ww, int(off[-1]), off, boxes, lambda tr: score_cubes_device(
+                    tr, [foreground_set[f][hh][ww] for f in frames], [foreground_set2[f][hh][ww] for f in frames], score_batch))
     if result_dir:
         _save_masks(result_dir, range(n_frames), mask_groups, h, w)
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
-def score_index_list(trainer, raw_store, flow_store, idx, score_batch):
-    """Scores of the store cubes named by ``idx`` (int64 ``[n]``, n > 0, repeats allowed), in the launch shapes of
-    ``score_cubes_device``: launches of exactly ``score_batch`` cubes (of ``n`` when the list is shorter than one launch), the tail
-    launch padded by repeating the last index.  Returns the DEVICE tensors (raw [n], of [n] | None) in list order."""
+def score_index_list(trainer, raw_store, flow_store, idx, score_batch, batch=None):
+    """Scores of the store cubes named by ``idx`` (int64 ``[n]``, numpy or device tensor, n > 0, repeats allowed): THE launch loop
+    of the test stage.  Launches of exactly ``batch`` cubes -- default: ``score_batch``, or ``n`` when the list is shorter than one
+    launch; ``score_cubes_device`` passes the size it derived from its whole list for every chunk --, the tail launch padded by
+    repeating the last index.  Returns the DEVICE tensors (raw [n], of [n] | None) in list order."""
     dev = trainer.bank.device
     n = len(idx)
-    B = n if n < score_batch else int(score_batch)
-    idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+    B = int(batch) if batch is not None else (n if n < score_batch else int(score_batch))
+    idx_d = (idx if torch.is_tensor(idx) else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))).to(dev)
     r_all, o_all = torch.empty(n, device=dev), None
     for s0 in range(0, n, B):
         m = min(B, n - s0)
@@ -280,9 +282,9 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     ``foreground.block_groups`` (scene = ``scene_idx[f] - 1`` when ``scene_idx`` is given, else None; ``off`` CSR over all frames);
     ``boxes`` float ``[N,>=4]``, one row per store cube.  A cube named by two index lists is stored once and scored once per list.
 
-    Every group feeds ``scoring.frame_scores`` with the statistics, ``cube_stat`` and paints that ``score_frames`` gives it, and
-    the launches have the shapes ``score_cubes_device`` uses, so the frame scores and the masks under ``result_dir`` are the
-    staged path's.  ``out`` (CUDA float64 ``[n_frames]``, initialised to ``-BIG``) is max-accumulated into: a test set that comes
+    Both routes run one group body (``_group_scorer``) and one launch loop (``score_index_list``, which ``score_cubes_device`` calls
+    on its staging buffers), so the statistics, ``cube_stat``, paints and launch shapes -- hence the frame scores and the masks under
+    ``result_dir`` -- are the staged path's by construction.  ``out`` (CUDA float64 ``[n_frames]``, initialised to ``-BIG``) is max-accumulated into: a test set that comes
     in several parts (``[mi355x] direct_max_cubes``) is scored part by part, with ``frame_range`` = the ``(first, end)`` frames whose
     masks this call writes (default: all) and ``trainers`` = a dict that keeps the engines between calls."""
     raw_store, flow_store = store
@@ -296,35 +298,15 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     else:
         raise ValueError('score_store: no group, no out and no frame_range to tell the number of frames')
     fs_dev = out if out is not None else torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
-    trainers = {} if trainers is None else trainers
     mask_groups = [] if result_dir else None
+    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {} if trainers is None else trainers,
+                          fs_dev, mask_groups)
     for gk in sorted(groups, key=lambda k: (k[1], k[2], -1 if k[0] is None else k[0])):
-        key, hh, ww = gk
-        if (key is None) != (scene_idx is None):
+        if (gk[0] is None) != (scene_idx is None):
             raise ValueError('group %r does not fit scene_idx %s' % (gk, 'given' if scene_idx is not None else 'absent'))
         idx, off = groups[gk]
-        n = len(idx)
-        if n == 0:
-            continue
-        models = net_set[key][hh][ww] if key is not None else net_set[hh][ww]
-        gboxes = boxes[idx]
-        if len(models) > 0:
-            net = models[0]
-            if id(net) not in trainers:
-                trainers[id(net)] = FusedTrainer(net)
-            st_r = stats_raw[key][hh][ww] if key is not None else stats_raw[hh][ww]
-            st_o = (stats_of[key][hh][ww] if key is not None else stats_of[hh][ww]) if useFlow else (0.0, 1.0)
-            r, o = score_index_list(trainers[id(net)], raw_store, flow_store, idx, score_batch)
-            o = o if useFlow else None
-            stats = np.array([[st_r[0], st_r[1], st_o[0], st_o[1]]], np.float64)
-            cube_stat = np.zeros(n, np.int32)
-        else:        # anomaly: no object in the training set in this block (test.py:346-348)
-            r, o = torch.zeros(n, device=device), None
-            stats = np.array([[0.0, 1.0, 0.0, 1.0]])
-            cube_stat = np.full(n, -1, np.int32)
-        scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(gboxes, h, w), w_raw, w_of, out=fs_dev)
-        if mask_groups is not None:
-            mask_groups.append((off, _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0), gboxes))
+        if len(idx):
+            group(*gk, len(idx), off, boxes[idx], lambda tr: score_index_list(tr, raw_store, flow_store, idx, score_batch))
     if result_dir:
         first, end = frame_range if frame_range is not None else (0, n_frames)
         _save_masks(result_dir, range(first, end), mask_groups, h, w)
@@ -367,24 +349,22 @@ def main(config_path='config.cfg', flownet2=None):
     results_dir = 'results'
     shanghai = ds == 'ShanghaiTech'
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
-    if direct:
-        fs = score_direct(c, device, os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None,
-                          flownet2=flownet2)
-        os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
-        np.save(frame_scores_path, fs)
-    elif not cp.getboolean(ds, 'scores_saved'):
-        fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
-        fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
-        bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)
-        scene_idx = np.load(base + 'scene_idx.npy') if shanghai else None
-        net_set, st_r, st_o = load_artifacts(base, fg, method, shanghai, lambda: build_network(c), device, c['h_block'], c['w_block'])
-        mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
-        fs = score_frames(net_set, st_r, st_o, fset, fset2, bset, h, w, c['w_raw'], c['w_of'], c['useFlow'], device,
-                          c['score_batch'], scene_idx, mask_dir)
-        os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
-        np.save(frame_scores_path, fs)
-    else:
+    if cp.getboolean(ds, 'scores_saved'):
         fs = np.load(frame_scores_path)
+    else:
+        mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
+        if direct:
+            fs = score_direct(c, device, mask_dir, flownet2=flownet2)
+        else:
+            fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
+            fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
+            bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)
+            scene_idx = np.load(base + 'scene_idx.npy') if shanghai else None
+            net_set, st_r, st_o = load_artifacts(base, fg, method, shanghai, lambda: build_network(c), device, c['h_block'], c['w_block'])
+            fs = score_frames(net_set, st_r, st_o, fset, fset2, bset, h, w, c['w_raw'], c['w_of'], c['useFlow'], device,
+                              c['score_batch'], scene_idx, mask_dir)
+        os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
+        np.save(frame_scores_path, fs)
 
     # ---- evaluation (test.py:362-399), criterion = 'frame'
     lab_path = base + 'frame_labels_test.npy'

@@ -16,6 +16,17 @@ def digest(t, k=8):
                            a[idx].numpy()])
 
 
+def small_config(test_block_mode=True):
+    """The stock config.cfg shrunk for the script-level tests, written to ./config.cfg and returned: one epoch, batches of 4, and
+    for UCSDped2 a 2x2 block grid with ``train_block_mode = 9`` (and ``test_block_mode = 9`` unless told otherwise)."""
+    cfg = open(os.path.join(os.path.dirname(os.path.dirname(GOLDEN)), 'config.cfg')).read()
+    cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('batch_size = 128', 'batch_size = 4')
+    cfg = cfg.replace('[UCSDped2]\n', '[UCSDped2]\nh_block = 2\nw_block = 2\ntrain_block_mode = 9\n'
+                      + ('test_block_mode = 9\n' if test_block_mode else ''))      # dataset-level overrides
+    open('config.cfg', 'w').write(cfg)
+    return cfg
+
+
 def load_golden(name):
     return dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
 

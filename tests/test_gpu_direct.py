@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from _util import small_config
+
 pytestmark = pytest.mark.gpu
 
 F, H, W, P = 4, 72, 80, 32
@@ -247,10 +249,7 @@ def test_main_direct_equals_staged(tmp_path, monkeypatch):
     import test as S
     monkeypatch.chdir(tmp_path)
     _synthetic_ped2_tree(np.random.default_rng(11))
-    cfg = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'config.cfg')).read()
-    cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('batch_size = 128', 'batch_size = 4')
-    cfg = cfg.replace('[UCSDped2]\n', '[UCSDped2]\nh_block = 2\nw_block = 2\ntrain_block_mode = 9\ntest_block_mode = 9\n')
-    open('config.cfg', 'w').write(cfg)
+    cfg = small_config()
     scores = 'results/UCSDped2/frame_scores_obj_det_with_motion_SelfComplete.npy'
 
     def cube_files():
@@ -300,3 +299,40 @@ def test_main_direct_equals_staged(tmp_path, monkeypatch):
     assert len(ranges) > 1 and ranges[0][0] == 0 and ranges[-1][1] == 4 == info['n_frames']
     assert all(prev[1] == nxt[0] for prev, nxt in zip(ranges, ranges[1:])) and all(0 < k <= 3 for k in counts[:-1]) and counts[-1] <= 3
     assert info['scene_idx'] is None and info['labels'].tolist() == [False, True, False, True]
+
+
+def test_a_short_list_under_a_forced_launch_size_is_padded_not_shrunk(cube_set, models):
+    """``score_index_list(..., batch=4)`` on 2 cubes is ONE launch of 4 cubes, the last one repeated -- what the staged route's
+    tail chunk relies on: bit for bit the first two scores of that 4-cube launch (a launch of 2 takes other kernels)."""
+    import test as S
+    from vec_vad_amd.trainer import FusedTrainer
+    tr = FusedTrainer(models[0]['net_set'][0][0][0])
+    store = (torch.from_numpy(cube_set['raw']).cuda(), torch.from_numpy(cube_set['flow']).cuda())
+    calls = []
+    score_cubes = tr.score_cubes
+    tr.score_cubes = lambda raw, flow, idx: calls.append(idx.cpu().tolist()) or score_cubes(raw, flow, idx)
+    r4, o4 = (t.clone() for t in score_cubes(*store, torch.tensor([7, 3, 3, 3], device='cuda')))        # the launch itself
+    for idx in (np.array([7, 3]), torch.tensor([7, 3], device='cuda')):          # host list | device list
+        r, o = S.score_index_list(tr, *store, idx, score_batch=4, batch=4)
+        assert r.shape == o.shape == (2,) and torch.equal(r, r4[:2]) and torch.equal(o, o4[:2])
+    assert calls == [[7, 3, 3, 3]] * 2
+    r2, _ = S.score_index_list(tr, *store, np.array([7, 3]), score_batch=4)         # the default rule: a launch of n = 2 cubes
+    assert calls[-1] == [7, 3] and r2.shape == (2,)
+
+
+def test_score_store_equals_score_frames_with_masks_and_without_flow(tmp_path, cube_set, models):
+    """``result_dir`` set and ``useFlow=False`` on the set that has a block without a trained model: same frame scores, same masks."""
+    import test as S
+    from foreground import block_groups
+    m = models[0]
+    fset, fset2, bset = cube_set['host']
+    da, db = str(tmp_path / 'staged'), str(tmp_path / 'direct')
+    fs_a = S.score_frames(m['net_set'], m['st_r'], m['st_o'], fset, fset2, bset, FH, FW, 1.0, 0.5, False, 'cuda', score_batch=4,
+                          result_dir=da)
+    store = (torch.from_numpy(cube_set['raw']).cuda(), torch.from_numpy(cube_set['flow']).cuda())
+    groups = block_groups(cube_set['cube_frame'], cube_set['cube_blocks'], len(COUNTS))
+    fs_b = S.score_store(m['net_set'], m['st_r'], m['st_o'], store, groups, cube_set['boxes'], FH, FW, 1.0, 0.5, False, 'cuda', 4,
+                         None, db)
+    assert fs_a.shape == (7,) and np.array_equal(fs_a, fs_b)
+    assert fs_a[1] == -S.BIG and (fs_a == S.BIG).any()              # a frame without cubes; a cube in the block without a model
+    _masks_equal(da, db, 7)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from _util import small_config
+
 pytestmark = pytest.mark.gpu
 
 OH, OW = 64, 128
@@ -168,10 +170,7 @@ def staged(tmp_path_factory, net):
     os.chdir(root)
     try:
         _synthetic_ped2_tree(np.random.default_rng(11))
-        cfg = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'config.cfg')).read()
-        cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('batch_size = 128', 'batch_size = 4')
-        cfg = cfg.replace('[UCSDped2]\n', '[UCSDped2]\nh_block = 2\nw_block = 2\ntrain_block_mode = 9\ntest_block_mode = 9\n')
-        open('config.cfg', 'w').write(cfg)
+        cfg = small_config()
         T.main('config.cfg')
         ds = unified_dataset_interface('UCSDped2', os.path.join('raw_datasets', 'UCSDped2'), context_frame_num=1, mode='test',
                                        border_mode='hard')

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from _util import small_config
+
 pytestmark = pytest.mark.gpu
 
 HB = WB = 2
@@ -37,10 +39,7 @@ def _tree():
     boxes[1] = np.concatenate([np.asarray(boxes[1]).reshape(-1, 5), np.array([TWO_BLOCK_BOX])])
     boxes[2] = np.zeros((0, 5))
     np.save(path, boxes, allow_pickle=True)
-    cfg = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'config.cfg')).read()
-    cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('batch_size = 128', 'batch_size = 4')
-    cfg = cfg.replace('[UCSDped2]\n', '[UCSDped2]\nh_block = 2\nw_block = 2\ntrain_block_mode = 9\ntest_block_mode = 9\n')
-    open('config.cfg', 'w').write(cfg)
+    cfg = small_config()
     return cfg
 
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import load_golden
+from _util import load_golden, small_config
 
 pytestmark = pytest.mark.gpu
 
@@ -258,10 +258,7 @@ def test_extraction_stage_and_full_scripts(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
     rng = np.random.default_rng(11)
     frames, flows, boxes = _synthetic_ped2_tree(rng)
-    cfg = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'config.cfg')).read()
-    cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('batch_size = 128', 'batch_size = 4')
-    cfg = cfg.replace('[UCSDped2]\n', '[UCSDped2]\nh_block = 2\nw_block = 2\ntrain_block_mode = 9\n')      # dataset-level overrides
-    open('config.cfg', 'w').write(cfg)
+    small_config(test_block_mode=False)
     c = T.read_config('config.cfg')
     assert c['h_block'] == 2 and c['cp'].getint('UCSDped2', 'train_block_mode') == 9 and c['batch_size'] == 4
 

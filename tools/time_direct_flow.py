@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time the test stage with the optical flow staged through ``optical_flow/`` files against ``[mi355x] direct_flow = True``, on the
-synthetic UCSDped2-shaped tree of ``tools/time_direct_test.py`` (240x360 grey .tif frames, one test video).  FlowNet2 carries seeded
+synthetic UCSDped2-shaped tree of ``tools/synthetic_tree.py`` (240x360 grey .tif frames, one test video).  FlowNet2 carries seeded
 random weights (``torch.manual_seed(0)``): its run time does not depend on them.  One child process per leg, on the same machine:
 
   A  ``calc_optical_flow`` on the test split, ``pairs_per_launch=4`` (writes ``optical_flow/UCSDped2/Test...``), then ``test.main``
@@ -26,13 +26,11 @@ import time
 
 import numpy as np
 
+from synthetic_tree import make_tree, metered, tree_bytes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TEST_FLOW = os.path.join('optical_flow', 'UCSDped2', 'Test')
 PAIRS = 4
-
-
-def tree_bytes(path):
-    return sum(os.path.getsize(os.path.join(d, f)) for d, _, files in os.walk(path) for f in files) if os.path.isdir(path) else 0
 
 
 def step_times(net, reps):
@@ -71,16 +69,7 @@ def leg(direct, reps):
     import vad_datasets as V
     import test as S
     meter = {'decode': 0.0}
-    real = V.get_inputs
-
-    def get_inputs(addr):
-        t0 = time.perf_counter()
-        try:
-            return real(addr)
-        finally:
-            meter['decode'] += time.perf_counter() - t0
-
-    V.get_inputs = FG.get_inputs = get_inputs
+    V.get_inputs = FG.get_inputs = metered(meter, V.get_inputs, 'decode')
     torch.manual_seed(0)
     net = COF.FlowNet2().cuda().eval()
     torch.cuda.synchronize()
@@ -117,8 +106,6 @@ def main():
     if a.leg:
         return leg(a.leg == 'direct', a.reps)
     sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from time_direct_test import make_tree
     own = a.work is None
     work = tempfile.mkdtemp(prefix='direct_flow_tree_') if own else os.path.abspath(a.work)
     if not own:
@@ -126,7 +113,7 @@ def main():
     out_path = os.path.abspath(a.out) if a.out else None
     os.chdir(work)
     try:
-        make_tree(a.frames, a.boxes)
+        make_tree({'train': (6, 6), 'test': (a.frames,)}, a.boxes)
         cfg = open(os.path.join(ROOT, 'config.cfg')).read()
         cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('save_score_masks = True', 'save_score_masks = False')
         open('config.cfg', 'w').write(cfg)

@@ -22,43 +22,9 @@ import time
 
 import numpy as np
 
+from synthetic_tree import make_tree, metered
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def make_tree(n_test, boxes_per_frame, seed=11):
-    """raw_datasets/ + optical_flow/ + bbox files like UCSDped2: two short training videos and one test video of n_test frames."""
-    from PIL import Image
-    rng = np.random.default_rng(seed)
-    H, W = 240, 360
-    for mode, sub, counts in (('train', 'Train', (6, 6)), ('test', 'Test', (n_test,))):
-        all_boxes = []
-        for v, n in enumerate(counts, start=1):
-            name = '%s%03d' % (sub, v)
-            os.makedirs(os.path.join('raw_datasets', 'UCSDped2', sub, name))
-            os.makedirs(os.path.join('optical_flow', 'UCSDped2', sub, name))
-            if mode == 'test':
-                os.makedirs(os.path.join('raw_datasets', 'UCSDped2', sub, name + '_gt'))
-            for k in range(n):
-                g = rng.integers(0, 256, (H, W), dtype=np.uint8)
-                fl = (rng.standard_normal((H, W, 2)) * 2).astype(np.float32)
-                fl[:60, :90] = 0                                   # a still corner: boxes there fail the motion test
-                Image.fromarray(g).save(os.path.join('raw_datasets', 'UCSDped2', sub, name, '%04d.tif' % (k + 1)))
-                np.save(os.path.join('optical_flow', 'UCSDped2', sub, name, '%04d.npy' % (k + 1)), fl)
-                if mode == 'test':
-                    gt = np.zeros((H, W), np.uint8)
-                    if k % 2:
-                        gt[100:120, 100:130] = 255
-                    Image.fromarray(gt).save(os.path.join('raw_datasets', 'UCSDped2', sub, name + '_gt', '%04d.bmp' % (k + 1)))
-                bb = []
-                for m in range(boxes_per_frame):
-                    x0, y0 = rng.uniform(95, W - 70), rng.uniform(65, H - 70)
-                    bb.append([x0, y0, x0 + rng.uniform(8, 64), y0 + rng.uniform(8, 64), rng.random()])
-                bb[0] = [5.0, 4.0, 40.0, 50.0, 0.9]                # inside the still corner -> dropped
-                all_boxes.append(np.array(bb).reshape(-1, 5))
-        arr = np.empty(len(all_boxes), dtype=object)
-        for i, b in enumerate(all_boxes):
-            arr[i] = b
-        np.save(os.path.join('raw_datasets', 'UCSDped2', 'bboxes_%s_obj_det_with_motion.npy' % mode), arr, allow_pickle=True)
 
 
 def leg(direct):
@@ -69,19 +35,8 @@ def leg(direct):
     import vad_datasets as V
     import test as S
     meter = {'decode': 0.0, 'extract': 0.0, 'cube_load': 0.0}
-
-    def metered(fn, key):
-        def run(*a, **k):
-            t0 = time.perf_counter()
-            try:
-                return fn(*a, **k)
-            finally:
-                meter[key] += time.perf_counter() - t0
-        return run
-
-    decode = metered(V.get_inputs, 'decode')
-    V.get_inputs = FG.get_inputs = decode
-    FG.extract_test = metered(FG.extract_test, 'extract')
+    V.get_inputs = FG.get_inputs = metered(meter, V.get_inputs, 'decode')
+    FG.extract_test = metered(meter, FG.extract_test, 'extract')
     real_device = FG.extract_device
 
     def extract_device(*a, **k):
@@ -103,7 +58,7 @@ def leg(direct):
         return info, timed_parts()
 
     FG.extract_device = extract_device
-    np_load, timed_load = np.load, metered(np.load, 'cube_load')
+    np_load, timed_load = np.load, metered(meter, np.load, 'cube_load')
     np.load = lambda f, *a, **k: (timed_load if 'foreground_' in os.path.basename(str(f)) else np_load)(f, *a, **k)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -134,7 +89,7 @@ def main():
     out_path = os.path.abspath(a.out) if a.out else None
     os.chdir(work)
     try:
-        make_tree(a.frames, a.boxes)
+        make_tree({'train': (6, 6), 'test': (a.frames,)}, a.boxes)
         cfg = open(os.path.join(ROOT, 'config.cfg')).read()
         cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('save_score_masks = True', 'save_score_masks = False')
         open('config.cfg', 'w').write(cfg)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time the training stage with flow and cubes staged through files against ``[mi355x] direct_train = True`` + ``direct_flow = True``, on
-a synthetic UCSDped2-shaped training split built like the tree of ``tools/time_direct_test.py`` (240x360 grey .tif frames, random boxes
+a synthetic UCSDped2-shaped training split built like the tree of ``tools/synthetic_tree.py`` (240x360 grey .tif frames, random boxes
 of which the first of every frame lies in a corner; here two training videos of ``--frames / 2`` frames each, no test split).  FlowNet2 carries seeded random weights
 (``torch.manual_seed(0)``): its run time does not depend on them.  One child process per leg, each under its own time limit, A first,
 on the same machine; the tool ends at the first child that does not exit normally:
@@ -33,39 +33,12 @@ import time
 
 import numpy as np
 
+from synthetic_tree import make_tree, metered, tree_bytes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN_FLOW = os.path.join('optical_flow', 'UCSDped2', 'Train')
 CUBE_GLOB = os.path.join('data', 'raw2flow', '*foreground_train_*')
 PAIRS = 4
-
-
-def tree_bytes(path):
-    return sum(os.path.getsize(os.path.join(d, f)) for d, _, files in os.walk(path) for f in files) if os.path.isdir(path) else 0
-
-
-def make_train_tree(n_train, boxes_per_frame, seed=11):
-    """raw_datasets/UCSDped2/Train... + the training bbox file, in the form of ``time_direct_test.make_tree``: one video per entry of
-    ``n_train``.  No flow file: leg A writes FlowNet2's, leg B must not need any."""
-    from PIL import Image
-    rng = np.random.default_rng(seed)
-    H, W = 240, 360
-    all_boxes = []
-    for v, n in enumerate(n_train, start=1):
-        name = 'Train%03d' % v
-        os.makedirs(os.path.join('raw_datasets', 'UCSDped2', 'Train', name))
-        for k in range(n):
-            g = rng.integers(0, 256, (H, W), dtype=np.uint8)
-            Image.fromarray(g).save(os.path.join('raw_datasets', 'UCSDped2', 'Train', name, '%04d.tif' % (k + 1)))
-            bb = []
-            for m in range(boxes_per_frame):
-                x0, y0 = rng.uniform(95, W - 70), rng.uniform(65, H - 70)
-                bb.append([x0, y0, x0 + rng.uniform(8, 64), y0 + rng.uniform(8, 64), rng.random()])
-            bb[0] = [5.0, 4.0, 40.0, 50.0, 0.9]
-            all_boxes.append(np.array(bb).reshape(-1, 5))
-    arr = np.empty(len(all_boxes), dtype=object)
-    for i, b in enumerate(all_boxes):
-        arr[i] = b
-    np.save(os.path.join('raw_datasets', 'UCSDped2', 'bboxes_train_obj_det_with_motion.npy'), arr, allow_pickle=True)
 
 
 def leg(direct):
@@ -76,21 +49,9 @@ def leg(direct):
     import vad_datasets as V
     import train as T
     meter = {'decode': 0.0, 'extract': 0.0}
-
-    def metered(fn, key, sync=False):
-        def run(*a, **k):
-            t0 = time.perf_counter()
-            try:
-                return fn(*a, **k)
-            finally:
-                if sync:
-                    torch.cuda.synchronize()
-                meter[key] += time.perf_counter() - t0
-        return run
-
-    V.get_inputs = FG.get_inputs = metered(V.get_inputs, 'decode')
-    FG.extract_train = metered(FG.extract_train, 'extract', sync=True)
-    FG.extract_train_device = metered(FG.extract_train_device, 'extract', sync=True)
+    V.get_inputs = FG.get_inputs = metered(meter, V.get_inputs, 'decode')
+    FG.extract_train = metered(meter, FG.extract_train, 'extract', sync=torch.cuda.synchronize)
+    FG.extract_train_device = metered(meter, FG.extract_train_device, 'extract', sync=torch.cuda.synchronize)
     torch.manual_seed(0)
     net = COF.FlowNet2().cuda().eval()
     torch.cuda.synchronize()
@@ -141,7 +102,7 @@ def main():
     out_path = os.path.abspath(a.out) if a.out else None
     os.chdir(work)
     try:
-        make_train_tree((a.frames - a.frames // 2, a.frames // 2), a.boxes)
+        make_tree({'train': (a.frames - a.frames // 2, a.frames // 2)}, a.boxes, flow=False)      # leg A writes FlowNet2's flow, leg B needs none
         cfg = open(os.path.join(ROOT, 'config.cfg')).read().replace('epochs = 10', 'epochs = 1')
         env = dict(os.environ, PYTHONPATH=ROOT)
         from vec_vad_amd import build as B

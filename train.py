@@ -321,14 +321,52 @@ def _gather_var(dist, t, n, world, present=True):
     return torch.cat(parts)
 
 
+def _training_blocks(c, base, store=None):
+    """The one place that tells the three routes apart: ``(scenes, rows, blocks)``.  The saved files nest ``[h][w]``, ``rows[h]`` blocks
+    in grid row ``h``, below ``scenes`` scenes for ShanghaiTech (else None).  ``blocks`` yields ``((s, h, w), segments)`` in training order,
+    ``segments`` as ``train_block`` takes them: the block's index list into ``store`` (``extract_train_device``), ShanghaiTech's segment
+    files (train.py:292-299), or the block's arrays of the ``foreground_train_*`` files.  A block with <= 1 cube is left out
+    (train.py:370 "num > 1 for data parallel"); a ShanghaiTech block never is."""
+    ds, fg, hb, wb = c['dataset_name'], c['mode_fg'], c['h_block'], c['w_block']
+    if store is not None:
+        def blocks():
+            for h, w in ((h, w) for h in range(hb) for w in range(wb)):
+                block_idx = store['groups'][(None, h, w)][0] if (None, h, w) in store['groups'] else np.zeros(0, np.int64)
+                if len(block_idx) > 1:
+                    yield (None, h, w), [(store['raw'], store['flow'], block_idx)]
+        return None, [wb] * hb, blocks()
+    if ds == 'ShanghaiTech':
+        tot_seg = len([f for f in os.listdir(os.path.dirname(base))
+                       if f.startswith('%s_foreground_train_%s_seg_' % (ds, fg)) and f.endswith('-raw.npy')])
+        probe = np.load(base + 'foreground_train_{}_seg_0-raw.npy'.format(fg), allow_pickle=True)
+        grid = [(s, h, w) for s in range(len(probe)) for h in range(len(probe[s])) for w in range(len(probe[s][h]))]
+        del probe
+
+        def seg_loader(k, s, h, w):
+            a = np.load(base + 'foreground_train_{}_seg_{}-raw.npy'.format(fg, k), allow_pickle=True)
+            b = np.load(base + 'foreground_train_{}_seg_{}-flow.npy'.format(fg, k), allow_pickle=True)
+            return np.asarray(a[s][h][w]), np.asarray(b[s][h][w])
+        return max(g[0] for g in grid) + 1, [wb] * hb, (
+            (g, [lambda k=k, g=g: seg_loader(k, *g) for k in range(tot_seg)]) for g in grid)
+    fset = np.load(base + 'foreground_train_{}-raw.npy'.format(fg), allow_pickle=True)
+    fset2 = np.load(base + 'foreground_train_{}-flow.npy'.format(fg), allow_pickle=True)
+
+    def blocks():
+        for h, w in ((h, w) for h in range(len(fset)) for w in range(len(fset[h]))):
+            data = np.asarray(fset[h][w])
+            if len(data) > 1:
+                data2 = np.asarray(fset2[h][w])
+                yield (None, h, w), [lambda data=data, data2=data2: (data, data2)]
+    return None, [len(row) for row in fset], blocks()
+
+
 def main(config_path='config.cfg', flownet2=None):
     """``flownet2``: the network ``[mi355x] direct_flow`` computes the training split's flow with (only with ``direct_train``);
     None loads ``[mi355x] flownet2_checkpoint``."""
     c = read_config(config_path)
     cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
-    shanghai = ds == 'ShanghaiTech'
     direct = c['direct_train']
-    if direct and shanghai:                                     # before any GPU work
+    if direct and ds == 'ShanghaiTech':                         # before any GPU work
         raise NotImplementedError(DIRECT_TRAIN_SHANGHAI)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
@@ -337,60 +375,26 @@ def main(config_path='config.cfg', flownet2=None):
         _extract_once(c, device, dist)
     net = build_network(c)
     base = os.path.join(root, mod, ds + '_')
-    hb, wb = c['h_block'], c['w_block']
-
+    store = None
     if direct:          # every rank cuts the whole split into its own store: nothing to wait for, nothing on a shared disk
         # (after build_network: loading FlowNet2 must not move the random state the initial weights are drawn from)
         from foreground import extract_train_device
         store = extract_train_device(c, device, log=print if rank == 0 else (lambda *a: None), flownet2=flownet2)
-        grid = [(None, h, w) for h in range(hb) for w in range(wb)]
-    elif shanghai:
-        save_seg = cp.getint(ds, 'saveSegNum')
-        names = sorted(f for f in os.listdir(os.path.join(root, mod))
-                       if f.startswith('%s_foreground_train_%s_seg_' % (ds, fg)) and f.endswith('-raw.npy'))
-        tot_seg = len(names)
-        probe = np.load(base + 'foreground_train_{}_seg_0-raw.npy'.format(fg), allow_pickle=True)
-        grid = [(s, h, w) for s in range(len(probe)) for h in range(len(probe[s])) for w in range(len(probe[s][h]))]
-        del probe
-    else:
-        fset = np.load(base + 'foreground_train_{}-raw.npy'.format(fg), allow_pickle=True)
-        fset2 = np.load(base + 'foreground_train_{}-flow.npy'.format(fg), allow_pickle=True)
-        grid = [(None, h, w) for h in range(len(fset)) for w in range(len(fset[h]))]
+    scenes, rows, blocks = _training_blocks(c, base, store)
 
-    def nested(fill):
-        if shanghai:
-            ns = max(g[0] for g in grid) + 1
-            return [[[fill() for _ in range(c['w_block'])] for _ in range(c['h_block'])] for _ in range(ns)]
-        if direct:
-            return [[fill() for _ in range(wb)] for _ in range(hb)]
-        return [[fill() for _ in range(len(fset[h]))] for h in range(len(fset))]
+    def nested():
+        def grid():
+            return [[[] for _ in range(n)] for n in rows]
+        return grid() if scenes is None else [grid() for _ in range(scenes)]
 
-    model_set, raw_scores_set, of_scores_set = nested(list), nested(list), nested(list)
-    for (s, h, w) in grid:
-        if shanghai:
-            def seg_loader(k, s=s, h=h, w=w):
-                a = np.load(base + 'foreground_train_{}_seg_{}-raw.npy'.format(fg, k), allow_pickle=True)
-                b = np.load(base + 'foreground_train_{}_seg_{}-flow.npy'.format(fg, k), allow_pickle=True)
-                return np.asarray(a[s][h][w]), np.asarray(b[s][h][w])
-            segments = [lambda k=k: seg_loader(k) for k in range(tot_seg)]
-        elif direct:
-            block_idx = store['groups'][(None, h, w)][0] if (None, h, w) in store['groups'] else np.zeros(0, np.int64)
-            if len(block_idx) <= 1:     # as below
-                continue
-            segments = [(store['raw'], store['flow'], block_idx)]
-        else:
-            data = np.asarray(fset[h][w])
-            if len(data) <= 1:          # train.py:370 "num > 1 for data parallel"
-                continue
-            data2 = np.asarray(fset2[h][w])
-            segments = [lambda data=data, data2=data2: (data, data2)]
+    model_set, raw_scores_set, of_scores_set = nested(), nested(), nested()
+    for (s, h, w), segments in blocks:
         sd, r, o = train_block(net, segments, c['epochs'], c['batch_size'], c['lambda_raw'], c['lambda_of'],
                                c['shuffle_seed'], device, tag='({}, {})'.format(h, w), dist=dist, overlap=c['overlap_wgrad'])
-        tgt = (model_set[s][h][w], raw_scores_set[s][h], of_scores_set[s][h]) if shanghai else \
-              (model_set[h][w], raw_scores_set[h], of_scores_set[h])
-        tgt[0].append({k: v.cpu() for k, v in sd.items()})
-        tgt[1][w] = r
-        tgt[2][w] = o
+        models, raw_sc, of_sc = ((t if s is None else t[s])[h] for t in (model_set, raw_scores_set, of_scores_set))
+        models[w].append({k: v.cpu() for k, v in sd.items()})
+        raw_sc[w] = r
+        of_sc[w] = o
     if rank == 0:
         torch.save(raw_scores_set, base + 'raw_training_scores_{}_{}.npy'.format(fg, method))
         torch.save(of_scores_set, base + 'of_training_scores_{}_{}.npy'.format(fg, method))
