@@ -167,6 +167,40 @@ def _write_frame_index(st, ds, mode):
     return scene_idx, labels
 
 
+PIXEL_GT_SHANGHAI = ('[mi355x] pixel_criterion = True does not cover ShanghaiTech (this build reads only its frame-level '
+                     'test_frame_mask): set it to False')
+
+
+def gt_source(c):
+    """The per-pixel ground truth of the test split for ``[mi355x] pixel_criterion``: the dataset the reference's evaluation step
+    builds (test.py:366-368: no context, 'hard' border) over ``<raw_dataset_dir>/<ds>``.  Returns ``gt`` with ``len(gt)`` = the
+    number of test frames and ``gt(i)`` = the mask of frame ``i`` as a contiguous uint8 ``[h,w]`` array (non-zero = anomalous
+    pixel).  Raises a one-line ``ValueError`` for ShanghaiTech (before anything is read), for a tree without per-pixel ground truth
+    and for a mask that is not ``frame_size[ds][:2]``."""
+    ds = c['dataset_name']
+    if ds == 'ShanghaiTech':
+        raise ValueError(PIXEL_GT_SHANGHAI)
+    root = os.path.join(c['raw_dataset_dir'], ds)
+    dataset = unified_dataset_interface(dataset_name=ds, dir=root, context_frame_num=0, mode='test', border_mode='hard')
+    h, w = frame_size[ds][0], frame_size[ds][1]
+    n_gt = len(dataset.all_gt_addr) if hasattr(dataset, 'all_gt_addr') else (dataset.all_gt.shape[1] if dataset.return_gt else 0)
+    if not dataset.return_gt or n_gt != len(dataset):
+        raise ValueError('[mi355x] pixel_criterion = True: {} holds per-pixel ground truth for {} of its {} test frames'.format(
+            root, n_gt if dataset.return_gt else 0, len(dataset)))
+
+    class Source:
+        def __len__(self):
+            return len(dataset)
+
+        def __call__(self, i):
+            g = np.asarray(dataset._gt(i))
+            if g.shape != (h, w):
+                raise ValueError('ground truth of test frame {} is {}, {} frames are {}x{}'.format(i, g.shape, ds, h, w))
+            return np.ascontiguousarray(g != 0 if g.dtype != np.uint8 else g, dtype=np.uint8)
+
+    return Source()
+
+
 def frame_cubes(raw_ds, flow_ds, idx, motion_thr, device='cuda'):
     """Cubes of frame ``idx`` that pass the motion test: (raw ``[m,(T,)P,P,3]`` uint8, flow ``[m,(Tf,)P,P,2]`` float32,
     kept box indices).  Flow energy per box = sum of squares over the patch (mean over the context frames when there is a

@@ -587,6 +587,33 @@ int vv_frame_scores(const float* raw, const float* of, const int32_t* frame_off,
                     double* frame_scores, vv_stream stream);
 int vv_roc_auc_counts(const double* scores, const uint8_t* labels, int32_t n, uint64_t* out3, vv_stream stream);
 
+/* ---- pixel-level evaluation (the criterion the reference's score_mask files exist for and test.py:362-365 never evaluates) ----
+ * NaN cube scores (a zero training std with an error equal to the mean) are outside the domain of all of these, as they are for
+ * vv_frame_scores: fmax drops them where numpy's maximum propagates them.
+ * vv_cube_scores: out[m] = the z-normalised, weighted score of cube m exactly as vv_frame_scores forms it (one shared device
+ *   function): cube_stat[m] < 0 ? big : w_raw*((double)raw[m]-mu_r)/sd_r [+ w_of*((double)of[m]-mu_o)/sd_o], products and sums
+ *   rounded separately; of == NULL drops the flow term.  double [n].
+ * vv_paint_masks: out[f][y][x] = max(out[f][y][x], scores[m]) for every cube m in [frame_off[f], frame_off[f+1]) whose rectangle
+ *   rects[m] = (y0, y1, x0, x1) holds y0 <= y < y1 and x0 <= x < x1.  rects int32 [n][4], 16-byte aligned, already resolved by
+ *   the host (ceil, Python slice wrapping and clipping: vec_vad_amd/scoring.py box_rects); the kernel rounds and wraps nothing.
+ *   out double [n_frames][h][w], 16-byte aligned, initialised by the caller (to -big, the mask background); a frame whose cubes
+ *   come from several block groups is painted by one call per group.  No atomics: a thread owns two consecutive pixels of the
+ *   flat h*w frame and walks the frame's boxes; a frame without boxes is not touched.  h * w < 2^31 - 512.
+ * vv_pixel_scores: per frame f, with G = the pixels where gt != 0 (gt uint8 [n_frames][h][w]) and P the mask vv_paint_masks
+ *   would paint over a background of -big (it is never formed): gt_count[f] = |G|; out[f] = the k-th largest value of P over G,
+ *   k = (|G| * pct + 99) / 100 in integers, when |G| > 0, else the maximum of P (= the frame score).  1 <= pct <= 100.  ALL
+ *   cubes of a frame must be in the one call (a quantile is not max-decomposable).  One workgroup per frame, integer LDS
+ *   histogram: bit-identical run to run.  max_boxes = the largest frame_off[f+1] - frame_off[f], which the caller knows from its
+ *   host copy of the table (the entry point cannot read device memory); above 2048 (the LDS table) the call returns
+ *   VV_ERR_UNSUPPORTED and launches nothing.  Against a table that breaks max_boxes the kernel only protects memory. */
+int vv_cube_scores(const float* raw, const float* of, const int32_t* cube_stat, const double* stats, double w_raw, double w_of,
+                   double big, int32_t n, double* out, vv_stream stream);
+int vv_paint_masks(const double* scores, const int32_t* frame_off, const int32_t* rects, int32_t n_frames, int32_t h, int32_t w,
+                   double* out, vv_stream stream);
+int vv_pixel_scores(const uint8_t* gt, const double* scores, const int32_t* frame_off, const int32_t* rects, int32_t pct,
+                    double big, int32_t n_frames, int32_t h, int32_t w, int32_t max_boxes, double* out, int32_t* gt_count,
+                    vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

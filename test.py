@@ -22,6 +22,12 @@ scores, score masks and the evaluation are those of the staged path.
 ``[mi355x] direct_flow = True`` (default False; needs ``direct_test``) also computes the optical flow of every chunk on the GPU
 (``calc_optical_flow.chunk_flows``: FlowNet2 from a captured graph between two HIP resize kernels), so the test stage reads nothing
 under ``optical_flow/``.  ``main(config_path, flownet2=None)`` takes the network to use; None loads ``[mi355x] flownet2_checkpoint``.
+
+``[mi355x] pixel_criterion = True`` (default False; UCSDped2 / avenue) adds the pixel-level criterion the masks are stored for and
+the reference never evaluates (test.py:362-365 ``criterion = 'frame'``): per frame one number (``scoring.pixel_scores``), computed
+on the GPU from the device-resident cube scores and the per-pixel ground truth, ``results/<ds>/pixel_scores_<fg>_<method>.npy``
+and ``<modality>_<fg>_<method>_pixel_results.npz``.  ``[mi355x] device_score_masks = True`` paints the ``score_mask`` files on the
+GPU (``scoring.paint_masks``) instead of the numpy loop over boxes; the same files.
 """
 import os
 import sys
@@ -189,11 +195,55 @@ def _save_masks(result_dir, frames, mask_groups, h, w):
         torch.save(fmap, os.path.join(result_dir, '{}'.format(f)))
 
 
-def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups):
+class PixelEval:
+    """What ``score_frames`` / ``score_store`` need for the pixel-level stage (their ``pixel`` keyword).  ``gt``: the ground-truth
+    source (``foreground.gt_source``: ``gt(i)`` -> uint8 ``[h,w]``) or None for no pixel criterion; ``percent``: the overlap in
+    integer percent; ``out``: CUDA float64 ``[n_frames]`` that receives the pixel scores of the frames a call covers; ``labels``:
+    the frame labels (bool ``[n_frames]``) the ground-truth pixel counts are checked against, or None; ``device_masks``: paint the
+    ``result_dir`` masks on the GPU; ``frames_per_chunk``: frames per ground-truth upload / mask download."""
+
+    def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64):
+        self.gt, self.percent, self.out, self.labels = gt, int(percent), out, labels
+        self.device_masks, self.frames_per_chunk = bool(device_masks), max(1, int(frames_per_chunk))
+        if gt is not None and out is None:
+            raise ValueError('PixelEval: a ground-truth source needs an `out` vector for the pixel scores')
+
+
+def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device):
+    """Frames ``[first, end)`` of the scored groups ``dev_groups`` ((off, device cube scores, device rectangles) each) in chunks:
+    the chunk's cubes are merged into frame order and reduced to pixel scores against the chunk's ground truth (uploaded once),
+    and / or its masks are painted on the device, group by group, brought to the host once and saved per frame."""
+    paint = pixel.device_masks and result_dir
+    if paint:
+        os.makedirs(result_dir, exist_ok=True)
+    for a in range(first, end, pixel.frames_per_chunk):
+        b = min(a + pixel.frames_per_chunk, end)
+        sub = [(off[a:b + 1], sc, rc) for off, sc, rc in dev_groups]
+        if pixel.gt is not None:
+            off, sc, rc = scoring.merge_groups(sub, n_frames=b - a, device=device)
+            gt = torch.from_numpy(np.stack([pixel.gt(i) for i in range(a, b)])).to(device)
+            _, cnt = scoring.pixel_scores(gt, sc, off, rc, pixel.percent, out=pixel.out[a:b])
+            if pixel.labels is not None:
+                bad = np.nonzero((cnt.cpu().numpy() > 0) != np.asarray(pixel.labels[a:b], bool))[0]
+                if len(bad):
+                    raise ValueError('frame {}: its label and its per-pixel ground truth disagree on whether it is anomalous'.format(
+                        a + int(bad[0])))
+        if paint:
+            masks = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
+            for off, sc, rc in sub:
+                if off[-1] > off[0]:
+                    scoring.paint_masks(sc, off, rc, h, w, out=masks)
+            masks = masks.cpu().numpy()
+            for f in range(a, b):
+                torch.save(masks[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))      # its own array, as _save_masks saves
+
+
+def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups, dev_groups=None):
     """The per-group body of ``score_frames`` and ``score_store``.  The returned ``group(key, hh, ww, n, off, boxes, score)`` scores
     the ``n`` cubes of block ``(hh, ww)`` (of scene ``key``, or None) with ``score(trainer)`` -> device (raw [n], of [n] | None),
     max-accumulates their frame scores into ``fs_dev`` (``off``: CSR over the frames, ``boxes`` float64 ``[n,4]``) and, when
-    ``mask_groups`` is a list, appends the group's (off, host cube scores, boxes) for ``_save_masks``."""
+    ``mask_groups`` is a list, appends the group's (off, host cube scores, boxes) for ``_save_masks``; when ``dev_groups`` is a list,
+    the group's (off, device cube scores, device rectangles) for ``_pixel_stage``."""
     def group(key, hh, ww, n, off, boxes, score):
         def pick(nested):
             return nested[key][hh][ww] if key is not None else nested[hh][ww]
@@ -215,22 +265,36 @@ def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, devi
         scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(boxes, h, w), w_raw, w_of, out=fs_dev)
         if mask_groups is not None:
             mask_groups.append((off, _mask_scores(r, o, stats, w_raw, w_of, len(models) > 0), boxes))
+        if dev_groups is not None:
+            dev_groups.append((off, scoring.cube_scores(r, o, cube_stat, stats, w_raw, w_of),
+                               torch.from_numpy(scoring.box_rects(boxes, h, w)).to(device)))
     return group
 
 
+def _mask_lists(result_dir, pixel):
+    """(mask_groups, dev_groups) for a call: the host list feeds ``_save_masks``, the device list ``_pixel_stage``."""
+    device_masks = pixel is not None and pixel.device_masks
+    return ([] if result_dir and not device_masks else None,
+            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir)) else None)
+
+
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
-                 device, score_batch=2048, scene_idx=None, result_dir=None, log=print, return_device=False):
+                 device, score_batch=2048, scene_idx=None, result_dir=None, log=print, return_device=False, pixel=None):
     """Per-frame anomaly scores.  ``net_set[(s,)hh][ww]`` is a list with 0 or 1 eval-mode networks;
     ``stats_*[(s,)hh][ww]`` = (mean, std) of the training scores.
 
     The per-cube errors stay in HBM: ``vv_frame_scores`` z-normalises, weights and max-reduces them per frame
     (= the maximum of the reference's painted h x w mask, test.py:350-357,391).  Only when ``result_dir`` is given are the
-    masks themselves painted (on the host) and saved as ``<result_dir>/<frame>`` like the reference does."""
+    masks themselves painted (on the host) and saved as ``<result_dir>/<frame>`` like the reference does.
+
+    ``pixel`` (a ``PixelEval``, default None: nothing below happens): the per-cube scores and rectangles of every group also stay on
+    the device; with a ground-truth source the pixel scores of all frames go to ``pixel.out``, and with ``pixel.device_masks`` the
+    ``result_dir`` masks are painted on the GPU (same files) and no per-cube score visits the host."""
     n_frames = len(foreground_set)
-    mask_groups = [] if result_dir else None      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
+    mask_groups, dev_groups = _mask_lists(result_dir, pixel)      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
     fs_dev = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
     hb, wb = len(foreground_set[0]), len(foreground_set[0][0])
-    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups)
+    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups, dev_groups)
     keys = sorted(set(scene_idx[f] - 1 for f in range(n_frames))) if scene_idx is not None else [None]
     for hh in range(hb):
         for ww in range(wb):
@@ -246,8 +310,10 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
                 off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)      # indexed by frame: cubes of frame f = [off[f], off[f+1])
                 group(key, hh, ww, int(off[-1]), off, boxes, lambda tr: score_cubes_device(
                     tr, [foreground_set[f][hh][ww] for f in frames], [foreground_set2[f][hh][ww] for f in frames], score_batch))
-    if result_dir:
+    if mask_groups is not None:
         _save_masks(result_dir, range(n_frames), mask_groups, h, w)
+    if dev_groups is not None:
+        _pixel_stage(pixel, dev_groups, 0, n_frames, h, w, result_dir, device)
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -276,7 +342,7 @@ def score_index_list(trainer, raw_store, flow_store, idx, score_batch, batch=Non
 
 
 def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw, w_of, useFlow, device, score_batch=2048,
-                scene_idx=None, result_dir=None, out=None, frame_range=None, trainers=None, return_device=False):
+                scene_idx=None, result_dir=None, out=None, frame_range=None, trainers=None, return_device=False, pixel=None):
     """``score_frames`` for a device-resident cube store (``foreground.extract_device``).  ``store`` = (raw uint8 ``[N,5,32,32,3]``,
     flow float32 ``[N,Tf,32,32,2]``) CUDA tensors in ``CubeStore`` layout; ``groups`` = ``{(scene, hh, ww): (idx, off)}`` as built by
     ``foreground.block_groups`` (scene = ``scene_idx[f] - 1`` when ``scene_idx`` is given, else None; ``off`` CSR over all frames);
@@ -286,7 +352,8 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     on its staging buffers), so the statistics, ``cube_stat``, paints and launch shapes -- hence the frame scores and the masks under
     ``result_dir`` -- are the staged path's by construction.  ``out`` (CUDA float64 ``[n_frames]``, initialised to ``-BIG``) is max-accumulated into: a test set that comes
     in several parts (``[mi355x] direct_max_cubes``) is scored part by part, with ``frame_range`` = the ``(first, end)`` frames whose
-    masks this call writes (default: all) and ``trainers`` = a dict that keeps the engines between calls."""
+    masks this call writes (default: all) and ``trainers`` = a dict that keeps the engines between calls.  ``pixel``: as for
+    ``score_frames``, for the frames of ``frame_range`` -- a part never splits a frame, so each call fills its own range of ``pixel.out``."""
     raw_store, flow_store = store
     boxes = np.asarray(boxes, dtype=np.float64).reshape(len(boxes), -1)[:, :4]
     if out is not None:
@@ -298,25 +365,29 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     else:
         raise ValueError('score_store: no group, no out and no frame_range to tell the number of frames')
     fs_dev = out if out is not None else torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
-    mask_groups = [] if result_dir else None
+    mask_groups, dev_groups = _mask_lists(result_dir, pixel)
     group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {} if trainers is None else trainers,
-                          fs_dev, mask_groups)
+                          fs_dev, mask_groups, dev_groups)
     for gk in sorted(groups, key=lambda k: (k[1], k[2], -1 if k[0] is None else k[0])):
         if (gk[0] is None) != (scene_idx is None):
             raise ValueError('group %r does not fit scene_idx %s' % (gk, 'given' if scene_idx is not None else 'absent'))
         idx, off = groups[gk]
         if len(idx):
             group(*gk, len(idx), off, boxes[idx], lambda tr: score_index_list(tr, raw_store, flow_store, idx, score_batch))
-    if result_dir:
-        first, end = frame_range if frame_range is not None else (0, n_frames)
+    first, end = frame_range if frame_range is not None else (0, n_frames)
+    if mask_groups is not None:
         _save_masks(result_dir, range(first, end), mask_groups, h, w)
+    if dev_groups is not None:
+        _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device)
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
-def score_direct(c, device, mask_dir=None, log=print, flownet2=None):
+def score_direct(c, device, mask_dir=None, log=print, flownet2=None, pixel=None):
     """``[mi355x] direct_test``: frames and boxes in, frame scores out.  The parts of ``foreground.extract_device`` are scored as
     they come and max-accumulated into one device vector; the store, the engines and their captured launches serve every part.
-    ``flownet2``: the FlowNet2 that ``[mi355x] direct_flow`` computes the flow with (None: loaded from the configured checkpoint)."""
+    ``flownet2``: the FlowNet2 that ``[mi355x] direct_flow`` computes the flow with (None: loaded from the configured checkpoint).
+    ``pixel``: a function ``(n_frames, labels) -> PixelEval | None`` called once the extraction knows both; every part fills its own
+    frame range of the pixel scores."""
     from foreground import extract_device
     ds, fg, method = c['dataset_name'], c['mode_fg'], c['method']
     base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
@@ -326,10 +397,11 @@ def score_direct(c, device, mask_dir=None, log=print, flownet2=None):
                                          c['w_block'])
     fs_dev = torch.full((info['n_frames'],), -float(BIG), dtype=torch.float64, device=device)
     trainers = {}
+    pixel = pixel(info['n_frames'], info['labels']) if pixel is not None else None
     for part in parts:
         score_store(net_set, st_r, st_o, (part['raw'], part['flow']), part['groups'], part['boxes'], h, w, c['w_raw'], c['w_of'],
                     c['useFlow'], device, c['score_batch'], info['scene_idx'], mask_dir, out=fs_dev, frame_range=part['frames'],
-                    trainers=trainers, return_device=True)
+                    trainers=trainers, return_device=True, pixel=pixel)
     return fs_dev.cpu().numpy()
 
 
@@ -338,6 +410,13 @@ def main(config_path='config.cfg', flownet2=None):
     cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
     if c['direct_flow'] and not c['direct_test']:
         raise ValueError('[mi355x] direct_flow = True needs direct_test = True: only the direct test path computes the flow on the GPU')
+    gt = None
+    if c['pixel_criterion'] and not cp.getboolean(ds, 'scores_saved'):
+        from foreground import gt_source
+        gt = gt_source(c)                 # ShanghaiTech / a tree without per-pixel ground truth: refused before any GPU work
+    elif c['pixel_criterion'] and ds == 'ShanghaiTech':
+        from foreground import PIXEL_GT_SHANGHAI
+        raise ValueError(PIXEL_GT_SHANGHAI)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
     direct = c['direct_test'] and not cp.getboolean(ds, 'scores_saved')       # frames -> scores without cube files
@@ -349,22 +428,43 @@ def main(config_path='config.cfg', flownet2=None):
     results_dir = 'results'
     shanghai = ds == 'ShanghaiTech'
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
+    pixel_scores_path = os.path.join(results_dir, ds, 'pixel_scores_{}_{}.npy'.format(fg, method))
+    ps = None
     if cp.getboolean(ds, 'scores_saved'):
         fs = np.load(frame_scores_path)
+        if c['pixel_criterion']:
+            ps = np.load(pixel_scores_path)
     else:
         mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
+        made = []
+
+        def pixel_eval(n_frames, labels):
+            """The ``pixel`` keyword of the scoring calls, or None with both new keys off (today's calls)."""
+            if gt is None and not (c['device_score_masks'] and mask_dir):
+                return None
+            if gt is not None and len(gt) != n_frames:
+                raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
+            out = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device) if gt is not None else None
+            made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk']))
+            return made[0]
+
         if direct:
-            fs = score_direct(c, device, mask_dir, flownet2=flownet2)
+            fs = score_direct(c, device, mask_dir, flownet2=flownet2, pixel=pixel_eval)
         else:
             fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
             fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
             bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)
             scene_idx = np.load(base + 'scene_idx.npy') if shanghai else None
             net_set, st_r, st_o = load_artifacts(base, fg, method, shanghai, lambda: build_network(c), device, c['h_block'], c['w_block'])
+            lab_file = base + 'frame_labels_test.npy'
             fs = score_frames(net_set, st_r, st_o, fset, fset2, bset, h, w, c['w_raw'], c['w_of'], c['useFlow'], device,
-                              c['score_batch'], scene_idx, mask_dir)
+                              c['score_batch'], scene_idx, mask_dir,
+                              pixel=pixel_eval(len(fset), np.load(lab_file).astype(bool) if os.path.exists(lab_file) else None))
         os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
         np.save(frame_scores_path, fs)
+        if gt is not None:
+            ps = made[0].out.cpu().numpy()
+            np.save(pixel_scores_path, ps)
 
     # ---- evaluation (test.py:362-399), criterion = 'frame'
     lab_path = base + 'frame_labels_test.npy'
@@ -389,6 +489,15 @@ def main(config_path='config.cfg', flownet2=None):
         # the same number from the device-side pair count (vv_roc_auc_counts); the .npz above keeps the reference's layout
         auc_dev = scoring.roc_auc(torch.from_numpy(np.asarray(fs, np.float64)).to(device), labels)
         print('AUC@ROC (device pair count) is {}'.format(auc_dev))
+    if ps is not None:
+        # ---- criterion = 'pixel': the ROC of the pixel scores against the same frame labels (scoring.py module docstring)
+        print('Evaluating {} by pixel-criterion:'.format(ds))
+        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_results.npz'.format(mod, fg, method))
+        print('Results written to {}:'.format(path))
+        pixel_auc = save_roc_pr_curve_data(ps, labels, path)
+        print('Pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], pixel_auc))
+        print('Pixel-level AUC@ROC (device pair count) is {}'.format(
+            scoring.roc_auc(torch.from_numpy(np.asarray(ps, np.float64)).to(device), labels)))
     return auc
 
 

@@ -173,6 +173,9 @@ _SIGS = {
     'vv_frame_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double, C.c_double, C.c_double, c_i32, c_vp,
                                 c_vp]),
     'vv_roc_auc_counts': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'vv_cube_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
+    'vv_paint_masks': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'vv_pixel_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
     'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),

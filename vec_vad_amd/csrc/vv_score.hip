@@ -3,6 +3,8 @@
 // replacing test.py:330-358 (numpy + one 240x360 float64 mask per cube + torch.save/torch.load per frame) and
 // utils.py:29-41 (sklearn roc_curve + auc).  Both kernels are tiny and latency-bound; they exist so that the scores never
 // leave HBM between the UNet bank and the final AUC.
+//   cube scores + boxes -> painted h x w score masks (vv_paint_masks) and the pixel-level criterion (vv_pixel_scores), which
+// the reference stores the masks for (test.py:350-358) and never evaluates (test.py:362-365: criterion = 'frame' only).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -13,6 +15,19 @@
 #pragma clang fp contract(off)
 
 namespace {
+
+// The z-normalised, weighted score of cube m (test.py:338-348), float64 like numpy's (float32 error - float64 mean) / float64
+// std: THE one place the expression lives, so vv_frame_scores, vv_cube_scores and what is painted from them agree to the bit.
+__device__ __forceinline__ double cube_score(const float* __restrict__ raw, const float* __restrict__ of,
+                                             const int32_t* __restrict__ cube_stat, const double* __restrict__ stats,
+                                             double w_raw, double w_of, double big, int m) {
+  const int s = cube_stat[m];
+  if (s < 0) return big;                            // no model for this block: anomaly by construction (test.py:346-348)
+  const double* st = stats + 4 * (int64_t)s;
+  double sc = w_raw * (((double)raw[m] - st[0]) / st[1]);
+  if (of) sc = sc + w_of * (((double)of[m] - st[2]) / st[3]);
+  return sc;
+}
 
 // The reference paints score m into mask[ceil(y1):ceil(y2), ceil(x1):ceil(x2)] (background -1e5), max-combines the masks
 // and later takes mask.max(): that is max over the cubes whose painted rectangle is non-empty, and -1e5 for frames with
@@ -28,18 +43,174 @@ __global__ void __launch_bounds__(256) frame_score_kernel(const float* __restric
   double best = frame_scores[f];
   for (int m = frame_off[f]; m < frame_off[f + 1]; ++m) {
     if (!paints[m]) continue;
-    int s = cube_stat[m];
-    double sc;
-    if (s < 0) {
-      sc = big;                                     // no model for this block: anomaly by construction (test.py:346-348)
-    } else {
-      const double* st = stats + 4 * (int64_t)s;
-      sc = w_raw * (((double)raw[m] - st[0]) / st[1]);
-      if (of) sc = sc + w_of * (((double)of[m] - st[2]) / st[3]);
-    }
-    best = fmax(best, sc);
+    best = fmax(best, cube_score(raw, of, cube_stat, stats, w_raw, w_of, big, m));
   }
   frame_scores[f] = best;
+}
+
+__global__ void __launch_bounds__(256) cube_score_kernel(const float* __restrict__ raw, const float* __restrict__ of,
+                                                         const int32_t* __restrict__ cube_stat,
+                                                         const double* __restrict__ stats, double w_raw, double w_of,
+                                                         double big, int n, double* __restrict__ out) {
+  int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m < n) out[m] = cube_score(raw, of, cube_stat, stats, w_raw, w_of, big, m);
+}
+
+// ---- painted masks: P_f[y,x] = max(out, every score of frame f whose rectangle (y0, y1, x0, x1) holds (y,x)) -----------------
+// Gather form: a thread owns two consecutive pixels of the frame taken as a flat h*w array, walks the frame's boxes (staged in
+// LDS, PAINT_PASS per pass; every lane reads the same box -> broadcast) and writes its pair back with one 16-byte store.  The
+// pairs are aligned on the ADDRESS (a frame of odd h*w starts 8 bytes off every other frame): `mis` shifts the tile by one pixel,
+// and a pair that hangs over either end of the frame falls back to the one 8-byte store that is inside.
+constexpr int PAINT_PASS = 256;              // boxes per LDS pass = threads of the workgroup
+constexpr int PAINT_TILE = 2 * 256;          // pixels per workgroup
+
+__global__ void __launch_bounds__(256) paint_mask_kernel(const double* __restrict__ scores,
+                                                         const int32_t* __restrict__ frame_off,
+                                                         const int4* __restrict__ rects, int f0, int h, int w,
+                                                         double* __restrict__ out) {
+  __shared__ int4 srect[PAINT_PASS];
+  __shared__ double ssc[PAINT_PASS];
+  const int f = f0 + blockIdx.y;
+  const int m0 = frame_off[f], m1 = frame_off[f + 1];
+  if (m1 <= m0) return;                      // a frame without boxes in this group keeps what it holds
+  const int hw = h * w;
+  double* fr = out + (int64_t)f * hw;
+  const int mis = (int)((reinterpret_cast<uintptr_t>(fr) >> 3) & 1);
+  const int p0 = blockIdx.x * PAINT_TILE + 2 * (int)threadIdx.x - mis;
+  const bool in0 = p0 >= 0 && p0 < hw, in1 = p0 + 1 < hw;      // p0 + 1 >= 0 always
+  double v0 = 0.0, v1 = 0.0;
+  if (in0 && in1) {
+    const double2 v = *reinterpret_cast<const double2*>(fr + p0);
+    v0 = v.x; v1 = v.y;
+  } else if (in0) {
+    v0 = fr[p0];
+  } else if (in1) {
+    v1 = fr[p0 + 1];
+  }
+  const int ya = in0 ? p0 / w : 0, xa = in0 ? p0 - ya * w : 0;
+  const int yb = in1 ? (p0 + 1) / w : 0, xb = in1 ? (p0 + 1) - yb * w : 0;
+  for (int base = m0; base < m1; base += PAINT_PASS) {
+    const int cnt = min(PAINT_PASS, m1 - base);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      srect[threadIdx.x] = rects[base + threadIdx.x];
+      ssc[threadIdx.x] = scores[base + threadIdx.x];
+    }
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const int4 r = srect[k];                // y0, y1, x0, x1
+      const double s = ssc[k];
+      if (ya >= r.x && ya < r.y && xa >= r.z && xa < r.w) v0 = fmax(v0, s);
+      if (yb >= r.x && yb < r.y && xb >= r.z && xb < r.w) v1 = fmax(v1, s);
+    }
+  }
+  if (in0 && in1) {
+    *reinterpret_cast<double2*>(fr + p0) = make_double2(v0, v1);
+  } else if (in0) {
+    fr[p0] = v0;
+  } else if (in1) {
+    fr[p0 + 1] = v1;
+  }
+}
+
+// ---- pixel-level criterion: one number per frame that carries the whole pixel-level ROC ------------------------------------
+// Anomalous frame (|G| > 0 ground-truth pixels): the k-th largest painted value over G, k = ceil(|G| pct / 100); normal frame:
+// the largest painted value = the frame score.  The mask is never formed: every ground-truth pixel names the best-scoring box
+// that covers it (lowest index among equals) in an int32 LDS histogram with one extra bin for "no box"; integer LDS adds, so
+// the totals do not depend on the order.  The k-th largest value is then the largest s_j whose cumulative count
+//   cum(j) = sum of hist[i] over boxes i with s_i > s_j, or s_i == s_j and i <= j
+// reaches k (the first box to reach k in descending order has hist > 0, and everything after it scores no more), or -big when
+// none does.  cum(j) is formed per box by one thread: O(n^2 / 256) per workgroup for n <= PIX_CAP boxes.
+constexpr int PIX_CAP = 2048;                // boxes per frame: 32 KB rectangles + 16 KB scores + 8 KB histogram of LDS
+
+__device__ __forceinline__ void pixel_vote(int p, int w, int n, const int4* srect, const double* ssc, int* hist) {
+  const int y = p / w, x = p - y * w;
+  int best = n;                              // the "no box" bin
+  double bs = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const int4 r = srect[k];
+    if (y >= r.x && y < r.y && x >= r.z && x < r.w) {
+      const double s = ssc[k];
+      if (best == n || s > bs) { best = k; bs = s; }
+    }
+  }
+  atomicAdd(&hist[best], 1);
+}
+
+__global__ void __launch_bounds__(256) pixel_score_kernel(const uint8_t* __restrict__ gt, const double* __restrict__ scores,
+                                                          const int32_t* __restrict__ frame_off,
+                                                          const int4* __restrict__ rects, int pct, double big, int h, int w,
+                                                          double* __restrict__ out, int32_t* __restrict__ gt_count) {
+  __shared__ int4 srect[PIX_CAP];
+  __shared__ double ssc[PIX_CAP];
+  __shared__ int hist[PIX_CAP + 1];
+  __shared__ double red[4];
+  __shared__ int total;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int m0 = frame_off[f];
+  const int n = max(0, min(frame_off[f + 1] - m0, PIX_CAP));      // the wrapper refuses more; here only memory is protected
+  for (int k = tid; k < n; k += 256) {
+    srect[k] = rects[m0 + k];
+    ssc[k] = scores[m0 + k];
+  }
+  for (int k = tid; k <= n; k += 256) hist[k] = 0;
+  if (tid == 0) total = 0;
+  __syncthreads();
+
+  // ground-truth pixels: single bytes up to the first 16-byte boundary, 16-byte loads, single bytes for the tail
+  const int hw = h * w;
+  const uint8_t* g = gt + (int64_t)f * hw;
+  const int head = min(hw, (int)((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15));
+  const int nvec = (hw - head) / 16;
+  int mine = 0;
+  for (int p = tid; p < head; p += 256) {
+    if (g[p]) { ++mine; pixel_vote(p, w, n, srect, ssc, hist); }
+  }
+  for (int v = tid; v < nvec; v += 256) {
+    const int p = head + 16 * v;
+    const uint4 q = *reinterpret_cast<const uint4*>(g + p);
+    const unsigned word[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!word[j]) continue;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if ((word[j] >> (8 * b)) & 0xffu) { ++mine; pixel_vote(p + 4 * j + b, w, n, srect, ssc, hist); }
+      }
+    }
+  }
+  for (int p = head + 16 * nvec + tid; p < hw; p += 256) {
+    if (g[p]) { ++mine; pixel_vote(p, w, n, srect, ssc, hist); }
+  }
+  if (mine) atomicAdd(&total, mine);
+  __syncthreads();
+
+  const int G = total;
+  const long long kth = ((long long)G * pct + 99) / 100;
+  double best = -big;
+  for (int j = tid; j < n; j += 256) {
+    const double sj = ssc[j];
+    bool ok;
+    if (G == 0) {
+      const int4 r = srect[j];
+      ok = r.y > r.x && r.w > r.z;           // a non-empty rectangle paints at least one pixel
+    } else {
+      long long cum = 0;
+      for (int i = 0; i < n; ++i) {
+        const double si = ssc[i];
+        if (si > sj || (si == sj && i <= j)) cum += hist[i];
+      }
+      ok = cum >= kth;
+    }
+    if (ok) best = fmax(best, sj);
+  }
+  for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_down(best, o));
+  if ((tid & 63) == 0) red[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+    out[f] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    gt_count[f] = G;
+  }
 }
 
 // Mann-Whitney form of the ROC-AUC: AUC = (#{(p,n): s_p > s_n} + 0.5 #{s_p == s_n}) / (P N).  Exact integer counts, no
@@ -112,6 +283,44 @@ extern "C" int vv_roc_auc_counts(const double* scores, const uint8_t* labels, in
   if (n == 0) return VV_OK;
   VV_LAUNCH(auc_count_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, scores, labels, n,
             (unsigned long long*)out3);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_cube_scores(const float* raw, const float* of, const int32_t* cube_stat, const double* stats, double w_raw,
+                              double w_of, double big, int32_t n, double* out, vv_stream stream) {
+  if (n < 0) return VV_ERR_BAD_ARG;
+  if (n == 0) return VV_OK;
+  if (!raw || !cube_stat || !stats || !out) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(cube_score_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, raw, of, cube_stat, stats, w_raw,
+            w_of, big, n, out);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_paint_masks(const double* scores, const int32_t* frame_off, const int32_t* rects, int32_t n_frames,
+                              int32_t h, int32_t w, double* out, vv_stream stream) {
+  if (n_frames < 0 || h < 0 || w < 0 || (int64_t)h * w > INT32_MAX - PAINT_TILE) return VV_ERR_BAD_ARG;
+  if (n_frames == 0 || h == 0 || w == 0) return VV_OK;
+  if (!scores || !frame_off || !rects || !out) return VV_ERR_BAD_ARG;
+  const int tiles = (h * w + 1 + PAINT_TILE - 1) / PAINT_TILE;      // + 1: a frame that starts 8 bytes off a 16-byte boundary
+  for (int f0 = 0; f0 < n_frames; f0 += 65535) {                    // gridDim.y
+    VV_LAUNCH(paint_mask_kernel, dim3(tiles, min(65535, n_frames - f0)), dim3(256), 0, (hipStream_t)stream, scores,
+              frame_off, reinterpret_cast<const int4*>(rects), f0, h, w, out);
+    VV_CHECK_LAUNCH();
+  }
+  return VV_OK;
+}
+
+extern "C" int vv_pixel_scores(const uint8_t* gt, const double* scores, const int32_t* frame_off, const int32_t* rects,
+                               int32_t pct, double big, int32_t n_frames, int32_t h, int32_t w, int32_t max_boxes, double* out,
+                               int32_t* gt_count, vv_stream stream) {
+  if (n_frames < 0 || h < 0 || w < 0 || max_boxes < 0 || pct < 1 || pct > 100 || (int64_t)h * w > INT32_MAX) return VV_ERR_BAD_ARG;
+  if (max_boxes > PIX_CAP) return VV_ERR_UNSUPPORTED;
+  if (n_frames == 0) return VV_OK;
+  if (!frame_off || !out || !gt_count || (!gt && h * w > 0) || ((!scores || !rects) && max_boxes > 0)) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(pixel_score_kernel, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, gt, scores, frame_off,
+            reinterpret_cast<const int4*>(rects), pct, big, h, w, out, gt_count);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

@@ -7,6 +7,14 @@ mask is the maximum over the cubes whose painted rectangle is non-empty (``-1e5`
 ``vv_frame_scores`` computes directly from the device-resident per-cube errors.
 
 ``roc_auc``: frame-level ROC-AUC (utils.py:29-41, sklearn roc_curve + auc) as the exact Mann-Whitney pair count.
+
+Pixel-level evaluation (the criterion the reference saves its ``score_mask`` files for and never evaluates, test.py:362-365):
+``box_rects`` resolves the painted rectangles on the host, ``cube_scores`` keeps the per-cube scores on the device, ``paint_masks``
+paints the h x w masks there, ``merge_groups`` brings the cubes of several block groups into frame order and ``pixel_scores``
+reduces a frame to the one number that carries its pixel-level ROC: with ``G`` the ground-truth pixels of an anomalous frame,
+the frame is detected at threshold ``t`` iff ``100 * #{p in G: mask[p] >= t} >= percent * #G``, i.e. iff the ``k``-th largest
+mask value over ``G``, ``k = ceil(#G * percent / 100)``, is ``>= t``; a normal frame is a false positive iff ``mask.max() >= t``.
+The area under that ROC is ``roc_auc`` of those numbers against the frame labels.
 """
 import math
 
@@ -16,6 +24,7 @@ import torch
 from . import _lib
 
 BIG = 100000          # test.py:188 big_number
+PIXEL_MAX_BOXES = 2048      # boxes of one frame ``pixel_scores`` takes (the LDS table of vv_pixel_scores)
 
 
 def box_paints(bboxes, h, w):
@@ -26,6 +35,149 @@ def box_paints(bboxes, h, w):
         y0, y1 = int(math.ceil(b[1])), int(math.ceil(b[3]))
         out[m] = len(range(*slice(y0, y1).indices(h))) > 0 and len(range(*slice(x0, x1).indices(w))) > 0
     return out
+
+
+def box_rects(bboxes, h, w):
+    """The rectangle ``mask[ceil(y1):ceil(y2), ceil(x1):ceil(x2)]`` (test.py:352-355) of every box as int32 ``[n,4]`` rows
+    ``(y0, y1, x0, x1)``: rows ``range(y0, y1)``, columns ``range(x0, x1)`` of an ``h x w`` mask.  Python slicing resolved here, on
+    the host: a negative ceiling wraps, values past the edge clip; the kernels neither round nor wrap.  A row with ``y1 <= y0`` or
+    ``x1 <= x0`` paints nothing: ``box_paints(b, h, w)[m] == (y1 > y0 and x1 > x0)``."""
+    out = np.zeros((len(bboxes), 4), np.int32)
+    for m, b in enumerate(bboxes):
+        x0, x1 = int(math.ceil(b[0])), int(math.ceil(b[2]))
+        y0, y1 = int(math.ceil(b[1])), int(math.ceil(b[3]))
+        out[m, 0:2] = slice(y0, y1).indices(h)[:2]
+        out[m, 2:4] = slice(x0, x1).indices(w)[:2]
+    return out
+
+
+def _dv(a, dt, dev):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dt).contiguous()
+
+
+def _stats(stats, dev):
+    stats = _dv(np.asarray(stats, np.float64).reshape(-1, 4) if not torch.is_tensor(stats) else stats, torch.float64, dev)
+    return stats if stats.numel() else torch.zeros((1, 4), dtype=torch.float64, device=dev)
+
+
+def cube_scores(raw, of, cube_stat, stats, w_raw, w_of):
+    """The per-cube scores ``frame_scores`` max-reduces, kept: CUDA float64 ``[n]``, ``BIG`` where ``cube_stat`` is ``-1``, else
+    ``w_raw * ((raw - mu_r) / sd_r) [+ w_of * ((of - mu_o) / sd_o)]`` in float64 with every product and sum rounded on its own (the
+    kernel shares the device function with ``vv_frame_scores``).  Arguments as for ``frame_scores``.  A NaN score (zero training
+    std, error equal to the mean) is outside the domain of everything downstream, as it is for ``frame_scores``."""
+    if not raw.is_cuda:
+        raise _lib.VecVadHipError('cube_scores needs device-resident scores; vec_vad_amd has no CPU path')
+    dev = raw.device
+    cube_stat, stats = _dv(cube_stat, torch.int32, dev), _stats(stats, dev)
+    raw = raw.to(torch.float32).contiguous()
+    of = of.to(torch.float32).contiguous() if of is not None else None
+    n = raw.numel()
+    if cube_stat.numel() != n or (of is not None and of.numel() != n):
+        raise ValueError('cube_scores: raw, of and cube_stat must name the same %d cubes' % n)
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().vv_cube_scores(raw.data_ptr(), of.data_ptr() if of is not None else None, cube_stat.data_ptr(),
+                                        stats.data_ptr(), float(w_raw), float(w_of), float(BIG), n, out.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream), 'vv_cube_scores')
+    return out
+
+
+def _csr(frame_off, n):
+    """Host int64 copy of a CSR table, checked against ``n`` rows: the kernels trust it."""
+    off = (frame_off.cpu().numpy() if torch.is_tensor(frame_off) else np.asarray(frame_off)).astype(np.int64).reshape(-1)
+    if off.size < 1 or (np.diff(off) < 0).any() or off[0] < 0 or off[-1] > n:
+        raise ValueError('frame_off must be non-decreasing offsets into the %d cubes given' % n)
+    return off
+
+
+def paint_masks(scores, frame_off, rects, h, w, out=None):
+    """The painted masks of ``F`` frames on the device: ``out[f]`` is max-combined with ``scores[m]`` over the rectangle
+    ``rects[m]`` (``box_rects`` rows) of every cube ``m`` in ``[frame_off[f], frame_off[f+1])`` -- what ``test.paint_frame`` paints
+    per frame.  scores: CUDA float64 ``[n]`` (``cube_scores``); frame_off: int32 ``[F+1]``; rects: int32 ``[n,4]``.  ``out``: CUDA
+    float64 ``[F,h,w]``, contiguous, max-accumulated into (a frame whose cubes come from several groups is painted once per
+    group); None starts from the background ``-BIG``.  NaN scores are outside the domain (dropped, where numpy propagates)."""
+    if not scores.is_cuda:
+        raise _lib.VecVadHipError('paint_masks needs device-resident scores; vec_vad_amd has no CPU path')
+    dev = scores.device
+    scores = scores.to(torch.float64).contiguous().view(-1)
+    off = _csr(frame_off, scores.numel())
+    F = off.size - 1
+    rects = _dv(rects, torch.int32, dev).view(-1, 4)
+    if rects.shape[0] != scores.numel():
+        raise ValueError('paint_masks: %d rectangles for %d scores' % (rects.shape[0], scores.numel()))
+    if out is None:
+        out = torch.full((F, h, w), -float(BIG), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (F, h, w) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('paint_masks: out must be a contiguous float64 [%d,%d,%d] tensor on %s' % (F, h, w, dev))
+    if scores.numel() == 0:           # nothing to paint: every frame keeps what it holds
+        return out
+    _lib.check(_lib.lib().vv_paint_masks(scores.data_ptr(), _dv(off, torch.int32, dev).data_ptr(), rects.data_ptr(), F, int(h),
+                                        int(w), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_paint_masks')
+    return out
+
+
+def merge_groups(groups, n_frames=None, device=None):
+    """One cube list in frame order out of several.  ``groups``: list of ``(off, scores, rects)`` -- ``off`` a host int32 CSR over
+    the same ``F`` frames (cubes of frame ``f`` = rows ``[off[f], off[f+1])`` of that group's tensors), ``scores`` ``[n_g]`` and
+    ``rects`` ``[n_g,4]`` tensors on one device.  Returns ``(off, scores, rects)`` with the cubes ordered by frame, then by group
+    in list order, then as they stand in the group.  The gather index is built on the host from the CSRs; the data moves with
+    ``torch.cat`` + ``index_select`` and never visits the host.  ``n_frames`` and ``device`` tell ``F`` and where the (empty) tensors live for an empty list."""
+    if not groups:
+        if n_frames is None:
+            raise ValueError('merge_groups: no group and no n_frames to tell the number of frames')
+        return (np.zeros(n_frames + 1, np.int32), torch.zeros(0, dtype=torch.float64, device=device),
+                torch.zeros((0, 4), dtype=torch.int32, device=device))
+    offs = np.stack([_csr(off, len(sc)) for off, sc, _ in groups])                     # [G, F+1]
+    if n_frames is not None and offs.shape[1] != n_frames + 1:
+        raise ValueError('merge_groups: the groups cover %d frames, not %d' % (offs.shape[1] - 1, n_frames))
+    base = np.concatenate([[0], np.cumsum([len(sc) for _, sc, _ in groups])[:-1]]).astype(np.int64)
+    cnt = np.diff(offs, axis=1).T.reshape(-1)                                              # runs in (frame, group) order
+    start = (offs[:, :-1] + base[:, None]).T.reshape(-1)                                   # first row of each run in the cat
+    first = np.concatenate([[0], np.cumsum(cnt)])
+    idx = np.repeat(start - first[:-1], cnt) + np.arange(first[-1])
+    off = first[::offs.shape[0]].astype(np.int32)
+    dev = groups[0][1].device
+    idx = torch.from_numpy(idx).to(dev)
+    scores = torch.cat([sc.reshape(-1) for _, sc, _ in groups]).index_select(0, idx)
+    rects = torch.cat([rc.reshape(-1, 4) for _, _, rc in groups]).index_select(0, idx)
+    return off, scores, rects
+
+
+def pixel_scores(gt, scores, frame_off, rects, percent=40, out=None):
+    """The pixel-level score of ``F`` frames (module docstring).  gt: uint8 ``[F,h,w]`` ground truth (non-zero = anomalous pixel;
+    CUDA tensor, or a host array that is uploaded); scores / frame_off / rects as for ``paint_masks``, with ALL cubes of a frame in
+    this one call (``merge_groups``): the quantile is not max-decomposable.  Returns ``(s_pix, gt_count)``, CUDA float64 ``[F]``
+    and int32 ``[F]``: ``gt_count[f]`` = ground-truth pixels of frame ``f``; ``s_pix[f]`` = the ``k``-th largest value of the painted
+    mask over them, ``k = (gt_count * percent + 99) // 100``, for an anomalous frame (``-BIG`` when fewer than ``k`` of them lie
+    under a box) and ``mask.max()`` for a normal one, written into ``out`` when one is given.  The mask itself is never formed.  A frame with more than
+    ``PIXEL_MAX_BOXES`` cubes is a ``ValueError`` before any launch.  NaN scores are outside the domain."""
+    if not scores.is_cuda:
+        raise _lib.VecVadHipError('pixel_scores needs device-resident scores; vec_vad_amd has no CPU path')
+    if int(percent) != percent or not 1 <= int(percent) <= 100:
+        raise ValueError('pixel_scores: percent must be an integer in 1..100, got %r' % (percent,))
+    dev = scores.device
+    scores = scores.to(torch.float64).contiguous().view(-1)
+    off = _csr(frame_off, scores.numel())
+    F = off.size - 1
+    gt = _dv(gt, torch.uint8, dev)
+    if gt.dim() != 3 or gt.shape[0] != F:
+        raise ValueError('pixel_scores: gt must be [%d,h,w], got %s' % (F, tuple(gt.shape)))
+    rects = _dv(rects, torch.int32, dev).view(-1, 4)
+    if rects.shape[0] != scores.numel():
+        raise ValueError('pixel_scores: %d rectangles for %d scores' % (rects.shape[0], scores.numel()))
+    counts = np.diff(off)
+    most = int(counts.max()) if F else 0
+    if most > PIXEL_MAX_BOXES:
+        raise ValueError('pixel_scores: frame %d has %d boxes, at most %d are supported' % (int(counts.argmax()), most, PIXEL_MAX_BOXES))
+    if out is None:
+        out = torch.empty(F, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (F,) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('pixel_scores: out must be a contiguous float64 [%d] tensor on %s' % (F, dev))
+    cnt = torch.empty(F, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().vv_pixel_scores(gt.data_ptr(), scores.data_ptr(), _dv(off, torch.int32, dev).data_ptr(), rects.data_ptr(),
+                                         int(percent), float(BIG), F, int(gt.shape[1]), int(gt.shape[2]), most, out.data_ptr(),
+                                         cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_pixel_scores')
+    return out, cnt
 
 
 def frame_scores(raw, of, frame_off, cube_stat, stats, paints, w_raw, w_of, out=None):
