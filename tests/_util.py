@@ -60,3 +60,35 @@ def observe(name, **vals):
             f.write(json.dumps(rec) + '\n')
     except OSError:
         pass
+
+
+# ---- kernel-level parity against a float64 restatement (tests/test_gpu_train_ops.py, tests/test_gpu_outconv.py) ----
+FLOOR = 16 * 2.0 ** -23      # floor of the float-summation bar
+SENT = 3.0                   # sentinel behind and beside every output
+
+
+def gen(*key):
+    return torch.Generator(device='cpu').manual_seed(sum((i + 1) * 7919 * int(k) for i, k in enumerate(key)) % (2 ** 31))
+
+
+def err(got, ref):
+    ref = ref.double()
+    return (got.detach().cpu().double() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-300)
+
+
+def bar(op, what, got, ref64, ref32, family='train_ops'):
+    """the float-summation bar: err_hip of the kernel against err_ref32 of the SAME restatement evaluated in float32 on the same inputs,
+    err_hip <= max(8 err_ref32, 16 * 2^-23); prints / records the figures before it asserts"""
+    e_hip, e_32 = err(got, ref64), err(ref32, ref64)
+    observe(family + ':' + op, err_hip=e_hip, err_ref32=e_32)
+    assert e_hip <= max(8 * e_32, FLOOR), (op, what, e_hip, e_32)
+
+
+def away_from_zero(y, a, b, margin=1e-3):
+    """y [.., C] float32 nudged so that no |a y + b| (float64 of the float32 values) is below the margin"""
+    z = a.double() * y.double() + b.double()
+    bad = z.abs() < 4 * margin
+    tgt = torch.where(z >= 0, 8 * margin, -8 * margin)
+    y = torch.where(bad, ((tgt - b.double()) / a.double()).float(), y)
+    assert (a.double() * y.double() + b.double()).abs().min().item() >= margin
+    return y

@@ -1,4 +1,5 @@
-"""Kernel-level parity of what an fp32 train step launches besides its 3x3 convolutions and the 1x1 output conv: the fp32
+"""Kernel-level parity of what an fp32 train step launches besides its 3x3 convolutions (tests/test_gpu_unet.py) and the 1x1 output
+conv (tests/test_gpu_outconv.py): the fp32
 transposed-conv family (vv_conv_mfma VV_CONVT_FWD / VV_CONVT_DGRAD, vv_wgrad_mfma + vv_wgrad_reduce with kind = VV_CONVT_FWD), BatchNorm
 (vv_bn_finalize, vv_bn_bwd_reduce + vv_bn_bwd_apply, vv_bn_bwd_sums), the reductions, adapters and layout copies of vv_elem.hip and the
 optimiser (vv_adam_tick + vv_adam_bucketed, vv_adam) -- each through the C ABI with G = 2 groups of different data (a wrong *_gstride
@@ -33,14 +34,12 @@ import pytest
 import torch
 
 import train_ops_restatement as R
-from _util import observe
+from _util import FLOOR, SENT, away_from_zero as _away_from_zero, bar as _bar, err as _err, gen as _gen, observe
 
 pytestmark = pytest.mark.gpu
 
 G = 2
 F64 = torch.float64
-FLOOR = 16 * 2.0 ** -23
-SENT = 3.0
 CONVT_SHAPES = [(16, 64, 32, 3), (8, 128, 64, 5), (8, 64, 32, 4), (4, 256, 128, 17), (4, 128, 64, 8)]
 
 
@@ -53,22 +52,6 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _gen(*key):
-    return torch.Generator(device='cpu').manual_seed(sum((i + 1) * 7919 * int(k) for i, k in enumerate(key)) % (2 ** 31))
-
-
-def _err(got, ref):
-    ref = ref.double()
-    return (got.detach().cpu().double() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-300)
-
-
-def _bar(op, what, got, ref64, ref32):
-    """the float-summation bar of the module docstring; prints / records the figures before it asserts"""
-    e_hip, e_32 = _err(got, ref64), _err(ref32, ref64)
-    observe('train_ops:' + op, err_hip=e_hip, err_ref32=e_32)
-    assert e_hip <= max(8 * e_32, FLOOR), (op, what, e_hip, e_32)
-
-
 def _f64(*ts):
     return [t.cpu().double() if t is not None else None for t in ts]
 
@@ -79,16 +62,6 @@ def _pack(L, lib, w, mode, K, N):
     out = torch.zeros(G, 9 * K * N + 16, device='cuda')
     L.check(lib.vv_pack_weights(tab.data_ptr(), 1, G, w.data_ptr(), w[0].numel(), out.data_ptr(), out.stride(0), 9 * K * N, _st()), 'pack')
     return out
-
-
-def _away_from_zero(y, a, b, margin=1e-3):
-    """y [.., C] float32 nudged so that no |a y + b| (float64 of the float32 values) is below the margin"""
-    z = a.double() * y.double() + b.double()
-    bad = z.abs() < 4 * margin
-    tgt = torch.where(z >= 0, 8 * margin, -8 * margin)
-    y = torch.where(bad, ((tgt - b.double()) / a.double()).float(), y)
-    assert (a.double() * y.double() + b.double()).abs().min().item() >= margin
-    return y
 
 
 # ================================================================================================ transposed conv, fp32

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import digest, digest_close, load_golden
+from _util import FLOOR, SENT, bar, digest, digest_close, load_golden, observe
 
 pytestmark = pytest.mark.gpu
 
@@ -467,12 +467,47 @@ def test_state_dict_roundtrip_and_move():
         net(torch.zeros(1, 15, 32, 32), torch.zeros(1, 2, 32, 32))      # no CPU fallback
 
 
+def _conv3_ref(x, w, bias=None, dgrad=False, dt=torch.float64):
+    """x [B, H, H, K] -> [B, H, H, N] on the CPU with torch.nn.functional.conv2d in dtype dt; w = the nn.Conv2d filter [Cout, Cin, 3, 3]
+    of the forward conv; dgrad: the data gradient (K = Cout, N = Cin) = conv2d with the transposed, flipped filter"""
+    w = w.detach().cpu().to(dt)
+    if dgrad:
+        w = w.transpose(0, 1).flip(2, 3)
+    y = torch.nn.functional.conv2d(x.detach().cpu().to(dt).permute(0, 3, 1, 2), w, None if bias is None else bias.detach().cpu().to(dt),
+                                   padding=1)
+    return y.permute(0, 2, 3, 1)
+
+
+def _conv_check(names, ys, xin, w, bias=None, dgrad=False):
+    """every y of ys against conv2d in float64 on the CPU (xin float64): err = max |y - ref64| over the whole output as a fraction of
+    the reference's maximum, recorded before it is judged.  All: err <= 2e-5, the project's bar for fp32 convolutions.  The direct
+    kernel ('direct...') is what the Winograd kernels are measured against, so it is also held to the float-summation rule of
+    tests/_util.py: err <= max(8 err_ref32, 16 * 2^-23) with err_ref32 the same figure of conv2d in float32 on the same inputs."""
+    ref = _conv3_ref(xin, w, bias, dgrad)
+    top = ref.abs().max().item()
+    e32 = (_conv3_ref(xin.float(), w, bias, dgrad, torch.float32).double() - ref).abs().max().item() / top
+    for name, y in zip(names, ys):
+        e = (y.detach().cpu().double().reshape(ref.shape) - ref).abs().max().item() / top
+        observe('conv3:' + name, err_hip=e, err_ref32=e32)
+        assert e <= 2e-5, (name, e)
+        if name.startswith('direct'):
+            assert e <= max(8 * e32, FLOOR), (name, e, e32)
+
+
 @pytest.mark.parametrize('H,Cin,Cout,B', [(32, 16, 32, 3), (32, 32, 32, 2), (16, 64, 64, 5), (8, 256, 128, 9), (4, 128, 256, 33),
                                            (16, 32, 64, 1)])
 def test_winograd_conv_matches_direct_conv(H, Cin, Cout, B):
     """vv_conv_wino (Winograd F(2x2,3x3) on the matrix cores) against vv_conv_mfma (direct implicit GEMM) on the same
     tensors, forward panel and data-gradient panel, BatchNorm+ReLU-on-load input, bias and BatchNorm partial sums:
-    agreement to fp32 round-off of the transforms (ragged last workgroup: B is not a multiple of the images per tile)."""
+    agreement to fp32 round-off of the transforms (ragged last workgroup: B is not a multiple of the images per tile).
+
+    The direct kernel is the reference of every Winograd test, so BOTH kernels are also held to torch.nn.functional.conv2d in float64
+    on the CPU, every element, at 2e-5 of the reference's maximum (_conv_check; the direct kernel also at the float-summation rule, which
+    is what tells an error of a few 1e-5 in it from round-off): forward with VV_IN_ACT,
+    bias and `stats`, forward with VV_IN_CAT (channels [0, Cin / 2) BatchNorm+ReLU of src0, the rest src1 as it is; Cin >= 32, a K
+    chunk of 16 channels never straddles the split), data gradient with VV_IN_PLAIN.  `stats`: the rows summed over the tiles against
+    the column sums and sums of squares of the STORED output under the float-summation bar of tests/_util.py, the rows behind the
+    vv_conv_ntiles2 / vv_wino_ntiles rows of the launch keep the sentinel."""
     import ctypes as C
     from vec_vad_amd import _lib as L
     lib = L.lib()
@@ -493,6 +528,7 @@ def test_winograd_conv_matches_direct_conv(H, Cin, Cout, B):
         L.check(fn(tab.data_ptr(), 1, G, w.data_ptr(), U, out.data_ptr(), out.stride(0), (9 if taps == 9 else 1) * K * N, st), 'pack')
         return out
 
+    assert lib.vv_conv_ntiles2(B, H, H, L.CONV3, 0) == lib.vv_conv_ntiles(B, H, H)
     for dgrad in (False, True):
         K, N = (Cout, Cin) if dgrad else (Cin, Cout)
         if N % 32:
@@ -500,9 +536,9 @@ def test_winograd_conv_matches_direct_conv(H, Cin, Cout, B):
         src = torch.randn(G, B * H * H, K, generator=g).cuda() if dgrad else x
         pd, pw = pack(lib.vv_pack_weights, 1 if dgrad else 0, K, N, 9), pack(lib.vv_pack_wino, 1 if dgrad else 0, K, N, 16)
         outs, stats = [], []
-        for fn, pk, nt in ((lib.vv_conv_mfma, pd, lib.vv_conv_ntiles(B, H, H)), (lib.vv_conv_wino, pw, lib.vv_wino_ntiles(B, H))):
+        for fn, pk, nt in ((lib.vv_conv_mfma, pd, lib.vv_conv_ntiles2(B, H, H, L.CONV3, 0)), (lib.vv_conv_wino, pw, lib.vv_wino_ntiles(B, H))):
             y = torch.full((G, B * H * H, N), 3.0, device='cuda')
-            s_ = torch.zeros(G, nt, 2, N, device='cuda')
+            s_ = torch.full((G * nt + 3, 2, N), SENT, device='cuda')          # dense [G][ntiles][2][N] + slack rows
             mode = L.IN_PLAIN if dgrad else L.IN_ACT
             cp = L.ConvParams(L.CONV3, mode, G, B, H, H, K, K, N, L.view(src, K, 0, src.stride(0)),
                               None if dgrad else a.data_ptr(), None if dgrad else b.data_ptr(), K, L.NULL_VIEW, 0, 0, None,
@@ -510,11 +546,84 @@ def test_winograd_conv_matches_direct_conv(H, Cin, Cout, B):
                               None if dgrad else s_.data_ptr())
             L.check(fn(C.byref(cp), st), 'conv')
             outs.append(y)
-            stats.append(s_.sum(1))
+            assert torch.equal(s_[G * nt:].cpu(), torch.full((3, 2, N), SENT))          # nothing behind the reported rows
+            stats.append(s_[:G * nt].view(G, nt, 2, N).sum(1))
+            if not dgrad:
+                tot, yc = s_[:G * nt].view(G, nt, 2, N).cpu().double().sum(1), y.cpu()
+                for gi in range(G):
+                    which = 'direct' if fn is lib.vv_conv_mfma else 'wino'
+                    bar(which + '_stats', 'sum', tot[gi, 0], yc[gi].double().sum(0), yc[gi].sum(0), family='conv3')
+                    bar(which + '_stats', 'sumsq', tot[gi, 1], (yc[gi].double() ** 2).sum(0), (yc[gi] ** 2).sum(0), family='conv3')
+        for gi in range(G):          # each kernel against float64 first: a failure names the kernel that is off
+            xin = src[gi].cpu().double() if dgrad else torch.relu(a[gi].cpu().double() * x[gi].cpu().double() + b[gi].cpu().double())
+            tag = '_dgrad' if dgrad else '_fwd'
+            _conv_check(('direct' + tag, 'wino' + tag), (outs[0][gi], outs[1][gi]), xin.view(B, H, H, K), w[gi],
+                        None if dgrad else bias[gi], dgrad)
         scale = outs[0].abs().max().item()
         assert (outs[0] - outs[1]).abs().max().item() <= 2e-5 * scale, (dgrad, (outs[0] - outs[1]).abs().max().item(), scale)
         if not dgrad:
             torch.testing.assert_close(stats[0], stats[1], rtol=2e-4, atol=2e-3)
+
+    if Cin >= 32:          # forward with a concat input
+        c0 = Cin // 2
+        x0 = torch.randn(G, B * H * H, c0, generator=g).cuda()
+        x1 = torch.randn(G, B * H * H, Cin - c0, generator=g).cuda()
+        outs = []
+        for fn, pk in ((lib.vv_conv_mfma, pack(lib.vv_pack_weights, 0, Cin, Cout, 9)), (lib.vv_conv_wino, pack(lib.vv_pack_wino, 0, Cin, Cout, 16))):
+            y = torch.full((G, B * H * H * Cout + 64), SENT, device='cuda')
+            cp = L.ConvParams(L.CONV3, L.IN_CAT, G, B, H, H, Cin, Cin, Cout, L.view(x0, c0, 0, x0.stride(0)), a.data_ptr(), b.data_ptr(), Cin,
+                              L.view(x1, Cin - c0, 0, x1.stride(0)), c0, 0, None, pk.data_ptr(), pk.stride(0), None, 0,
+                              L.view(y, Cout, 0, y.stride(0)), None)
+            L.check(fn(C.byref(cp), st), 'conv cat')
+            assert torch.equal(y[:, -64:].cpu(), torch.full((G, 64), SENT))
+            outs.append(y[:, :-64].view(G, B * H * H, Cout))
+        for gi in range(G):
+            ac, bc = a[gi, :c0].cpu().double(), b[gi, :c0].cpu().double()
+            xin = torch.cat([torch.relu(ac * x0[gi].cpu().double() + bc), x1[gi].cpu().double()], 1)
+            _conv_check(('direct_cat', 'wino_cat'), (outs[0][gi], outs[1][gi]), xin.view(B, H, H, Cin), w[gi])
+
+
+@pytest.mark.parametrize('mode', ['pool', 'cube'])
+def test_direct_conv_pool_and_cube_loads_against_float64(mode):
+    """VV_IN_POOL (2x2 max of relu(a x + b) on load: H = 16, 32 channels from a 32x32 source) and VV_IN_CUBE (channel gather through a
+    15 -> 16 channel map with -1 entries, H = 32, the cube shared by the groups) on vv_conv_mfma: the generic load path of vv_common.h
+    still serves them, the bank no longer launches them.  Every element against conv2d in float64 (_conv_check)."""
+    import ctypes as C
+    from vec_vad_amd import _lib as L
+    lib = L.lib()
+    G, Cout = 2, 32
+    g = torch.Generator(device='cpu').manual_seed(7 if mode == 'pool' else 8)
+    st = torch.cuda.current_stream().cuda_stream
+    if mode == 'pool':
+        H, Cin, B = 16, 32, 3
+        x = torch.randn(G, B * 4 * H * H, Cin, generator=g)
+        a, b = torch.rand(G, Cin, generator=g) + 0.5, torch.randn(G, Cin, generator=g) * 0.2
+        act = torch.relu(a[:, None].double() * x.double() + b[:, None].double()).view(G, B, H, 2, H, 2, Cin).amax((3, 5))
+        xd, ad, bd = x.cuda(), a.cuda(), b.cuda()
+        src, ap, bp, chm, im = L.view(xd, Cin, 0, xd.stride(0)), ad.data_ptr(), bd.data_ptr(), None, L.IN_POOL
+    else:
+        H, Cin, B = 32, 16, 2
+        cube = torch.rand(B * H * H, 15, generator=g)
+        chmap = torch.tensor([[0, 1, 2, 3, 4, 5, -1, -1, -1, 9, 10, 11, 12, 13, 14, -1],
+                              [-1, -1, -1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 0, 1, 2, -1]], dtype=torch.int32)
+        act = (cube.double()[:, chmap.clamp_min(0).long()] * (chmap >= 0).double()).permute(1, 0, 2).reshape(G, B, H, H, Cin)
+        xd, chd = cube.cuda(), chmap.cuda()
+        src, ap, bp, chm, im = L.view(xd, 15, 0, 0), None, None, chd.data_ptr(), L.IN_CUBE
+    w = torch.randn(G, Cout, Cin, 3, 3, generator=g) * 0.1
+    bias = torch.randn(G, Cout, generator=g)
+    wd, bsd = w.cuda(), bias.cuda()
+    ent = (L.PackEntry * 1)(L.PackEntry(0, 0, 0, Cin, Cin, Cout))
+    tab = torch.frombuffer(bytearray(bytes(ent)), dtype=torch.uint8).cuda()
+    pk = torch.zeros(G, 9 * Cin * Cout, device='cuda')
+    L.check(lib.vv_pack_weights(tab.data_ptr(), 1, G, wd.data_ptr(), w[0].numel(), pk.data_ptr(), pk.stride(0), 9 * Cin * Cout, st), 'pack')
+    y = torch.full((G, B * H * H * Cout + 64), SENT, device='cuda')
+    cp = L.ConvParams(L.CONV3, im, G, B, H, H, Cin, Cin, Cout, src, ap, bp, Cin, L.NULL_VIEW, 0, 0, chm, pk.data_ptr(), pk.stride(0),
+                      bsd.data_ptr(), Cout, L.view(y, Cout, 0, y.stride(0)), None)
+    L.check(lib.vv_conv_mfma(C.byref(cp), st), 'conv ' + mode)
+    y = y.cpu()
+    assert torch.equal(y[:, -64:], torch.full((G, 64), SENT))
+    for gi in range(G):
+        _conv_check(('direct_' + mode,), (y[gi, :-64],), act[gi], w[gi], bias[gi])
 
 
 @pytest.mark.parametrize('H,C0,C1,Cout,B', [(32, 32, 32, 32, 3), (8, 128, 128, 128, 5), (4, 128, 128, 256, 9)])
@@ -702,7 +811,8 @@ def test_full_bank_b512_linearity_and_determinism():
 def test_winograd_weight_gradient_matches_direct(H, Cin, Cout, B):
     """vv_wgrad_mfma with pad0 bit 8 (Winograd F(2x2,3x3) weight gradient: dU = sum_tiles V^T dM, dg = G^T dU G) against the
     direct tap-by-tap kernel on the same activation / gradient tensors (BatchNorm+ReLU-on-load input, ragged batch), through
-    the same slab reduction into the nn.Conv2d weight layout, and against a float64 evaluation on a sample of entries."""
+    the same slab reduction into the nn.Conv2d weight layout, and both forms against the float64 sum, every entry of
+    [G, Cout, Cin, 3, 3]."""
     import ctypes as C
     from vec_vad_amd import _lib as L
     lib = L.lib()
@@ -729,13 +839,22 @@ def test_winograd_weight_gradient_matches_direct(H, Cin, Cout, B):
     scale = outs[0].abs().max().item()
     for o in outs[1:]:
         assert (outs[0] - o).abs().max().item() <= 5e-5 * scale, ((outs[0] - o).abs().max().item(), scale)
-    # float64 spot check: dW[co,ci,ky,kx] = sum_{b,y,x} act[b,y+ky-1,x+kx-1,ci] * dy[b,y,x,co]
-    act = torch.relu(x.double() * a.double()[:, None, :] + b.double()[:, None, :]).view(G, B, H, H, Cin)
-    dyd = dy.double().view(G, B, H, H, Cout)
+    # float64, EVERY entry, both forms: dW[co,ci,ky,kx] = sum_{b,y,x} act[b,y+ky-1,x+kx-1,ci] * dy[b,y,x,co] at 5e-5 of the reference's
+    # maximum (the direct form is the reference of the Winograd form above and in test_winograd_kernels_random_sweep)
+    xc, dyc, ac, bc = x.cpu().double(), dy.cpu().double(), a.cpu().double(), b.cpu().double()
+    act = torch.relu(xc * ac[:, None, :] + bc[:, None, :]).view(G, B, H, H, Cin)
+    dyd = dyc.view(G, B * H * H, Cout)
     pad = torch.nn.functional.pad(act, (0, 0, 1, 1, 1, 1))
-    for (gi, co, ci, ky, kx) in ((0, 0, 0, 0, 0), (1, Cout - 1, Cin - 1, 2, 1), (0, 5, 7, 1, 1), (1, 17, 3, 0, 2)):
-        ref = (pad[gi, :, ky:ky + H, kx:kx + H, ci] * dyd[gi, :, :, :, co]).sum().item()
-        assert abs(outs[1][gi, co, ci, ky, kx].item() - ref) <= 2e-4 * scale + 1e-4 * abs(ref), (gi, co, ci, ky, kx)
+    ref = torch.zeros(G, Cout, Cin, 3, 3, dtype=torch.float64)
+    for gi in range(G):
+        for ky in range(3):
+            for kx in range(3):
+                ref[gi, :, :, ky, kx] = dyd[gi].t() @ pad[gi, :, ky:ky + H, kx:kx + H].reshape(B * H * H, Cin)
+    for name, o in zip(('direct', 'wino'), outs):
+        for gi in range(G):
+            e = (o[gi].cpu().double() - ref[gi]).abs().max().item() / ref[gi].abs().max().item()
+            observe('conv3:wgrad_' + name, err_hip=e)
+            assert e <= 5e-5, (name, gi, e)
 
 
 def test_eval_fold_matches_unfolded_path_and_tracks_updates(monkeypatch):

@@ -1,6 +1,7 @@
 """The float64 restatements of tests/train_ops_restatement.py against torch autograd of the nn modules the reference model uses
-(model/unet.py: nn.ConvTranspose2d(k3, s2, p1, op1), nn.BatchNorm2d -> nn.ReLU -> nn.MaxPool2d(2); train.py: torch.optim.Adam(eps=1e-7)).
-They guard the reference side of every test in tests/test_gpu_train_ops.py and need no GPU.  Everything runs in float64 on small
+(model/unet.py: nn.ConvTranspose2d(k3, s2, p1, op1), nn.BatchNorm2d -> nn.ReLU -> nn.MaxPool2d(2), nn.Conv2d(C, oc, 1); train.py:
+torch.optim.Adam(eps=1e-7)) and of the eval-mode nn.Conv2d(k3, p1) -> nn.BatchNorm2d pair.
+They guard the reference side of every test in tests/test_gpu_train_ops.py and tests/test_gpu_outconv.py and need no GPU.  Everything runs in float64 on small
 shapes: agreement to 1e-11 of the tensor's maximum (two float64 evaluations that differ in summation order only)."""
 import numpy as np
 import pytest
@@ -133,6 +134,67 @@ def test_pool_route_sends_gradient_to_first_maximum():
     act = torch.tensor([[1.0, 1.0, 0.0, 2.0], [1.0, 0.5, 2.0, 2.0]], dtype=F64).reshape(1, 2, 4, 1)
     r = R.pool_route(act, torch.tensor([5.0, 7.0], dtype=F64).reshape(1, 1, 2, 1))
     assert r.reshape(2, 4).tolist() == [[5.0, 0.0, 0.0, 7.0], [0.0, 0.0, 0.0, 0.0]]
+
+
+@pytest.mark.parametrize('B,HW,C,oc', [(3, 7, 8, 3), (2, 5, 4, 2), (1, 3, 8, 1), (2, 4, 8, 4)])
+def test_output_conv_restatement_matches_autograd(B, HW, C, oc):
+    """nn.Conv2d(C, oc, 1) on relu(a y + b), loss = 0.5 gscale sum (out - tgt)^2: out, score, d loss / d out, and the gradients with
+    respect to the activation, the weight and the bias; the BatchNorm-backward sums against their definition on the autograd dA."""
+    g = torch.Generator().manual_seed(B * 1000 + HW * 10 + oc)
+    conv = torch.nn.Conv2d(C, oc, 1).double()
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(oc, C, 1, 1, generator=g, dtype=F64))
+        conv.bias.copy_(torch.randn(oc, generator=g, dtype=F64))
+    y = torch.randn(B, HW, C, generator=g, dtype=F64)
+    a, b = torch.rand(C, generator=g, dtype=F64) + 0.5, torch.randn(C, generator=g, dtype=F64) * 0.3
+    mean, invstd = torch.randn(C, generator=g, dtype=F64) * 0.1, torch.rand(C, generator=g, dtype=F64) + 0.5
+    tgt = torch.randn(B, HW, oc, generator=g, dtype=F64)
+    gscale = 0.37
+    v = R.act_in(y, a, b).requires_grad_(True)
+    out = conv(v.permute(0, 2, 1)[..., None])[..., 0].permute(0, 2, 1)          # [B, HW, oc]
+    (0.5 * gscale * ((out - tgt) ** 2).sum()).backward()
+    w, bias = conv.weight.detach()[:, :, 0, 0], conv.bias.detach()
+    out4, score, dout4 = R.outconv_forward(y, a, b, w, bias, oc, tgt, gscale)
+    _close(out4[..., :oc], out.detach())
+    _close(score, ((out.detach() - tgt) ** 2).sum((1, 2)))
+    _close(dout4[..., :oc], gscale * (out.detach() - tgt))
+    assert out4[..., oc:].abs().sum().item() == 0.0 and dout4[..., oc:].abs().sum().item() == 0.0
+    dA, dWc, dbc, dW, db, s1, s2 = R.outconv_backward(dout4, y, a, b, w, mean, invstd)
+    _close(dA, v.grad)
+    _close(dW[:oc], conv.weight.grad[:, :, 0, 0])
+    _close(db[:oc], conv.bias.grad)
+    _close(dWc.sum(0), dW)
+    _close(dbc.sum(0), db)
+    assert dWc[:, oc:].abs().sum().item() == 0.0 and dbc[:, oc:].abs().sum().item() == 0.0
+    gate = (v.detach() > 0).double()
+    _close(s1, (v.grad * gate).sum(1))
+    _close(s2, (v.grad * gate * (y - mean) * invstd).sum(1))
+    # dA_stored replaces the dA of the sums only
+    st = dA + 0.25
+    r2 = R.outconv_backward(dout4, y, a, b, w, mean, invstd, dA_stored=st)
+    assert torch.equal(r2[0], dA) and torch.equal(r2[1], dWc)
+    _close(r2[5], (st * gate).sum(1))
+    _close(r2[6], (st * gate * (y - mean) * invstd).sum(1))
+
+
+@pytest.mark.parametrize('Cin,Cout', [(3, 5), (4, 2)])
+def test_fold_bn_restatement_matches_conv_then_eval_batchnorm(Cin, Cout):
+    """nn.Conv2d(k3, p1) -> nn.BatchNorm2d.eval() equals the convolution with the folded filter and bias (running_var down to 1e-6)"""
+    g = torch.Generator().manual_seed(Cin * 10 + Cout)
+    conv = torch.nn.Conv2d(Cin, Cout, 3, padding=1).double()
+    bn = torch.nn.BatchNorm2d(Cout, eps=1e-5).double().eval()
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(Cout, Cin, 3, 3, generator=g, dtype=F64))
+        conv.bias.copy_(torch.randn(Cout, generator=g, dtype=F64))
+        bn.weight.copy_(torch.rand(Cout, generator=g, dtype=F64) + 0.5)
+        bn.bias.copy_(torch.randn(Cout, generator=g, dtype=F64))
+        bn.running_mean.copy_(torch.randn(Cout, generator=g, dtype=F64))
+        bn.running_var.copy_(10.0 ** (-6 * torch.rand(Cout, generator=g, dtype=F64)))
+        bn.running_var[0] = 1e-6
+        x = torch.randn(2, Cin, 5, 4, generator=g, dtype=F64)
+        ref = bn(conv(x))
+        wf, bf = R.fold_bn(conv.weight.reshape(Cout, -1), conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, 1e-5)
+        _close(torch.nn.functional.conv2d(x, wf.view(Cout, Cin, 3, 3), bf, padding=1), ref)
 
 
 def test_adam_restatement_matches_torch_optimizer():

@@ -1,9 +1,10 @@
-"""Plain torch / numpy restatements of the operations a train step of the UNet bank runs besides its 3x3 convolutions, one function
-per operation, written from the operation's definition and not from the HIP kernels (vec_vad_amd/csrc/vv_conv.hip, vv_wgrad.hip,
-vv_elem.hip).  Every function computes in the dtype of its arguments: float64 tensors give the reference of tests/test_gpu_train_ops.py,
-the same call on float32 tensors gives the "plain float32 evaluation" those tests measure the kernels' round-off against.
+"""Plain torch / numpy restatements of the operations a train step of the UNet bank runs besides its 3x3 convolutions (and of the
+eval-mode BatchNorm folding), one function per operation, written from the operation's definition and not from the HIP kernels (vec_vad_amd/csrc/vv_conv.hip, vv_wgrad.hip,
+vv_elem.hip).  Every function computes in the dtype of its arguments: float64 tensors give the reference of tests/test_gpu_train_ops.py
+and tests/test_gpu_outconv.py, the same call on float32 tensors gives the "plain float32 evaluation" those tests measure the kernels' round-off against.
 tests/test_train_ops_host.py checks each function in float64 against torch autograd of the nn modules the reference model uses
-(model/unet.py: nn.ConvTranspose2d(k3, s2, p1, op1), nn.BatchNorm2d -> nn.ReLU -> nn.MaxPool2d(2); train.py: torch.optim.Adam(eps=1e-7)).
+(model/unet.py: nn.ConvTranspose2d(k3, s2, p1, op1), nn.BatchNorm2d -> nn.ReLU -> nn.MaxPool2d(2), nn.Conv2d(C, oc, 1); train.py:
+torch.optim.Adam(eps=1e-7)).
 
 Activations are NHWC ([B, H, W, C]) as the kernels store them; filters keep the PyTorch parameter layouts.
 """
@@ -110,6 +111,48 @@ def bn_relu_pool_backward(y, a, b, mean, invstd, gamma, dA, dpool=None):
     n = y.shape[0] * y.shape[1] * y.shape[2]
     dy = gamma * invstd * (dz - dbeta / n - xhat * (dgamma / n))
     return dy, dgamma, dbeta, dz
+
+
+# ---------------------------------------------------------------------------------------------- output conv, nn.Conv2d(C, oc, 1)
+# (include/vecvad_hip.h, vv_outconv_params) one group: y [B, HW, C] = the conv output in front of the last BatchNorm, w [oc, C],
+# bias [oc], tgt [B, HW, oc] = the target channels of this group; four output channels are stored, those >= oc are 0
+
+def outconv_forward(y, a, b, w, bias, oc, tgt, gscale):
+    """v = relu(a y + b); out[p][co] = bias[co] + sum_c v[p][c] W[co][c]; score[cube] = sum (out - tgt)^2; dout = gscale (out - tgt)
+    -> out4 [B, HW, 4], score [B], dout4 [B, HW, 4]"""
+    v = act_in(y, a, b)
+    out = v @ w[:oc].t() + bias[:oc]
+    e = out - tgt[..., :oc]
+    out4, dout4 = y.new_zeros(y.shape[:-1] + (4,)), y.new_zeros(y.shape[:-1] + (4,))
+    out4[..., :oc] = out
+    dout4[..., :oc] = gscale * e
+    return out4, (e * e).sum((1, 2)), dout4
+
+
+def outconv_backward(dout4, y, a, b, w, mean, invstd, dA_stored=None):
+    """dout4 [B, HW, 4] (channels >= oc = w.shape[0] are not read) -> dA [B, HW, C] = sum_co dout[co] W[co]; per cube dW [B, 4, C] =
+    sum_p dout[p][co] v[p][c] and db [B, 4] = sum_p dout[p][co] (rows >= oc zero); their sums over the cubes [4, C], [4]; per cube the
+    BatchNorm-backward sums [B, C] of g = dA [v > 0] and of g xhat, xhat = (y - mean) invstd -- of dA_stored where given (what a
+    kernel stored, a bf16 rounding for instance) instead of the dA formed here"""
+    oc = w.shape[0]
+    v = act_in(y, a, b)
+    d = dout4[..., :oc]
+    dA = d @ w
+    dWc, dbc = y.new_zeros(y.shape[0], 4, y.shape[-1]), y.new_zeros(y.shape[0], 4)
+    dWc[:, :oc] = d.transpose(1, 2) @ v
+    dbc[:, :oc] = d.sum(1)
+    g = (dA if dA_stored is None else dA_stored) * (v > 0).to(y.dtype)
+    xhat = (y - mean) * invstd
+    return dA, dWc, dbc, dWc.sum(0), dbc.sum(0), g.sum(1), (g * xhat).sum(1)
+
+
+# ---------------------------------------------------------------------------------------------- eval mode: BatchNorm folded into the conv
+
+def fold_bn(w, bias, gamma, beta, running_mean, running_var, eps):
+    """w [Cout, row] (row = Cin * 9 filter elements per output channel), the rest [Cout]; a = gamma / sqrt(running_var + eps)
+    -> a[c] w[c][k],  a[c] (bias[c] - running_mean[c]) + beta[c]"""
+    a = gamma / torch.sqrt(running_var + eps)
+    return a[:, None] * w, a * (bias - running_mean) + beta
 
 
 # ---------------------------------------------------------------------------------------------- Adam, torch.optim.Adam(eps=1e-7)
