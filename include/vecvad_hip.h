@@ -614,6 +614,35 @@ int vv_pixel_scores(const uint8_t* gt, const double* scores, const int32_t* fram
                     double big, int32_t n_frames, int32_t h, int32_t w, int32_t max_boxes, double* out, int32_t* gt_count,
                     vv_stream stream);
 
+/* ---- per-pixel anomaly maps (where inside a box the anomaly lies: the per-pixel squared error the cube score is the sum of) ----
+ * vv_error_maps: e_raw[b][p] = sum over the UNets g with tgt_src[g] == 0, in ascending g, of sum over c < oc[g], in ascending c, of
+ *   (out4[g][b*HW+p][c] - tgt0[(b*HW+p)*tgt0_cstride + tgt_coff[g] + c])^2 in fp32; e_of the same over tgt_src[g] == 1 and tgt1.
+ *   out4 [G][B*HW][4], 16-byte aligned, is the reconstruction vv_outconv_fwd stores when vv_outconv_params.out4 != NULL; oc, tgt_src,
+ *   tgt_coff, tgt0 / tgt1 and their channel strides are the fields of vv_outconv_params of the same names.  e_raw, e_of: float
+ *   [B][HW]; e_of == NULL (tgt1 may then be NULL too) skips the flow UNets.  The sum of e_raw[b] over p is the raw score of cube b
+ *   up to the order of the fp32 sum.  One thread per pixel, one streaming pass, no atomics: bit-identical run to run.
+ * vv_error_zmaps: out[m][q] = the score vv_cube_scores forms (the same device function) with 1024 * e_raw[m][q] (1024 * e_of[m][q])
+ *   in place of the cube's raw (flow) error, q < 1024 pixels of the 32x32 patch: cube_stat[m] < 0 ? big : w_raw*((double)(1024*e_raw)
+ *   - mu_r)/sd_r [+ ...].  A cube whose error is spread evenly over its pixels gets the constant map out[m][q] = its cube score, to the
+ *   bit.  e_raw, e_of (NULL drops the flow term): float [n][1024]; out double [n][1024] (8 KB per cube).
+ * vv_paint_zmaps: vv_paint_masks with a value that varies inside the rectangle: out[f][y][x] = max(out[f][y][x], z[m][py*32+px]) for
+ *   every cube m of frame f whose rectangle (y0, y1, x0, x1) holds (y, x), with py = ((2*(y-y0)+1)*32) / (2*(y1-y0)) and px likewise
+ *   in integer arithmetic (nearest source pixel; 0..31; the identity for a rectangle 32 wide).  z double [n][1024]; everything else as
+ *   for vv_paint_masks, any number of boxes per frame, no atomics.  h * w < 2^25 - 512.
+ * vv_mask_kth: vv_pixel_scores on formed masks (double [n_frames][h][w]): gt_count[f] = |G|; out[f] = the k-th largest value of
+ *   masks[f] over G, k = (|G| * pct + 99) / 100, when |G| > 0, else the maximum of masks[f] (-big for a frame of no pixels).  Exact:
+ *   a radix select on the order-preserving integer image of the doubles with integer LDS histograms, one workgroup per frame;
+ *   bit-identical run to run and independent of ties.  NaN mask values are outside the domain. */
+int vv_error_maps(int32_t G, int32_t B, int32_t HW, const float* out4, const int32_t* oc, const int32_t* tgt_src,
+                  const int32_t* tgt_coff, const float* tgt0, int32_t tgt0_cstride, const float* tgt1, int32_t tgt1_cstride,
+                  float* e_raw, float* e_of, vv_stream stream);
+int vv_error_zmaps(const float* e_raw, const float* e_of, const int32_t* cube_stat, const double* stats, double w_raw, double w_of,
+                   double big, int32_t n, double* out, vv_stream stream);
+int vv_paint_zmaps(const double* z, const int32_t* frame_off, const int32_t* rects, int32_t n_frames, int32_t h, int32_t w,
+                   double* out, vv_stream stream);
+int vv_mask_kth(const uint8_t* gt, const double* masks, int32_t pct, double big, int32_t n_frames, int32_t h, int32_t w,
+                double* out, int32_t* gt_count, vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

@@ -28,6 +28,13 @@ the reference never evaluates (test.py:362-365 ``criterion = 'frame'``): per fra
 on the GPU from the device-resident cube scores and the per-pixel ground truth, ``results/<ds>/pixel_scores_<fg>_<method>.npy``
 and ``<modality>_<fg>_<method>_pixel_results.npz``.  ``[mi355x] device_score_masks = True`` paints the ``score_mask`` files on the
 GPU (``scoring.paint_masks``) instead of the numpy loop over boxes; the same files.
+
+``[mi355x] pixel_maps = True`` (default False) keeps the per-pixel reconstruction error of every scored cube on the device, paints it
+back into the frame through the cube's rectangle (``scoring.error_zmaps`` + ``scoring.paint_error_masks``: fine masks that say where
+inside a box the anomaly lies, with the support of the ``score_mask`` files) and saves them as ``results/<ds>/error_mask/<frame>``
+when ``save_score_masks`` is on; with ``pixel_criterion`` the same criterion is also evaluated on the fine masks
+(``scoring.mask_pixel_scores``): ``pixel_scores_fine_<fg>_<method>.npy`` and ``<modality>_<fg>_<method>_pixel_fine_results.npz``.
+Everything else -- frame scores, ``score_mask`` files, pixel scores -- is what a run without the key writes.
 """
 import os
 import sys
@@ -81,18 +88,18 @@ def load_artifacts(base, fg, method, shanghai, build_net, device, h_block=1, w_b
     return over(build, weights, weights, depth), over(stat, raw_tr, weights, depth), over(stat, of_tr, weights, depth)
 
 
-def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=None):
+def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=None, maps=False):
     """cube_list / flow_list: per-frame arrays [n_i,5,32,32,3] uint8 / [n_i,(Tf,)32,32,2] fp32 (n_i may be 0).
     The cubes go to the GPU in bounded super-chunks (``chunk_cubes``, default 32 launches' worth, >= 4096: ~55 KB per cube for the
     5raw+5of bank, so host and device staging stay at a few hundred MB whatever the size of the test set) through ONE fixed device
     staging buffer, and every chunk is scored by ``score_index_list`` in launches of exactly ``score_batch`` cubes (the tail launch
     re-scores the chunk's last cube as padding: eval-mode scores do not depend on the batch) -- one workspace, one launch plan and
     one captured hipGraph serve the whole test set.  Returns the DEVICE tensors (raw [n], of [n] | None) of all cubes in frame order -- they feed
-    vv_frame_scores without visiting the host."""
+    vv_frame_scores without visiting the host.  ``maps``: also the per-pixel error maps (e_raw [n,32,32], e_of [n,32,32] | None) behind them."""
     dev = trainer.bank.device
     keep = [k for k in range(len(cube_list)) if len(cube_list[k])]
     if not keep:
-        return torch.zeros(0, device=dev), None
+        return (torch.zeros(0, device=dev), None) + ((torch.zeros((0, 32, 32), device=dev), None) if maps else ())
     counts = [len(cube_list[k]) for k in keep]
     n = int(sum(counts))
     B = int(min(score_batch, n)) if n < score_batch else int(score_batch)
@@ -111,19 +118,26 @@ def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=N
     flowd = torch.empty((cap,) + f0.shape[1:], dtype=torch.float32, device=dev)
     r_all = torch.empty(n, device=dev)
     o_all = None
+    er_all, eo_all = torch.empty((n, 32, 32), device=dev) if maps else None, None
     done = 0
     pend_r, pend_f, pend_n = [], [], 0
 
     def flush():
-        nonlocal done, pend_r, pend_f, pend_n, o_all
+        nonlocal done, pend_r, pend_f, pend_n, o_all, eo_all
         m_tot = pend_n
         if not m_tot:
             return
         rawd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_r))))
         flowd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_f))))
         # launches of B cubes whatever the chunk holds: B comes from the whole list, and the bank picks its kernels by it
-        r, o = score_index_list(trainer, rawd, flowd, torch.arange(m_tot, device=dev), score_batch, batch=B)
+        r, o, *e = score_index_list(trainer, rawd, flowd, torch.arange(m_tot, device=dev), score_batch, batch=B, maps=maps)
         r_all[done:done + m_tot] = r
+        if maps:
+            er_all[done:done + m_tot] = e[0]
+            if e[1] is not None:
+                if eo_all is None:
+                    eo_all = torch.empty((n, 32, 32), device=dev)
+                eo_all[done:done + m_tot] = e[1]
         if o is not None:
             if o_all is None:
                 o_all = torch.empty(n, device=dev)
@@ -143,7 +157,7 @@ def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=N
             if pend_n == cap:
                 flush()
     flush()
-    return r_all, o_all
+    return (r_all, o_all, er_all, eo_all) if maps else (r_all, o_all)
 
 
 def score_cubes_batched(trainer, cube_list, flow_list, score_batch):
@@ -200,25 +214,37 @@ class PixelEval:
     source (``foreground.gt_source``: ``gt(i)`` -> uint8 ``[h,w]``) or None for no pixel criterion; ``percent``: the overlap in
     integer percent; ``out``: CUDA float64 ``[n_frames]`` that receives the pixel scores of the frames a call covers; ``labels``:
     the frame labels (bool ``[n_frames]``) the ground-truth pixel counts are checked against, or None; ``device_masks``: paint the
-    ``result_dir`` masks on the GPU; ``frames_per_chunk``: frames per ground-truth upload / mask download."""
+    ``result_dir`` masks on the GPU; ``frames_per_chunk``: frames per ground-truth upload / mask download.  ``maps`` (``[mi355x]
+    pixel_maps``): the per-pixel error maps of every scored cube are kept and painted into fine masks, saved per frame under
+    ``error_dir`` when one is given and, with a ground-truth source, reduced to ``out_fine`` (CUDA float64 ``[n_frames]``) like ``out``."""
 
-    def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64):
+    def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64, maps=False, error_dir=None,
+                 out_fine=None):
         self.gt, self.percent, self.out, self.labels = gt, int(percent), out, labels
         self.device_masks, self.frames_per_chunk = bool(device_masks), max(1, int(frames_per_chunk))
+        self.maps, self.error_dir, self.out_fine = bool(maps), error_dir, out_fine
         if gt is not None and out is None:
             raise ValueError('PixelEval: a ground-truth source needs an `out` vector for the pixel scores')
+        if self.maps and gt is not None and out_fine is None:
+            raise ValueError('PixelEval: maps with a ground-truth source need an `out_fine` vector for the fine pixel scores')
 
 
-def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device):
+def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_groups=None):
     """Frames ``[first, end)`` of the scored groups ``dev_groups`` ((off, device cube scores, device rectangles) each) in chunks:
     the chunk's cubes are merged into frame order and reduced to pixel scores against the chunk's ground truth (uploaded once),
-    and / or its masks are painted on the device, group by group, brought to the host once and saved per frame."""
+    and / or its masks are painted on the device, group by group, brought to the host once and saved per frame.  ``map_groups``
+    (``pixel.maps``; one entry per group of ``dev_groups``: None for a block without a model, else (e_raw, e_of, stats, w_raw, w_of)):
+    the chunk's z-maps are formed and painted group by group into one fine-mask buffer, which is saved per frame under
+    ``pixel.error_dir`` and / or reduced to ``pixel.out_fine`` against the same ground truth."""
     paint = pixel.device_masks and result_dir
     if paint:
         os.makedirs(result_dir, exist_ok=True)
+    if map_groups is not None and pixel.error_dir:
+        os.makedirs(pixel.error_dir, exist_ok=True)
     for a in range(first, end, pixel.frames_per_chunk):
         b = min(a + pixel.frames_per_chunk, end)
         sub = [(off[a:b + 1], sc, rc) for off, sc, rc in dev_groups]
+        gt = None
         if pixel.gt is not None:
             off, sc, rc = scoring.merge_groups(sub, n_frames=b - a, device=device)
             gt = torch.from_numpy(np.stack([pixel.gt(i) for i in range(a, b)])).to(device)
@@ -236,14 +262,36 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device):
             masks = masks.cpu().numpy()
             for f in range(a, b):
                 torch.save(masks[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))      # its own array, as _save_masks saves
+        if map_groups is not None:
+            fine = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
+            for (off, _, rc), kept in zip(sub, map_groups):
+                lo, hi = int(off[0]), int(off[-1])
+                if hi <= lo:
+                    continue
+                if kept is None:     # a block without a model: BIG all over the box, as in the painted mask
+                    z = torch.full((hi - lo, 32, 32), float(BIG), dtype=torch.float64, device=device)
+                else:
+                    e_raw, e_of, stats, w_raw, w_of = kept
+                    z = scoring.error_zmaps(e_raw[lo:hi], e_of[lo:hi] if e_of is not None else None, np.zeros(hi - lo, np.int32), stats,
+                                            w_raw, w_of)
+                scoring.paint_error_masks(z, off - lo, rc[lo:hi], h, w, out=fine)
+                del z
+            if gt is not None:
+                scoring.mask_pixel_scores(gt, fine, pixel.percent, out=pixel.out_fine[a:b])
+            if pixel.error_dir:
+                fine = fine.cpu().numpy()
+                for f in range(a, b):
+                    torch.save(fine[f - a].copy(), os.path.join(pixel.error_dir, '{}'.format(f)))
 
 
-def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups, dev_groups=None):
+def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups, dev_groups=None,
+                  map_groups=None):
     """The per-group body of ``score_frames`` and ``score_store``.  The returned ``group(key, hh, ww, n, off, boxes, score)`` scores
     the ``n`` cubes of block ``(hh, ww)`` (of scene ``key``, or None) with ``score(trainer)`` -> device (raw [n], of [n] | None),
     max-accumulates their frame scores into ``fs_dev`` (``off``: CSR over the frames, ``boxes`` float64 ``[n,4]``) and, when
     ``mask_groups`` is a list, appends the group's (off, host cube scores, boxes) for ``_save_masks``; when ``dev_groups`` is a list,
-    the group's (off, device cube scores, device rectangles) for ``_pixel_stage``."""
+    the group's (off, device cube scores, device rectangles) for ``_pixel_stage``; when ``map_groups`` is a list, ``score(trainer)`` also
+    returns the per-pixel error maps (e_raw, e_of | None) and the group's entry for ``_pixel_stage`` is appended next to them."""
     def group(key, hh, ww, n, off, boxes, score):
         def pick(nested):
             return nested[key][hh][ww] if key is not None else nested[hh][ww]
@@ -254,12 +302,12 @@ def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, devi
                 trainers[id(net)] = FusedTrainer(net)
             st_r = pick(stats_raw)
             st_o = pick(stats_of) if useFlow else (0.0, 1.0)
-            r, o = score(trainers[id(net)])
+            r, o, *e = score(trainers[id(net)])
             o = o if useFlow else None
             stats = np.array([[st_r[0], st_r[1], st_o[0], st_o[1]]], np.float64)
             cube_stat = np.zeros(n, np.int32)
         else:        # anomaly: no object in the training set in this block (test.py:346-348)
-            r, o = torch.zeros(n, device=device), None
+            r, o, e = torch.zeros(n, device=device), None, None
             stats = np.array([[0.0, 1.0, 0.0, 1.0]])
             cube_stat = np.full(n, -1, np.int32)
         scoring.frame_scores(r, o, off, cube_stat, stats, scoring.box_paints(boxes, h, w), w_raw, w_of, out=fs_dev)
@@ -268,14 +316,18 @@ def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, devi
         if dev_groups is not None:
             dev_groups.append((off, scoring.cube_scores(r, o, cube_stat, stats, w_raw, w_of),
                                torch.from_numpy(scoring.box_rects(boxes, h, w)).to(device)))
+        if map_groups is not None:
+            map_groups.append(None if e is None else (e[0], e[1] if useFlow else None, stats, w_raw, w_of))
     return group
 
 
 def _mask_lists(result_dir, pixel):
-    """(mask_groups, dev_groups) for a call: the host list feeds ``_save_masks``, the device list ``_pixel_stage``."""
+    """(mask_groups, dev_groups, map_groups) for a call: the host list feeds ``_save_masks``, the device lists ``_pixel_stage``."""
     device_masks = pixel is not None and pixel.device_masks
+    maps = pixel is not None and pixel.maps and (pixel.gt is not None or bool(pixel.error_dir))
     return ([] if result_dir and not device_masks else None,
-            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir)) else None)
+            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir) or maps) else None,
+            [] if maps else None)
 
 
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
@@ -291,10 +343,12 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
     the device; with a ground-truth source the pixel scores of all frames go to ``pixel.out``, and with ``pixel.device_masks`` the
     ``result_dir`` masks are painted on the GPU (same files) and no per-cube score visits the host."""
     n_frames = len(foreground_set)
-    mask_groups, dev_groups = _mask_lists(result_dir, pixel)      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
+    mask_groups, dev_groups, map_groups = _mask_lists(result_dir, pixel)      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
+    maps = map_groups is not None
     fs_dev = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
     hb, wb = len(foreground_set[0]), len(foreground_set[0][0])
-    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups, dev_groups)
+    group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups, dev_groups,
+                          map_groups)
     keys = sorted(set(scene_idx[f] - 1 for f in range(n_frames))) if scene_idx is not None else [None]
     for hh in range(hb):
         for ww in range(wb):
@@ -309,36 +363,45 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
                 boxes = np.concatenate([np.asarray(bbox_set[f][hh][ww], dtype=np.float64)[:, :4] for f in frames])
                 off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)      # indexed by frame: cubes of frame f = [off[f], off[f+1])
                 group(key, hh, ww, int(off[-1]), off, boxes, lambda tr: score_cubes_device(
-                    tr, [foreground_set[f][hh][ww] for f in frames], [foreground_set2[f][hh][ww] for f in frames], score_batch))
+                    tr, [foreground_set[f][hh][ww] for f in frames], [foreground_set2[f][hh][ww] for f in frames], score_batch,
+                    maps=maps))
     if mask_groups is not None:
         _save_masks(result_dir, range(n_frames), mask_groups, h, w)
     if dev_groups is not None:
-        _pixel_stage(pixel, dev_groups, 0, n_frames, h, w, result_dir, device)
+        _pixel_stage(pixel, dev_groups, 0, n_frames, h, w, result_dir, device, map_groups)
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
-def score_index_list(trainer, raw_store, flow_store, idx, score_batch, batch=None):
+def score_index_list(trainer, raw_store, flow_store, idx, score_batch, batch=None, maps=False):
     """Scores of the store cubes named by ``idx`` (int64 ``[n]``, numpy or device tensor, n > 0, repeats allowed): THE launch loop
     of the test stage.  Launches of exactly ``batch`` cubes -- default: ``score_batch``, or ``n`` when the list is shorter than one
     launch; ``score_cubes_device`` passes the size it derived from its whole list for every chunk --, the tail launch padded by
-    repeating the last index.  Returns the DEVICE tensors (raw [n], of [n] | None) in list order."""
+    repeating the last index.  Returns the DEVICE tensors (raw [n], of [n] | None) in list order; with ``maps`` also the per-pixel
+    error maps (e_raw [n,32,32], e_of [n,32,32] | None) of the same cubes -- the padding of the tail launch is dropped from all four."""
     dev = trainer.bank.device
     n = len(idx)
     B = int(batch) if batch is not None else (n if n < score_batch else int(score_batch))
     idx_d = (idx if torch.is_tensor(idx) else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))).to(dev)
     r_all, o_all = torch.empty(n, device=dev), None
+    er_all, eo_all = torch.empty((n, 32, 32), device=dev) if maps else None, None
     for s0 in range(0, n, B):
         m = min(B, n - s0)
         sel = idx_d[s0:s0 + m]
         if m < B:
             sel = torch.cat([sel, sel[-1:].expand(B - m)])
-        r, o = trainer.score_cubes(raw_store, flow_store, sel)
+        r, o, *e = trainer.score_cubes(raw_store, flow_store, sel, maps=True) if maps else trainer.score_cubes(raw_store, flow_store, sel)
         r_all[s0:s0 + m] = r[:m]
         if o is not None:
             if o_all is None:
                 o_all = torch.empty(n, device=dev)
             o_all[s0:s0 + m] = o[:m]
-    return r_all, o_all
+        if maps:
+            er_all[s0:s0 + m] = e[0][:m]
+            if e[1] is not None:
+                if eo_all is None:
+                    eo_all = torch.empty((n, 32, 32), device=dev)
+                eo_all[s0:s0 + m] = e[1][:m]
+    return (r_all, o_all, er_all, eo_all) if maps else (r_all, o_all)
 
 
 def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw, w_of, useFlow, device, score_batch=2048,
@@ -365,20 +428,21 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
     else:
         raise ValueError('score_store: no group, no out and no frame_range to tell the number of frames')
     fs_dev = out if out is not None else torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
-    mask_groups, dev_groups = _mask_lists(result_dir, pixel)
+    mask_groups, dev_groups, map_groups = _mask_lists(result_dir, pixel)
+    maps = map_groups is not None
     group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {} if trainers is None else trainers,
-                          fs_dev, mask_groups, dev_groups)
+                          fs_dev, mask_groups, dev_groups, map_groups)
     for gk in sorted(groups, key=lambda k: (k[1], k[2], -1 if k[0] is None else k[0])):
         if (gk[0] is None) != (scene_idx is None):
             raise ValueError('group %r does not fit scene_idx %s' % (gk, 'given' if scene_idx is not None else 'absent'))
         idx, off = groups[gk]
         if len(idx):
-            group(*gk, len(idx), off, boxes[idx], lambda tr: score_index_list(tr, raw_store, flow_store, idx, score_batch))
+            group(*gk, len(idx), off, boxes[idx], lambda tr: score_index_list(tr, raw_store, flow_store, idx, score_batch, maps=maps))
     first, end = frame_range if frame_range is not None else (0, n_frames)
     if mask_groups is not None:
         _save_masks(result_dir, range(first, end), mask_groups, h, w)
     if dev_groups is not None:
-        _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device)
+        _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_groups)
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -429,23 +493,32 @@ def main(config_path='config.cfg', flownet2=None):
     shanghai = ds == 'ShanghaiTech'
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
     pixel_scores_path = os.path.join(results_dir, ds, 'pixel_scores_{}_{}.npy'.format(fg, method))
-    ps = None
+    fine_scores_path = os.path.join(results_dir, ds, 'pixel_scores_fine_{}_{}.npy'.format(fg, method))
+    ps = ps_fine = None
     if cp.getboolean(ds, 'scores_saved'):
         fs = np.load(frame_scores_path)
         if c['pixel_criterion']:
             ps = np.load(pixel_scores_path)
+            if c['pixel_maps']:
+                ps_fine = np.load(fine_scores_path)
     else:
         mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
+        error_dir = os.path.join(results_dir, ds, 'error_mask') if c['save_score_masks'] and c['pixel_maps'] else None
+        maps = c['pixel_maps'] and (error_dir is not None or gt is not None)      # neither a file nor a score to form them for: off
         made = []
 
         def pixel_eval(n_frames, labels):
             """The ``pixel`` keyword of the scoring calls, or None with both new keys off (today's calls)."""
-            if gt is None and not (c['device_score_masks'] and mask_dir):
+            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps:
                 return None
             if gt is not None and len(gt) != n_frames:
                 raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
             out = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device) if gt is not None else None
-            made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk']))
+            if not maps:
+                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk']))
+            else:
+                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
+                                      maps=True, error_dir=error_dir, out_fine=out.clone() if gt is not None else None))
             return made[0]
 
         if direct:
@@ -465,6 +538,9 @@ def main(config_path='config.cfg', flownet2=None):
         if gt is not None:
             ps = made[0].out.cpu().numpy()
             np.save(pixel_scores_path, ps)
+            if made[0].maps:
+                ps_fine = made[0].out_fine.cpu().numpy()
+                np.save(fine_scores_path, ps_fine)
 
     # ---- evaluation (test.py:362-399), criterion = 'frame'
     lab_path = base + 'frame_labels_test.npy'
@@ -498,6 +574,14 @@ def main(config_path='config.cfg', flownet2=None):
         print('Pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], pixel_auc))
         print('Pixel-level AUC@ROC (device pair count) is {}'.format(
             scoring.roc_auc(torch.from_numpy(np.asarray(ps, np.float64)).to(device), labels)))
+    if ps_fine is not None:
+        # ---- the same criterion on the fine masks ([mi355x] pixel_maps)
+        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_fine_results.npz'.format(mod, fg, method))
+        print('Results written to {}:'.format(path))
+        fine_auc = save_roc_pr_curve_data(ps_fine, labels, path)
+        print('Fine pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], fine_auc))
+        print('Fine pixel-level AUC@ROC (device pair count) is {}'.format(
+            scoring.roc_auc(torch.from_numpy(np.asarray(ps_fine, np.float64)).to(device), labels)))
     return auc
 
 

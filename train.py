@@ -111,7 +111,8 @@ def read_config(path='config.cfg'):
              flownet2_checkpoint=cp.get('mi355x', 'flownet2_checkpoint', fallback=None),
              pixel_criterion=cp.getboolean('mi355x', 'pixel_criterion', fallback=False),
              pixel_overlap_percent=cp.getint('mi355x', 'pixel_overlap_percent', fallback=40),
-             device_score_masks=cp.getboolean('mi355x', 'device_score_masks', fallback=False))
+             device_score_masks=cp.getboolean('mi355x', 'device_score_masks', fallback=False),
+             pixel_maps=cp.getboolean('mi355x', 'pixel_maps', fallback=False))
     if not 1 <= c['pixel_overlap_percent'] <= 100:
         raise ValueError('[mi355x] pixel_overlap_percent must be an integer in 1..100, got {}'.format(c['pixel_overlap_percent']))
     if c['flownet2_checkpoint'] is None:

@@ -176,6 +176,10 @@ _SIGS = {
     'vv_cube_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
     'vv_paint_masks': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'vv_pixel_scores': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'vv_error_maps': (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'vv_error_zmaps': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
+    'vv_paint_zmaps': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'vv_mask_kth': (c_i32, [c_vp, c_vp, c_i32, c_f64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
     'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),

@@ -1170,11 +1170,29 @@ class UNetBank:
                                           self.adam_m.data_ptr(), self.adam_v.data_ptr(), self._adam_sc.data_ptr(), beta1, beta2,
                                           eps, grad_scale, st), 'adam')
 
-    def outputs_nchw(self, ws):
-        """(of_out [B,2*n_of,32,32], raw_out [B,3*n_raw,32,32]) in the reference's channel order."""
+    @staticmethod
+    def _need_out4(ws):
         if not getattr(ws, 'out4_valid', False):
             raise RuntimeError('the last forward on this workspace did not store the reconstructions (fused train / scoring steps skip '
                                'that store): use forward(ws, train, outputs=True) or FusedTrainer.keep_outputs = True')
+
+    def error_maps(self, ws):
+        """(e_raw [B,32,32], e_of [B,32,32] | None): the per-pixel squared reconstruction error of the last forward on ``ws``, summed
+        over the raw / flow UNets and their channels (vv_error_maps) -- what ``cube_scores`` holds summed over the patch as well.
+        Needs the stored reconstructions (``forward(ws, train, outputs=True)``); fresh tensors, the caller's own."""
+        self._need_out4(ws)
+        B, HWp = ws.B, HW0 * HW0
+        e_raw = torch.empty(B, HW0, HW0, device=self.device)
+        e_of = torch.empty(B, HW0, HW0, device=self.device) if ws.n_of else None
+        L.check(self.lib.vv_error_maps(self.Ga, B, HWp, ws.out4.data_ptr(), self._p(self.oc, self.g0), self._p(self.tsrc, self.g0),
+                                       self._p(self.tcoff, self.g0), ws.cube.data_ptr(), ws.cube.shape[2],
+                                       ws.flow.data_ptr() if ws.n_of else None, ws.flow.shape[2],
+                                       e_raw.data_ptr(), e_of.data_ptr() if e_of is not None else None, self._stream()), 'error_maps')
+        return e_raw, e_of
+
+    def outputs_nchw(self, ws):
+        """(of_out [B,2*n_of,32,32], raw_out [B,3*n_raw,32,32]) in the reference's channel order."""
+        self._need_out4(ws)
         B, HWp = ws.B, HW0 * HW0
         units = self.units[self.g0:self.g0 + self.Ga]
         raw_o = torch.empty(B, RAW_C * ws.n_raw, HW0, HW0, device=self.device)

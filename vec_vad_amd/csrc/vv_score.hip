@@ -260,6 +260,152 @@ __global__ void __launch_bounds__(256) auc_count_kernel(const double* __restrict
   }
 }
 
+// ---- per-pixel anomaly maps: the per-pixel errors of vv_error_maps -> z-maps -> fine masks -> the pixel criterion on a formed mask --
+// z[m][q] = cube_score with 1024 * e[m][q] in place of the cube's error (a 32x32 patch: the cube's error is the sum of its 1024 pixel
+// errors, so a cube whose error is spread evenly gets the constant map z = its cube score, to the bit; the scaling by 2^10 is exact).
+constexpr int ZMAP_PIX = 1024;               // pixels of a patch (32 x 32)
+constexpr int ZMAP_SIDE = 32;
+
+__global__ void __launch_bounds__(256) error_zmap_kernel(const float* __restrict__ e_raw, const float* __restrict__ e_of,
+                                                         const int32_t* __restrict__ cube_stat, const double* __restrict__ stats,
+                                                         double w_raw, double w_of, double big, int64_t total,
+                                                         double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const float r = 1024.f * e_raw[i];
+  const float o = e_of ? 1024.f * e_of[i] : 0.f;
+  out[i] = cube_score(&r, e_of ? &o : nullptr, cube_stat + i / ZMAP_PIX, stats, w_raw, w_of, big, 0);
+}
+
+// nearest source row / column of a patch stretched over [lo, hi): ((2 (v - lo) + 1) * 32) / (2 (hi - lo)) in integers, 0..31 for
+// lo <= v < hi, the identity when hi - lo == 32
+__device__ __forceinline__ int zmap_src(int v, int lo, int hi) { return ((2 * (v - lo) + 1) * ZMAP_SIDE) / (2 * (hi - lo)); }
+
+// paint_mask_kernel with the value read from the cube's z-map instead of one score per box: same tiles, same pairs, same LDS passes
+// over the frame's rectangles (no limit on their number); z is read through L2 only where the pixel lies inside the rectangle.
+__global__ void __launch_bounds__(256) paint_zmap_kernel(const double* __restrict__ z, const int32_t* __restrict__ frame_off,
+                                                         const int4* __restrict__ rects, int f0, int h, int w,
+                                                         double* __restrict__ out) {
+  __shared__ int4 srect[PAINT_PASS];
+  const int f = f0 + blockIdx.y;
+  const int m0 = frame_off[f], m1 = frame_off[f + 1];
+  if (m1 <= m0) return;                      // a frame without boxes in this group keeps what it holds
+  const int hw = h * w;
+  double* fr = out + (int64_t)f * hw;
+  const int mis = (int)((reinterpret_cast<uintptr_t>(fr) >> 3) & 1);
+  const int p0 = blockIdx.x * PAINT_TILE + 2 * (int)threadIdx.x - mis;
+  const bool in0 = p0 >= 0 && p0 < hw, in1 = p0 + 1 >= 0 && p0 + 1 < hw;
+  double v0 = 0.0, v1 = 0.0;
+  if (in0 && in1) {
+    const double2 v = *reinterpret_cast<const double2*>(fr + p0);
+    v0 = v.x; v1 = v.y;
+  } else if (in0) {
+    v0 = fr[p0];
+  } else if (in1) {
+    v1 = fr[p0 + 1];
+  }
+  const int ya = in0 ? p0 / w : -1, xa = in0 ? p0 - ya * w : -1;               // -1: inside no rectangle (y0, x0 >= 0)
+  const int yb = in1 ? (p0 + 1) / w : -1, xb = in1 ? (p0 + 1) - yb * w : -1;
+  for (int base = m0; base < m1; base += PAINT_PASS) {
+    const int cnt = min(PAINT_PASS, m1 - base);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) srect[threadIdx.x] = rects[base + threadIdx.x];
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const int4 r = srect[k];                // y0, y1, x0, x1
+      const double* zm = z + (int64_t)(base + k) * ZMAP_PIX;
+      if (ya >= r.x && ya < r.y && xa >= r.z && xa < r.w)
+        v0 = fmax(v0, zm[zmap_src(ya, r.x, r.y) * ZMAP_SIDE + zmap_src(xa, r.z, r.w)]);
+      if (yb >= r.x && yb < r.y && xb >= r.z && xb < r.w)
+        v1 = fmax(v1, zm[zmap_src(yb, r.x, r.y) * ZMAP_SIDE + zmap_src(xb, r.z, r.w)]);
+    }
+  }
+  if (in0 && in1) {
+    *reinterpret_cast<double2*>(fr + p0) = make_double2(v0, v1);
+  } else if (in0) {
+    fr[p0] = v0;
+  } else if (in1) {
+    fr[p0 + 1] = v1;
+  }
+}
+
+// The pixel criterion on a formed mask: per frame the k-th largest mask value over the ground-truth pixels, k = ceil(|G| pct / 100),
+// or the largest value of the whole mask for a frame without ground truth (= k-th largest with k = 1 over every pixel).  Exact
+// radix select, most significant digit first, on the order-preserving 64-bit integer image of the doubles: per pass every selected
+// pixel whose key continues the prefix found so far adds 1 to the int32 LDS histogram of its next digit (integer adds: the totals do
+// not depend on the order), the digit that holds the k-th largest is read off the histogram from the top, and k is reduced by what
+// lies above it.  11-bit digits (8 KB histogram): 5 passes of 11 bits and one of 9.  A NaN is outside the domain.
+constexpr int KTH_BITS = 11, KTH_BINS = 1 << KTH_BITS;
+
+__device__ __forceinline__ unsigned long long kth_key(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__global__ void __launch_bounds__(256) mask_kth_kernel(const uint8_t* __restrict__ gt, const double* __restrict__ masks, int pct,
+                                                       double big, int hw, double* __restrict__ out,
+                                                       int32_t* __restrict__ gt_count) {
+  __shared__ int hist[KTH_BINS];
+  __shared__ int chunk[256];
+  __shared__ int total;
+  __shared__ int sel_digit, sel_rest;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const uint8_t* g = gt + (int64_t)f * hw;
+  const double* mk = masks + (int64_t)f * hw;
+  if (tid == 0) total = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int p = tid; p < hw; p += 256) mine += g[p] != 0;
+  if (mine) atomicAdd(&total, mine);
+  __syncthreads();
+  const int G = total;
+  const bool all = G == 0;                   // a normal frame: the maximum over every pixel
+  const int n_sel = all ? hw : G;
+  if (n_sel == 0) {                          // a frame without pixels
+    if (tid == 0) { out[f] = -big; gt_count[f] = 0; }
+    return;
+  }
+  int k = all ? 1 : (int)(((long long)G * pct + 99) / 100);      // 1 <= k <= n_sel
+  unsigned long long prefix = 0;             // the digits found so far, at their place in the key
+  int done = 0;                              // bits of the key found so far
+  while (done < 64) {
+    const int width = min(KTH_BITS, 64 - done), shift = 64 - done - width;
+    for (int b = tid; b < KTH_BINS; b += 256) hist[b] = 0;
+    __syncthreads();
+    for (int p = tid; p < hw; p += 256) {
+      if (!all && !g[p]) continue;
+      const unsigned long long key = kth_key(mk[p]);
+      if (done && (key >> (64 - done)) != (prefix >> (64 - done))) continue;
+      atomicAdd(&hist[(int)((key >> shift) & ((1u << width) - 1))], 1);
+    }
+    __syncthreads();
+    // 256 chunks of 8 bins; thread 0 walks the chunk sums from the top, then the 8 bins of the chunk that reaches k
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < KTH_BINS / 256; ++j) s += hist[tid * (KTH_BINS / 256) + j];
+    chunk[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+      int above = 0, c = 255;
+      while (c > 0 && above + chunk[c] < k) { above += chunk[c]; --c; }
+      int d = c * (KTH_BINS / 256) + (KTH_BINS / 256) - 1;
+      while (d > c * (KTH_BINS / 256) && above + hist[d] < k) { above += hist[d]; --d; }
+      sel_digit = d;
+      sel_rest = k - above;
+    }
+    __syncthreads();
+    prefix |= (unsigned long long)sel_digit << shift;
+    k = sel_rest;
+    done += width;
+    __syncthreads();                         // sel_digit / sel_rest are read before the next pass rewrites them
+  }
+  if (tid == 0) {
+    const unsigned long long u = (prefix >> 63) ? (prefix & 0x7fffffffffffffffull) : ~prefix;
+    out[f] = __longlong_as_double((long long)u);
+    gt_count[f] = G;
+  }
+}
+
 }  // namespace
 
 extern "C" int vv_frame_scores(const float* raw, const float* of, const int32_t* frame_off, const int32_t* cube_stat,
@@ -321,6 +467,43 @@ extern "C" int vv_pixel_scores(const uint8_t* gt, const double* scores, const in
   if (!frame_off || !out || !gt_count || (!gt && h * w > 0) || ((!scores || !rects) && max_boxes > 0)) return VV_ERR_BAD_ARG;
   VV_LAUNCH(pixel_score_kernel, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, gt, scores, frame_off,
             reinterpret_cast<const int4*>(rects), pct, big, h, w, out, gt_count);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_error_zmaps(const float* e_raw, const float* e_of, const int32_t* cube_stat, const double* stats, double w_raw,
+                              double w_of, double big, int32_t n, double* out, vv_stream stream) {
+  if (n < 0) return VV_ERR_BAD_ARG;
+  if (n == 0) return VV_OK;
+  if (!e_raw || !cube_stat || !stats || !out) return VV_ERR_BAD_ARG;
+  const int64_t total = (int64_t)n * ZMAP_PIX;
+  if (total / 256 > INT32_MAX) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(error_zmap_kernel, dim3((unsigned)(total / 256)), dim3(256), 0, (hipStream_t)stream, e_raw, e_of, cube_stat, stats,
+            w_raw, w_of, big, total, out);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_paint_zmaps(const double* z, const int32_t* frame_off, const int32_t* rects, int32_t n_frames, int32_t h,
+                              int32_t w, double* out, vv_stream stream) {
+  if (n_frames < 0 || h < 0 || w < 0 || (int64_t)h * w > INT32_MAX / 64 - PAINT_TILE) return VV_ERR_BAD_ARG;      // zmap_src: 64 (v - lo) in int32
+  if (n_frames == 0 || h == 0 || w == 0) return VV_OK;
+  if (!z || !frame_off || !rects || !out) return VV_ERR_BAD_ARG;
+  const int tiles = (h * w + 1 + PAINT_TILE - 1) / PAINT_TILE;      // + 1: a frame that starts 8 bytes off a 16-byte boundary
+  for (int f0 = 0; f0 < n_frames; f0 += 65535) {                    // gridDim.y
+    VV_LAUNCH(paint_zmap_kernel, dim3(tiles, min(65535, n_frames - f0)), dim3(256), 0, (hipStream_t)stream, z, frame_off,
+              reinterpret_cast<const int4*>(rects), f0, h, w, out);
+    VV_CHECK_LAUNCH();
+  }
+  return VV_OK;
+}
+
+extern "C" int vv_mask_kth(const uint8_t* gt, const double* masks, int32_t pct, double big, int32_t n_frames, int32_t h, int32_t w,
+                           double* out, int32_t* gt_count, vv_stream stream) {
+  if (n_frames < 0 || h < 0 || w < 0 || pct < 1 || pct > 100 || (int64_t)h * w > INT32_MAX - 256) return VV_ERR_BAD_ARG;
+  if (n_frames == 0) return VV_OK;
+  if (!out || !gt_count || ((!gt || !masks) && h * w > 0)) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(mask_kth_kernel, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, gt, masks, pct, big, h * w, out, gt_count);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

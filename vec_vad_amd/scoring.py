@@ -15,6 +15,11 @@ reduces a frame to the one number that carries its pixel-level ROC: with ``G`` t
 the frame is detected at threshold ``t`` iff ``100 * #{p in G: mask[p] >= t} >= percent * #G``, i.e. iff the ``k``-th largest
 mask value over ``G``, ``k = ceil(#G * percent / 100)``, is ``>= t``; a normal frame is a false positive iff ``mask.max() >= t``.
 The area under that ROC is ``roc_auc`` of those numbers against the frame labels.
+
+Per-pixel anomaly maps (``[mi355x] pixel_maps``): a painted mask is constant inside every box.  ``error_zmaps`` turns the per-pixel
+reconstruction errors of the bank (``FusedTrainer.score_cubes(maps=True)``) into one z-normalised 32 x 32 map per cube,
+``paint_error_masks`` stretches every map over its cube's rectangle (nearest source pixel, ``patch_index``) and max-combines them
+into fine masks with the support of the painted ones, and ``mask_pixel_scores`` is ``pixel_scores`` on such formed masks.
 """
 import math
 
@@ -177,6 +182,95 @@ def pixel_scores(gt, scores, frame_off, rects, percent=40, out=None):
     _lib.check(_lib.lib().vv_pixel_scores(gt.data_ptr(), scores.data_ptr(), _dv(off, torch.int32, dev).data_ptr(), rects.data_ptr(),
                                          int(percent), float(BIG), F, int(gt.shape[1]), int(gt.shape[2]), most, out.data_ptr(),
                                          cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_pixel_scores')
+    return out, cnt
+
+
+PATCH = 32             # side of a cube's patch: the z-maps are [n, PATCH, PATCH]
+
+
+def patch_index(v, lo, hi):
+    """The patch row (column) painted at frame row (column) ``v`` of a rectangle ``[lo, hi)``: the nearest source pixel of the 32-pixel
+    patch stretched over it, ``((2 * (v - lo) + 1) * 32) // (2 * (hi - lo))`` in integers -- ``0..31``, non-decreasing in ``v``, the
+    identity when ``hi - lo == 32``.  What ``vv_paint_zmaps`` computes; numpy integer arrays or ints."""
+    return ((2 * (v - lo) + 1) * PATCH) // (2 * (hi - lo))
+
+
+def error_zmaps(e_raw, e_of, cube_stat, stats, w_raw, w_of):
+    """The z-map of every cube: CUDA float64 ``[n,32,32]``, ``z[m][q] = w_raw * ((1024 * e_raw[m][q] - mu_r) / sd_r) [+ w_of * ((1024 *
+    e_of[m][q] - mu_o) / sd_o)]`` -- the expression of ``cube_scores`` (the same device function, float64, every product, quotient and
+    sum rounded on its own) with 1024 times the pixel's error in place of the cube's, ``BIG`` where ``cube_stat`` is ``-1``.  The cube's
+    error is the sum of its 1024 pixel errors, so a cube whose error is spread evenly gets the constant map ``z = its cube score``, to
+    the bit.  e_raw / e_of: CUDA float32 ``[n,32,32]`` (``of=None`` drops the flow term); cube_stat, stats as for ``cube_scores``.
+    Costs 8 KB of device memory per cube: form the maps of a chunk of frames, not of a test set."""
+    if not e_raw.is_cuda:
+        raise _lib.VecVadHipError('error_zmaps needs device-resident error maps; vec_vad_amd has no CPU path')
+    dev = e_raw.device
+    cube_stat, stats = _dv(cube_stat, torch.int32, dev), _stats(stats, dev)
+    e_raw = e_raw.to(torch.float32).contiguous()
+    e_of = e_of.to(torch.float32).contiguous() if e_of is not None else None
+    n = cube_stat.numel()
+    if e_raw.numel() != n * PATCH * PATCH or (e_of is not None and e_of.numel() != n * PATCH * PATCH):
+        raise ValueError('error_zmaps: e_raw, e_of must be [%d,%d,%d] maps of the %d cubes of cube_stat' % (n, PATCH, PATCH, n))
+    out = torch.empty((n, PATCH, PATCH), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().vv_error_zmaps(e_raw.data_ptr(), e_of.data_ptr() if e_of is not None else None, cube_stat.data_ptr(),
+                                        stats.data_ptr(), float(w_raw), float(w_of), float(BIG), n, out.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream), 'vv_error_zmaps')
+    return out
+
+
+def paint_error_masks(z, frame_off, rects, h, w, out=None):
+    """``paint_masks`` with a value that varies inside the box: pixel ``(y, x)`` of the rectangle ``(y0, y1, x0, x1)`` of cube ``m`` is
+    max-combined with ``z[m][patch_index(y, y0, y1)][patch_index(x, x0, x1)]``.  z: CUDA float64 ``[n,32,32]`` (``error_zmaps``);
+    frame_off, rects, h, w and ``out`` exactly as for ``paint_masks`` (CSR over ``F`` frames, ``box_rects`` rows, float64 ``[F,h,w]``
+    max-accumulated into, background ``-BIG`` when None): a frame may be painted group by group, and the support of a fine mask is the
+    support of the painted one.  For a box inside the frame the rectangle is the crop the cube was cut from.  NaNs are outside the
+    domain."""
+    if not z.is_cuda:
+        raise _lib.VecVadHipError('paint_error_masks needs device-resident maps; vec_vad_amd has no CPU path')
+    dev = z.device
+    z = z.to(torch.float64).contiguous().view(-1, PATCH, PATCH)
+    n = z.shape[0]
+    off = _csr(frame_off, n)
+    F = off.size - 1
+    rects = _dv(rects, torch.int32, dev).view(-1, 4)
+    if rects.shape[0] != n:
+        raise ValueError('paint_error_masks: %d rectangles for %d maps' % (rects.shape[0], n))
+    if out is None:
+        out = torch.full((F, h, w), -float(BIG), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (F, h, w) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('paint_error_masks: out must be a contiguous float64 [%d,%d,%d] tensor on %s' % (F, h, w, dev))
+    if n == 0:                        # nothing to paint: every frame keeps what it holds
+        return out
+    _lib.check(_lib.lib().vv_paint_zmaps(z.data_ptr(), _dv(off, torch.int32, dev).data_ptr(), rects.data_ptr(), F, int(h), int(w),
+                                        out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_paint_zmaps')
+    return out
+
+
+def mask_pixel_scores(gt, masks, percent=40, out=None):
+    """``pixel_scores`` on formed masks.  gt: uint8 ``[F,h,w]`` (CUDA tensor, or a host array that is uploaded); masks: CUDA float64
+    ``[F,h,w]`` (``paint_error_masks``, ``paint_masks``).  Returns ``(s_pix, gt_count)``, CUDA float64 ``[F]`` and int32 ``[F]``:
+    ``s_pix[f]`` = the ``k``-th largest value of ``masks[f]`` over the ground-truth pixels, ``k = (gt_count * percent + 99) // 100``, for
+    an anomalous frame (a ``-BIG`` pixel counts as ``-BIG``) and ``masks[f].max()`` for a normal one, written into ``out`` when one is
+    given.  Exact (a radix select on the integer image of the doubles), whatever the ties.  NaNs are outside the domain."""
+    if not masks.is_cuda:
+        raise _lib.VecVadHipError('mask_pixel_scores needs device-resident masks; vec_vad_amd has no CPU path')
+    if int(percent) != percent or not 1 <= int(percent) <= 100:
+        raise ValueError('mask_pixel_scores: percent must be an integer in 1..100, got %r' % (percent,))
+    dev = masks.device
+    if masks.dim() != 3:
+        raise ValueError('mask_pixel_scores: masks must be [F,h,w], got %s' % (tuple(masks.shape),))
+    masks = masks.to(torch.float64).contiguous()
+    F, h, w = masks.shape
+    gt = _dv(gt, torch.uint8, dev)
+    if tuple(gt.shape) != (F, h, w):
+        raise ValueError('mask_pixel_scores: gt must be [%d,%d,%d], got %s' % (F, h, w, tuple(gt.shape)))
+    if out is None:
+        out = torch.empty(F, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (F,) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('mask_pixel_scores: out must be a contiguous float64 [%d] tensor on %s' % (F, dev))
+    cnt = torch.empty(F, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().vv_mask_kth(gt.data_ptr(), masks.data_ptr(), int(percent), float(BIG), F, int(h), int(w), out.data_ptr(),
+                                     cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_mask_kth')
     return out, cnt
 
 

@@ -475,25 +475,30 @@ class FusedTrainer:
 
     # ---- eval-mode scoring (train.py:413-427, test.py:319-335)
     @torch.no_grad()
-    def score_cubes(self, raw_u8, flow, idx=None, batch=None):
+    def score_cubes(self, raw_u8, flow, idx=None, batch=None, maps=False):
+        """Per-cube (raw, flow | None) squared-error sums of the cubes ``idx`` of a device-resident store.  ``maps=True`` also returns
+        the per-pixel errors they are the sums of, ``(r, o, e_raw [B,32,32], e_of [B,32,32] | None)``: the same forward with the
+        reconstructions stored, then ``bank.error_maps`` into fresh tensors -- ``r`` and ``o`` are the bits of the plain call."""
         bank = self.bank
         if self._graph_ok():
-            return self._score_graphed(raw_u8, flow, idx, batch)
+            return self._score_graphed(raw_u8, flow, idx, batch, maps)
         ws = bank.set_input_cubes(raw_u8, flow, idx, batch)
-        bank.forward(ws, False, outputs=False)
-        return bank.cube_scores(ws)
+        bank.forward(ws, False, outputs=bool(maps))
+        return bank.cube_scores(ws) + bank.error_maps(ws) if maps else bank.cube_scores(ws)
 
-    def _score_graphed(self, raw_u8, flow, idx, batch):
+    def _score_graphed(self, raw_u8, flow, idx, batch, maps=False):
         """Eval-mode scoring of one batch replayed from a hipGraph: cube gather + folded-model forward + the per-cube score sums.
-        The folded model is rebuilt OUTSIDE the graph when the parameters changed (bank.prepare_eval)."""
+        The folded model is rebuilt OUTSIDE the graph when the parameters changed (bank.prepare_eval).  ``maps``: a capture of its own
+        (key 'eval_maps') of the plan that stores the reconstructions; the error maps are formed behind the replay, outside the graph,
+        into tensors of the caller's own."""
         bank, lib = self.bank, self.bank.lib
         B = int(idx.numel()) if idx is not None else (batch if batch is not None else raw_u8.shape[0])
-        key = ('eval', B, raw_u8.data_ptr(), flow.data_ptr() if flow is not None else 0)
+        key = ('eval_maps' if maps else 'eval', B, raw_u8.data_ptr(), flow.data_ptr() if flow is not None else 0)
         cap = self._graph_lookup(key)
         if cap is None or cap == 'warm':
             ws = bank.set_input_cubes(raw_u8, flow, idx, batch)
-            bank.forward(ws, False, outputs=False)
-            out = bank.cube_scores(ws)
+            bank.forward(ws, False, outputs=bool(maps))
+            out = bank.cube_scores(ws) + bank.error_maps(ws) if maps else bank.cube_scores(ws)
             if cap is None:
                 self._graphs[key] = 'warm'
                 return out
@@ -503,7 +508,7 @@ class FusedTrainer:
             seg = [self._thunk(lib.vv_cube_gather, (B, bank.tot_raw, bank.tot_of, HWp, sidx.data_ptr(), raw_u8.data_ptr(),
                                                     flow.data_ptr() if flow is not None else None, ws.cube.data_ptr(),
                                                     ws.flow.data_ptr()), 'cube_gather')]
-            seg += [self._thunk(*c) for c in ws.fwdq[False].calls]
+            seg += [self._thunk(*c) for c in (ws.fwd if maps else ws.fwdq)[False].calls]
             cap = type('Captured', (), {})()
             cap.ws, cap.idx, cap.keep = ws, sidx, (raw_u8, flow)
             cap.launches = len(seg)
@@ -520,8 +525,8 @@ class FusedTrainer:
             cap.idx.copy_(idx)
             cap.identity = False
         cap.segments[0][0].replay()
-        cap.ws.out4_valid = False
-        return bank.cube_scores(cap.ws)
+        cap.ws.out4_valid = bool(maps)
+        return bank.cube_scores(cap.ws) + bank.error_maps(cap.ws) if maps else bank.cube_scores(cap.ws)
 
     @torch.no_grad()
     def score_nchw(self, x, x_of):
