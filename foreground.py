@@ -172,7 +172,7 @@ PIXEL_GT_SHANGHAI = ('[mi355x] pixel_criterion = True does not cover ShanghaiTec
 
 
 def gt_source(c):
-    """The per-pixel ground truth of the test split for ``[mi355x] pixel_criterion``: the dataset the reference's evaluation step
+    """The per-pixel ground truth of the test split for ``[mi355x] pixel_criterion`` / ``region_criterion``: the dataset the reference's evaluation step
     builds (test.py:366-368: no context, 'hard' border) over ``<raw_dataset_dir>/<ds>``.  Returns ``gt`` with ``len(gt)`` = the
     number of test frames and ``gt(i)`` = the mask of frame ``i`` as a contiguous uint8 ``[h,w]`` array (non-zero = anomalous
     pixel).  Raises a one-line ``ValueError`` for ShanghaiTech (before anything is read), for a tree without per-pixel ground truth
@@ -189,6 +189,8 @@ def gt_source(c):
             root, n_gt if dataset.return_gt else 0, len(dataset)))
 
     class Source:
+        frame_video_idx = list(dataset.frame_video_idx)      # the video of every test frame ([mi355x] region_criterion: tracks)
+
         def __len__(self):
             return len(dataset)
 

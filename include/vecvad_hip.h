@@ -643,6 +643,34 @@ int vv_paint_zmaps(const double* z, const int32_t* frame_off, const int32_t* rec
 int vv_mask_kth(const uint8_t* gt, const double* masks, int32_t pct, double big, int32_t n_frames, int32_t h, int32_t w,
                 double* out, int32_t* gt_count, vv_stream stream);
 
+/* ---- region- and track-based detection criteria (RBDC / TBDC): exact integer geometry; the curves are the host's ----
+ * A region is an 8-connected component of the non-zero pixels of a frame's ground truth; the regions of a frame are numbered 1..R in
+ * raster order of each component's first pixel, 0 is background.  The match and link tables hold VV_REGION_MAX regions per frame.
+ * vv_label_regions: gt uint8 [n_frames][h][w] -> labels int32 [n_frames][h][w] (the numbering above) and n_regions[f] = R, the true
+ *   count even above VV_REGION_MAX (labels are then still the raster ranks; the calls below ignore those above the cap).  Union-find on
+ *   pixel indices with atomicMin (a parent never lies above its child, so every walk and every join ends by construction; no workgroup
+ *   waits for another), then one workgroup per frame ranks the roots with a block scan.  The result is canonical: bit-identical run to
+ *   run.  h * w <= 2^31 - 1 (VV_ERR_UNSUPPORTED within 1024 of it).
+ * vv_region_match: a detection is a cube m of frame f (frame_off CSR [n_frames + 1] into scores double [n_boxes] and rects int32
+ *   [n_boxes][4] rows (y0, y1, x0, x1), as for vv_paint_masks) whose rectangle is non-empty; it matches region r of its frame iff
+ *   inter > 0 and 100 * inter >= iou_pct * (area_m + area_r - inter) in int64, inter = pixels of r inside the rectangle, area_m =
+ *   (y1-y0)*(x1-x0).  region_area int32 [n_frames][64] (0 past R), region_score double [n_frames][64] = the largest score among the
+ *   detections that match the region, -big if none does; box_state uint8 [n_boxes] = 0 empty rectangle, 1 matched a region, 2 false
+ *   positive.  1 <= iou_pct <= 100.  One workgroup per frame, integer LDS histograms, any number of boxes per frame.
+ * vv_region_links: links[f][r-1] gets bit q-1 when region r of frame f and region q of the frame before it share a pixel position;
+ *   the frame before frame 0 is prev_labels int32 [h][w] (NULL: none).  same_video uint8 [n_frames]: a frame with 0 gets no links.
+ *   links uint64 [n_frames][64] is written whole (zeros where nothing links).  LDS table per 2048 positions, 64-bit atomicOr.
+ * Empty shapes (n_frames == 0; h * w == 0; n_boxes == 0) are VV_OK; NULL pointers with non-empty shapes, negative sizes, iou_pct
+ * outside 1..100 and h * w > INT32_MAX are VV_ERR_BAD_ARG. */
+#define VV_REGION_MAX 64
+int vv_label_regions(const uint8_t* gt, int32_t* labels, int32_t* n_regions, int32_t n_frames, int32_t h, int32_t w,
+                     vv_stream stream);
+int vv_region_match(const int32_t* labels, const double* scores, const int32_t* frame_off, const int32_t* rects, int32_t iou_pct,
+                    double big, int32_t n_frames, int32_t h, int32_t w, int32_t n_boxes, int32_t* region_area, double* region_score,
+                    uint8_t* box_state, vv_stream stream);
+int vv_region_links(const int32_t* prev_labels, const int32_t* labels, const uint8_t* same_video, int32_t n_frames, int32_t h,
+                    int32_t w, uint64_t* links, vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

@@ -35,6 +35,13 @@ inside a box the anomaly lies, with the support of the ``score_mask`` files) and
 when ``save_score_masks`` is on; with ``pixel_criterion`` the same criterion is also evaluated on the fine masks
 (``scoring.mask_pixel_scores``): ``pixel_scores_fine_<fg>_<method>.npy`` and ``<modality>_<fg>_<method>_pixel_fine_results.npz``.
 Everything else -- frame scores, ``score_mask`` files, pixel scores -- is what a run without the key writes.
+
+``[mi355x] region_criterion = True`` (default False; UCSDped2 / avenue; independent of ``pixel_criterion``) adds the region- and
+track-based detection criteria (RBDC / TBDC, ``scoring`` module docstring) with the scored boxes as detections: per chunk the ground truth
+is labelled into regions, matched against the chunk's boxes and linked to the frame before on the GPU (``scoring.label_regions``,
+``region_match``, ``region_links``); ``results/<ds>/region_scores_<fg>_<method>.npz`` keeps the region, track and false-positive scores
+and ``<modality>_<fg>_<method>_region_results.npz`` the curves and the two numbers.  Regions and tracks are derived from the per-pixel
+ground truth, not read from hand-drawn annotations as for published numbers.  Every other file is what a run without the key writes.
 """
 import os
 import sys
@@ -216,17 +223,59 @@ class PixelEval:
     the frame labels (bool ``[n_frames]``) the ground-truth pixel counts are checked against, or None; ``device_masks``: paint the
     ``result_dir`` masks on the GPU; ``frames_per_chunk``: frames per ground-truth upload / mask download.  ``maps`` (``[mi355x]
     pixel_maps``): the per-pixel error maps of every scored cube are kept and painted into fine masks, saved per frame under
-    ``error_dir`` when one is given and, with a ground-truth source, reduced to ``out_fine`` (CUDA float64 ``[n_frames]``) like ``out``."""
+    ``error_dir`` when one is given and, with a ground-truth source, reduced to ``out_fine`` (CUDA float64 ``[n_frames]``) like ``out``.
+
+    ``regions`` (``[mi355x] region_criterion``; needs a ground-truth source): the region stage runs on every chunk next to the pixel
+    scores, with ``region_iou`` the match bound in integer percent and ``video_idx`` the video of every test frame
+    (``frame_video_idx``).  The object then carries the accumulating region state across chunks and across the parts of
+    ``score_store`` -- the last label map of the frame before (for the links), and per chunk the region counts, areas, scores, link
+    words and false-positive scores --, which ``region_state`` turns into the lists the curves are made of.  Frames must arrive in
+    increasing order, each once.  ``criterion = False`` keeps a ground-truth source without the pixel scores (``out`` not needed)."""
 
     def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64, maps=False, error_dir=None,
-                 out_fine=None):
+                 out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None):
         self.gt, self.percent, self.out, self.labels = gt, int(percent), out, labels
         self.device_masks, self.frames_per_chunk = bool(device_masks), max(1, int(frames_per_chunk))
         self.maps, self.error_dir, self.out_fine = bool(maps), error_dir, out_fine
-        if gt is not None and out is None:
+        self.criterion, self.regions, self.region_iou = bool(criterion), bool(regions), int(region_iou)
+        self.video_idx = None if video_idx is None else np.asarray(video_idx)
+        if gt is not None and self.criterion and out is None:
             raise ValueError('PixelEval: a ground-truth source needs an `out` vector for the pixel scores')
-        if self.maps and gt is not None and out_fine is None:
+        if self.maps and gt is not None and self.criterion and out_fine is None:
             raise ValueError('PixelEval: maps with a ground-truth source need an `out_fine` vector for the fine pixel scores')
+        if self.regions and (gt is None or self.video_idx is None):
+            raise ValueError('PixelEval: regions need a ground-truth source and the video index of every frame')
+        self.prev_labels, self.next_frame = None, 0        # label map of frame next_frame - 1 (device), the frame expected next
+        self.region_chunks = []                            # per chunk: (first frame, n_regions, area, score, links, fp scores), host
+
+    def region_stage(self, gt, off, scores, rects, a, b):
+        """The region stage of frames ``[a, b)``: ``gt`` the chunk's uploaded ground truth, (off, scores, rects) its merged cubes."""
+        if a != self.next_frame:
+            raise ValueError('PixelEval: the region stage expects frame {} next, got {}'.format(self.next_frame, a))
+        labels, n_regions = scoring.label_regions(gt, frame0=a)
+        area, best, state = scoring.region_match(labels, scores, off, rects, self.region_iou)
+        vid = self.video_idx
+        same = np.array([f > 0 and vid[f] == vid[f - 1] for f in range(a, b)], np.uint8)
+        links = scoring.region_links(labels, self.prev_labels, same)
+        self.region_chunks.append((a, n_regions.cpu().numpy(), area.cpu().numpy(), best.cpu().numpy(), links.cpu().numpy(),
+                                   scores[state == 2].cpu().numpy()))
+        if b > a:
+            self.prev_labels, self.next_frame = labels[-1].clone(), b
+
+    def region_state(self, track_percent=10):
+        """What the chunks add up to: region score / frame / area / track (one entry per region, in frame and number order), track
+        scores, false-positive scores (descending) and the number of frames seen."""
+        n_reg = np.concatenate([c[1] for c in self.region_chunks] or [np.zeros(0, np.int32)]).astype(np.int64)
+        links = np.concatenate([c[4] for c in self.region_chunks] or [np.zeros((0, scoring.REGION_MAX), np.int64)])
+        pick = np.arange(scoring.REGION_MAX)[None, :] < n_reg[:, None]                      # [F,64]: the regions that exist
+        score = np.concatenate([c[3] for c in self.region_chunks] or [np.zeros((0, scoring.REGION_MAX))])[pick]
+        area = np.concatenate([c[2] for c in self.region_chunks] or [np.zeros((0, scoring.REGION_MAX), np.int32)])[pick]
+        frame = np.repeat(np.arange(n_reg.size), n_reg)
+        track, _, k = scoring.link_tracks(n_reg, links, track_percent)
+        fp = np.sort(np.concatenate([c[5] for c in self.region_chunks] or [np.zeros(0)]))[::-1]
+        return dict(region_score=score.astype(np.float64), region_frame=frame.astype(np.int64), region_area=area.astype(np.int32),
+                    region_track=track, track_score=scoring.track_scores(score, track, k), fp_score=np.ascontiguousarray(fp),
+                    n_frames=np.int64(self.next_frame))
 
 
 def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_groups=None):
@@ -235,7 +284,8 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
     and / or its masks are painted on the device, group by group, brought to the host once and saved per frame.  ``map_groups``
     (``pixel.maps``; one entry per group of ``dev_groups``: None for a block without a model, else (e_raw, e_of, stats, w_raw, w_of)):
     the chunk's z-maps are formed and painted group by group into one fine-mask buffer, which is saved per frame under
-    ``pixel.error_dir`` and / or reduced to ``pixel.out_fine`` against the same ground truth."""
+    ``pixel.error_dir`` and / or reduced to ``pixel.out_fine`` against the same ground truth.  With ``pixel.regions`` the region stage
+    (``PixelEval.region_stage``) runs on the same merged cubes and the same uploaded ground truth."""
     paint = pixel.device_masks and result_dir
     if paint:
         os.makedirs(result_dir, exist_ok=True)
@@ -248,8 +298,12 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
         if pixel.gt is not None:
             off, sc, rc = scoring.merge_groups(sub, n_frames=b - a, device=device)
             gt = torch.from_numpy(np.stack([pixel.gt(i) for i in range(a, b)])).to(device)
-            _, cnt = scoring.pixel_scores(gt, sc, off, rc, pixel.percent, out=pixel.out[a:b])
-            if pixel.labels is not None:
+            if pixel.regions:
+                pixel.region_stage(gt, off, sc, rc, a, b)
+            cnt = None
+            if pixel.criterion:
+                _, cnt = scoring.pixel_scores(gt, sc, off, rc, pixel.percent, out=pixel.out[a:b])
+            if cnt is not None and pixel.labels is not None:
                 bad = np.nonzero((cnt.cpu().numpy() > 0) != np.asarray(pixel.labels[a:b], bool))[0]
                 if len(bad):
                     raise ValueError('frame {}: its label and its per-pixel ground truth disagree on whether it is anomalous'.format(
@@ -276,7 +330,7 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
                                             w_raw, w_of)
                 scoring.paint_error_masks(z, off - lo, rc[lo:hi], h, w, out=fine)
                 del z
-            if gt is not None:
+            if gt is not None and pixel.criterion:
                 scoring.mask_pixel_scores(gt, fine, pixel.percent, out=pixel.out_fine[a:b])
             if pixel.error_dir:
                 fine = fine.cpu().numpy()
@@ -475,10 +529,11 @@ def main(config_path='config.cfg', flownet2=None):
     if c['direct_flow'] and not c['direct_test']:
         raise ValueError('[mi355x] direct_flow = True needs direct_test = True: only the direct test path computes the flow on the GPU')
     gt = None
-    if c['pixel_criterion'] and not cp.getboolean(ds, 'scores_saved'):
+    want_gt = c['pixel_criterion'] or c['region_criterion']      # either one opens the ground-truth source
+    if want_gt and not cp.getboolean(ds, 'scores_saved'):
         from foreground import gt_source
         gt = gt_source(c)                 # ShanghaiTech / a tree without per-pixel ground truth: refused before any GPU work
-    elif c['pixel_criterion'] and ds == 'ShanghaiTech':
+    elif want_gt and ds == 'ShanghaiTech':
         from foreground import PIXEL_GT_SHANGHAI
         raise ValueError(PIXEL_GT_SHANGHAI)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
@@ -494,17 +549,21 @@ def main(config_path='config.cfg', flownet2=None):
     frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
     pixel_scores_path = os.path.join(results_dir, ds, 'pixel_scores_{}_{}.npy'.format(fg, method))
     fine_scores_path = os.path.join(results_dir, ds, 'pixel_scores_fine_{}_{}.npy'.format(fg, method))
-    ps = ps_fine = None
+    region_scores_path = os.path.join(results_dir, ds, 'region_scores_{}_{}.npz'.format(fg, method))
+    ps = ps_fine = regions = None
     if cp.getboolean(ds, 'scores_saved'):
         fs = np.load(frame_scores_path)
         if c['pixel_criterion']:
             ps = np.load(pixel_scores_path)
             if c['pixel_maps']:
                 ps_fine = np.load(fine_scores_path)
+        if c['region_criterion']:
+            regions = dict(np.load(region_scores_path))
     else:
         mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
         error_dir = os.path.join(results_dir, ds, 'error_mask') if c['save_score_masks'] and c['pixel_maps'] else None
-        maps = c['pixel_maps'] and (error_dir is not None or gt is not None)      # neither a file nor a score to form them for: off
+        pix_gt = gt is not None and c['pixel_criterion']      # the pixel scores are wanted (the source may be open for the regions alone)
+        maps = c['pixel_maps'] and (error_dir is not None or pix_gt)      # neither a file nor a score to form them for: off
         made = []
 
         def pixel_eval(n_frames, labels):
@@ -513,12 +572,16 @@ def main(config_path='config.cfg', flownet2=None):
                 return None
             if gt is not None and len(gt) != n_frames:
                 raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
-            out = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device) if gt is not None else None
+            out = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device) if pix_gt else None
+            # the region keys travel as trailing keywords: with region_criterion off the calls are the ones made before it existed
+            rk = dict(criterion=pix_gt, regions=True, region_iou=c['region_iou_percent'], video_idx=gt.frame_video_idx) \
+                if c['region_criterion'] else {}
             if not maps:
-                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk']))
+                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
+                                      **rk))
             else:
                 made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
-                                      maps=True, error_dir=error_dir, out_fine=out.clone() if gt is not None else None))
+                                      maps=True, error_dir=error_dir, out_fine=out.clone() if pix_gt else None, **rk))
             return made[0]
 
         if direct:
@@ -535,17 +598,36 @@ def main(config_path='config.cfg', flownet2=None):
                               pixel=pixel_eval(len(fset), np.load(lab_file).astype(bool) if os.path.exists(lab_file) else None))
         os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
         np.save(frame_scores_path, fs)
-        if gt is not None:
+        if pix_gt:
             ps = made[0].out.cpu().numpy()
             np.save(pixel_scores_path, ps)
             if made[0].maps:
                 ps_fine = made[0].out_fine.cpu().numpy()
                 np.save(fine_scores_path, ps_fine)
+        if c['region_criterion']:
+            regions = made[0].region_state(c['track_percent'])
+            if int(regions['n_frames']) != len(fs):
+                raise ValueError('the region stage saw {} of the {} test frames'.format(int(regions['n_frames']), len(fs)))
+            np.savez(region_scores_path, **regions)
+
+    def region_results():
+        """criterion = 'region' / 'track' (scoring.py module docstring): needs no frame labels, only the saved region file."""
+        if regions is None:
+            return
+        print('Evaluating {} by region- and track-criterion (regions and tracks derived from the per-pixel ground truth):'.format(ds))
+        path = os.path.join(results_dir, ds, '{}_{}_{}_region_results.npz'.format(mod, fg, method))
+        fpr, rbdr, tbdr, rbdc, tbdc = scoring.region_curves(regions['region_score'], regions['track_score'], regions['fp_score'],
+                                                            int(regions['n_frames']))
+        np.savez(path, fpr=fpr, rbdr=rbdr, tbdr=tbdr, rbdc=rbdc, tbdc=tbdc)
+        print('Results written to {}:'.format(path))
+        print('RBDC (IoU {}%) is {}'.format(c['region_iou_percent'], rbdc))
+        print('TBDC (IoU {}%, {}% of a track) is {}'.format(c['region_iou_percent'], c['track_percent'], tbdc))
 
     # ---- evaluation (test.py:362-399), criterion = 'frame'
     lab_path = base + 'frame_labels_test.npy'
     if not os.path.exists(lab_path):
         print('no {} -> frame-level evaluation skipped (ground-truth masks need the dataset frame indexers)'.format(lab_path))
+        region_results()
         return None
     labels = np.load(lab_path).astype(bool)
     print('Evaluating {} by frame-criterion:'.format(ds))
@@ -582,6 +664,7 @@ def main(config_path='config.cfg', flownet2=None):
         print('Fine pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], fine_auc))
         print('Fine pixel-level AUC@ROC (device pair count) is {}'.format(
             scoring.roc_auc(torch.from_numpy(np.asarray(ps_fine, np.float64)).to(device), labels)))
+    region_results()
     return auc
 
 

@@ -112,9 +112,13 @@ def read_config(path='config.cfg'):
              pixel_criterion=cp.getboolean('mi355x', 'pixel_criterion', fallback=False),
              pixel_overlap_percent=cp.getint('mi355x', 'pixel_overlap_percent', fallback=40),
              device_score_masks=cp.getboolean('mi355x', 'device_score_masks', fallback=False),
-             pixel_maps=cp.getboolean('mi355x', 'pixel_maps', fallback=False))
-    if not 1 <= c['pixel_overlap_percent'] <= 100:
-        raise ValueError('[mi355x] pixel_overlap_percent must be an integer in 1..100, got {}'.format(c['pixel_overlap_percent']))
+             pixel_maps=cp.getboolean('mi355x', 'pixel_maps', fallback=False),
+             region_criterion=cp.getboolean('mi355x', 'region_criterion', fallback=False),
+             region_iou_percent=cp.getint('mi355x', 'region_iou_percent', fallback=10),
+             track_percent=cp.getint('mi355x', 'track_percent', fallback=10))
+    for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
+        if not 1 <= c[key] <= 100:
+            raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -180,6 +180,9 @@ _SIGS = {
     'vv_error_zmaps': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
     'vv_paint_zmaps': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'vv_mask_kth': (c_i32, [c_vp, c_vp, c_i32, c_f64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'vv_label_regions': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'vv_region_match': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vv_region_links': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
     'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),

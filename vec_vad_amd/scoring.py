@@ -20,6 +20,28 @@ Per-pixel anomaly maps (``[mi355x] pixel_maps``): a painted mask is constant ins
 reconstruction errors of the bank (``FusedTrainer.score_cubes(maps=True)``) into one z-normalised 32 x 32 map per cube,
 ``paint_error_masks`` stretches every map over its cube's rectangle (nearest source pixel, ``patch_index``) and max-combines them
 into fine masks with the support of the painted ones, and ``mask_pixel_scores`` is ``pixel_scores`` on such formed masks.
+
+Region- and track-based detection criteria (``[mi355x] region_criterion``; RBDC / TBDC of Ramachandra and Jones, "Street Scene", WACV
+2020), with regions and tracks derived from the per-pixel ground truth instead of hand-drawn annotations.  All percentages are
+integers, so every comparison is exact in integer arithmetic.
+  Detection: a scored cube ``m`` of a frame whose rectangle ``rects[m]`` (``box_rects`` row) is non-empty; area ``(y1-y0)*(x1-x0)``,
+    score ``cube_scores[m]``.  A cube with an empty rectangle is no detection at all, as it paints nothing.
+  Region: an 8-connected component of the non-zero ground-truth pixels of a frame, numbered ``1..R`` in raster order of each
+    component's first pixel (``0`` = background); at most ``REGION_MAX`` = 64 per frame (``label_regions``).
+  Match: detection ``m`` matches region ``r`` of its frame iff ``inter > 0 and 100 * inter >= region_iou_percent * (area_m + area_r -
+    inter)`` in int64, ``inter`` = pixels of ``r`` inside the rectangle.  A detection that matches no region of its frame is a false
+    positive (every detection of a normal frame is one); this does not depend on any threshold (``region_match``).
+  Region score: the largest score among the detections that match the region, ``-BIG`` if none does; the region is detected at
+    threshold ``t`` iff its score is ``>= t``.
+  Track: regions of consecutive frames of one video are linked when they share a pixel position (``region_links``); tracks are the
+    connected components of the link graph (``link_tracks``).  Track score: the ``k``-th largest region score of the track, ``k = (len
+    * track_percent + 99) // 100`` -- the track is detected at ``t`` iff at least ``k`` of its regions are (``track_scores``).
+  Curves (``region_curves``): thresholds are the distinct values among all region, track and false-positive scores, descending; a
+    score of ``-BIG`` (a region no detection matches) is "never detected" and supplies no threshold.  At ``t``: ``fpr`` = false
+    positives with score ``>= t`` / ``n_frames``, ``rbdr`` = regions with score ``>= t`` / regions, ``tbdr`` likewise for tracks.
+    Each curve starts at (0, 0), is piecewise linear through its points, is cut at ``fpr = 1`` by linear interpolation on the segment
+    that crosses it and extended flat to ``fpr = 1`` when its last point lies left of it; RBDC / TBDC are the trapezoid areas over
+    ``fpr`` in [0, 1].  No region at all: ``nan``.  Region scores [3, 1], false positives [2], 2 frames: RBDC = 0.75.
 """
 import math
 
@@ -272,6 +294,193 @@ def mask_pixel_scores(gt, masks, percent=40, out=None):
     _lib.check(_lib.lib().vv_mask_kth(gt.data_ptr(), masks.data_ptr(), int(percent), float(BIG), F, int(h), int(w), out.data_ptr(),
                                      cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_mask_kth')
     return out, cnt
+
+
+REGION_MAX = 64        # regions of one frame (the tables of vv_region_match / vv_region_links; one bit each in a link word)
+
+
+def _percent(name, v):
+    if int(v) != v or not 1 <= int(v) <= 100:
+        raise ValueError('%s must be an integer in 1..100, got %r' % (name, v))
+    return int(v)
+
+
+def label_regions(gt, frame0=0):
+    """The ground-truth regions of ``F`` frames (module docstring).  gt: uint8 ``[F,h,w]`` (non-zero = anomalous pixel; CUDA tensor, or
+    a host array that is uploaded).  Returns ``(labels, n_regions)``, CUDA int32 ``[F,h,w]`` and ``[F]``: ``labels[f]`` holds ``0`` for
+    background and ``1..R`` for the 8-connected components in raster order of their first pixel, ``n_regions[f] = R``.  A frame with
+    more than ``REGION_MAX`` regions is a one-line ``ValueError`` that names it as frame ``frame0 + f``."""
+    if not torch.is_tensor(gt):
+        gt = torch.from_numpy(np.ascontiguousarray(gt))
+    if not torch.cuda.is_available():
+        raise _lib.VecVadHipError('label_regions needs a GPU; vec_vad_amd has no CPU path')
+    dev = gt.device if gt.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    gt = _dv(gt, torch.uint8, dev)
+    if gt.dim() != 3:
+        raise ValueError('label_regions: gt must be [F,h,w], got %s' % (tuple(gt.shape),))
+    F, h, w = gt.shape
+    labels = torch.empty((F, h, w), dtype=torch.int32, device=dev)
+    n_regions = torch.zeros(F, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().vv_label_regions(gt.data_ptr(), labels.data_ptr(), n_regions.data_ptr(), F, h, w,
+                                          torch.cuda.current_stream(dev).cuda_stream), 'vv_label_regions')
+    cnt = n_regions.cpu().numpy()
+    if F and int(cnt.max()) > REGION_MAX:
+        f = int(np.nonzero(cnt > REGION_MAX)[0][0])
+        raise ValueError('label_regions: frame %d has %d ground-truth regions, at most %d are supported' % (frame0 + f, int(cnt[f]), REGION_MAX))
+    return labels, n_regions
+
+
+def _labels(name, labels):
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise _lib.VecVadHipError('%s needs device-resident labels; vec_vad_amd has no CPU path' % name)
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError('%s: labels must be an int32 [F,h,w] tensor (label_regions), got %s %s' % (name, labels.dtype, tuple(labels.shape)))
+    return labels.contiguous()
+
+
+def region_match(labels, scores, frame_off, rects, iou_percent=10):
+    """Detections against regions (module docstring).  labels: CUDA int32 ``[F,h,w]`` (``label_regions``); scores / frame_off / rects
+    as for ``pixel_scores``, with ALL cubes of a frame in this one call (``merge_groups``); any number of cubes per frame.  Returns
+    ``(region_area, region_score, box_state)``: CUDA int32 ``[F,64]`` (pixels of region ``r`` of frame ``f`` at ``[f, r-1]``, 0 past the
+    frame's last region), float64 ``[F,64]`` (the largest score among the detections that match the region, ``-BIG`` if none does) and
+    uint8 ``[n]`` (0 = empty rectangle: no detection, 1 = matched a region, 2 = false positive).  NaN scores are outside the domain."""
+    labels = _labels('region_match', labels)
+    iou_percent = _percent('region_match: iou_percent', iou_percent)
+    dev = labels.device
+    F, h, w = labels.shape
+    scores = _dv(scores, torch.float64, dev).view(-1)
+    n = scores.numel()
+    off = _csr(frame_off, n)
+    if off.size - 1 != F:
+        raise ValueError('region_match: frame_off covers %d frames, labels %d' % (off.size - 1, F))
+    rects = _dv(rects, torch.int32, dev).view(-1, 4)
+    if rects.shape[0] != n:
+        raise ValueError('region_match: %d rectangles for %d scores' % (rects.shape[0], n))
+    area = torch.empty((F, REGION_MAX), dtype=torch.int32, device=dev)
+    best = torch.empty((F, REGION_MAX), dtype=torch.float64, device=dev)
+    state = torch.zeros(n, dtype=torch.uint8, device=dev)      # a cube no frame of the CSR names stays 0
+    _lib.check(_lib.lib().vv_region_match(labels.data_ptr(), scores.data_ptr(), _dv(off, torch.int32, dev).data_ptr(), rects.data_ptr(),
+                                         iou_percent, float(BIG), F, h, w, n, area.data_ptr(), best.data_ptr(), state.data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream), 'vv_region_match')
+    return area, best, state
+
+
+def region_links(labels, prev=None, same_video=None):
+    """Links between the regions of consecutive frames (module docstring).  labels: CUDA int32 ``[F,h,w]``; prev: the label map of the
+    frame before ``labels[0]`` (CUDA int32 ``[h,w]``) or None when there is none; same_video: ``[F]``, non-zero where frame ``f``
+    continues the video of the frame before it (None: all ones).  Returns CUDA int64 ``[F,64]`` holding 64-bit words: bit ``q-1`` of
+    ``links[f, r-1]`` is set iff region ``r`` of frame ``f`` shares a pixel position with region ``q`` of the frame before it; zeros
+    for a frame with ``same_video[f] == 0`` and for frame 0 without ``prev``."""
+    labels = _labels('region_links', labels)
+    dev = labels.device
+    F, h, w = labels.shape
+    if prev is not None:
+        if not torch.is_tensor(prev) or tuple(prev.shape) != (h, w) or prev.dtype != torch.int32 or prev.device != dev:
+            raise ValueError('region_links: prev must be an int32 [%d,%d] tensor on %s' % (h, w, dev))
+        prev = prev.contiguous()
+    same = torch.ones(F, dtype=torch.uint8, device=dev) if same_video is None else \
+        _dv(np.asarray(same_video).astype(bool).astype(np.uint8) if not torch.is_tensor(same_video) else (same_video != 0), torch.uint8, dev).view(-1)
+    if same.numel() != F:
+        raise ValueError('region_links: same_video names %d frames, labels %d' % (same.numel(), F))
+    links = torch.zeros((F, REGION_MAX), dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().vv_region_links(prev.data_ptr() if prev is not None else None, labels.data_ptr(), same.data_ptr(), F, h, w,
+                                         links.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_region_links')
+    return links
+
+
+def link_tracks(n_regions, links, track_percent=10):
+    """Tracks out of link words, on the host.  n_regions: ``[F]`` regions per frame (each ``<= REGION_MAX``); links: ``[F,64]`` 64-bit
+    words (``region_links``, chunks concatenated in frame order; int64 or uint64).  The regions are listed in (frame, number) order;
+    union-find over the link bits joins region ``r`` of frame ``f`` with every region ``q`` of frame ``f - 1`` whose bit is set.
+    Returns ``(track, length, k)``: int64 ``[n_total]`` track id per region (tracks numbered ``0..T-1`` in order of their first
+    region), int64 ``[T]`` regions per track and int64 ``[T]`` ``k = (length * track_percent + 99) // 100``."""
+    track_percent = _percent('link_tracks: track_percent', track_percent)
+    n_regions = np.asarray(n_regions.cpu() if torch.is_tensor(n_regions) else n_regions, np.int64).reshape(-1)
+    F = n_regions.size
+    links = links.cpu().numpy() if torch.is_tensor(links) else links
+    words = np.ascontiguousarray(np.asarray(links)).reshape(F, REGION_MAX).view(np.uint64) if F else np.zeros((0, REGION_MAX), np.uint64)
+    if F and (n_regions.min() < 0 or n_regions.max() > REGION_MAX):
+        raise ValueError('link_tracks: n_regions must lie in 0..%d' % REGION_MAX)
+    first = np.concatenate([[0], np.cumsum(n_regions)])
+    parent = list(range(int(first[-1])))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for f in range(1, F):
+        for r in range(int(n_regions[f])):
+            word = int(words[f, r])
+            q = 0
+            while word:
+                if word & 1:
+                    if q >= n_regions[f - 1]:
+                        raise ValueError('link_tracks: frame %d links to region %d of a frame with %d regions' % (f, q + 1, n_regions[f - 1]))
+                    a, b = find(int(first[f]) + r), find(int(first[f - 1]) + q)
+                    if a != b:
+                        parent[max(a, b)] = min(a, b)
+                word >>= 1
+                q += 1
+    ids, track = {}, np.zeros(len(parent), np.int64)
+    for i in range(len(parent)):
+        track[i] = ids.setdefault(find(i), len(ids))      # roots are the first region of their track: ids grow in region order
+    length = np.bincount(track, minlength=len(ids)).astype(np.int64)
+    return track, length, (length * track_percent + 99) // 100
+
+
+def track_scores(region_scores, track, k):
+    """The ``k[t]``-th largest region score of every track ``t`` (float64 ``[T]``): the track is detected at ``t`` iff at least ``k`` of
+    its regions are.  region_scores ``[n]``, track ``[n]`` (``link_tracks``), k ``[T]``."""
+    region_scores, track = np.asarray(region_scores, np.float64).reshape(-1), np.asarray(track, np.int64).reshape(-1)
+    k = np.asarray(k, np.int64).reshape(-1)
+    out = np.empty(k.size, np.float64)
+    for t in range(k.size):
+        out[t] = np.sort(region_scores[track == t])[::-1][k[t] - 1]
+    return out
+
+
+def _area_to_one(x, y):
+    """Trapezoid area over ``x`` in [0, 1] of the piecewise-linear curve through (x[i], y[i]) (x non-decreasing, x[0] == 0): cut at
+    ``x = 1`` by interpolation on the segment that crosses it, extended flat when the last point lies left of it."""
+    area = 0.0
+    for i in range(1, len(x)):
+        x0, x1, y0, y1 = x[i - 1], x[i], y[i - 1], y[i]
+        if x1 > 1.0:
+            if x0 < 1.0:
+                yc = y0 + (y1 - y0) * (1.0 - x0) / (x1 - x0)
+                area += (1.0 - x0) * (y0 + yc) / 2.0
+            return area
+        area += (x1 - x0) * (y0 + y1) / 2.0
+    return area + (1.0 - x[-1]) * y[-1]
+
+
+def region_curves(region_scores, track_scores, fp_scores, n_frames, log=print):
+    """RBDC and TBDC from the three score lists (module docstring), on the host in float64.  Returns ``(fpr, rbdr, tbdr, rbdc, tbdc)``:
+    the curve points, one per threshold in descending order behind the starting point (0, 0) (``fpr`` is not cut at 1; the areas
+    are).  Without a region the two numbers are ``nan``, the arrays hold the false-positive curve against zeros and a line says so."""
+    rs, ts, fp = (np.asarray(a, np.float64).reshape(-1) for a in (region_scores, track_scores, fp_scores))
+    if int(n_frames) != n_frames or n_frames < 1:
+        raise ValueError('region_curves: n_frames must be a positive integer, got %r' % (n_frames,))
+    if (rs.size == 0) != (ts.size == 0):
+        raise ValueError('region_curves: %d regions but %d tracks' % (rs.size, ts.size))
+    if np.isnan(rs).any() or np.isnan(ts).any() or np.isnan(fp).any():
+        raise ValueError('region_curves: NaN scores are outside the domain')
+    every = np.concatenate([rs, ts, fp])
+    thr = np.unique(every[every > -float(BIG)])[::-1]              # descending; -BIG = never detected
+    rs_s, ts_s, fp_s = np.sort(rs), np.sort(ts), np.sort(fp)
+
+    def at_least(sorted_scores):                                   # how many scores are >= each threshold
+        return (sorted_scores.size - np.searchsorted(sorted_scores, thr, side='left')).astype(np.float64)
+
+    fpr = np.concatenate([[0.0], at_least(fp_s) / float(n_frames)])
+    rbdr = np.concatenate([[0.0], at_least(rs_s) / rs.size if rs.size else np.zeros(thr.size)])
+    tbdr = np.concatenate([[0.0], at_least(ts_s) / ts.size if ts.size else np.zeros(thr.size)])
+    if rs.size == 0:
+        log('no ground-truth region in the test set: RBDC and TBDC are undefined (nan)')
+        return fpr, rbdr, tbdr, float('nan'), float('nan')
+    return fpr, rbdr, tbdr, float(_area_to_one(fpr, rbdr)), float(_area_to_one(fpr, tbdr))
 
 
 def frame_scores(raw, of, frame_off, cube_stat, stats, paints, w_raw, w_of, out=None):
