@@ -423,7 +423,10 @@ int vv_channelnorm_fwd(const float* in, float* out, int32_t B, int32_t C, int32_
  * kind 2 = the same nn.Conv2d in "row-K" form for the few-channel first layers (FlowNetC.py conv1: 7x7 s2 on 3 channels;
  * FlowNetSD.py conv0: 3x3 s1 on 6): src.cstride = 4 (R = 7, stride 2) or 8 (R = 3, stride 1), src.coff = 0; K runs over the
  * flattened (kx, c) run of one filter row, Cin = CinP = ceil8(R * cstride) (32 / 24), and the panel is packed with taps = R from a
- * weight tensor rearranged to [N][kx * cstride + c][ky] (zeros at the pad channels and beyond kx = R - 1). */
+ * weight tensor rearranged to [N][kx * cstride + c][ky] (zeros at the pad channels and beyond kx = R - 1).
+ * Size limit: the source is loaded through 32-bit byte offsets, so B * H * W * src.cstride * 4 must stay below 2^31 bytes (2 GiB);
+ * a larger source is refused with VV_ERR_UNSUPPORTED and nothing is launched.  vv_conv3x3_n2 and vv_conv2d_f16 address their source
+ * with 64-bit pointers and refuse B * H * W * src_cstride >= 2^31 ELEMENTS (the pixel index is an int). */
 typedef struct vv_conv2d_params {
   int32_t kind, R, stride;
   int32_t B, H, W;          /* input size */

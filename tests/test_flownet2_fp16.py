@@ -75,6 +75,7 @@ F16_CONV_CASES = [  # (kind, R, stride, Cin, Cout, H, W, relu)
     # two-channel heads: predict_flow (tile / split / tap forms) and upsampled_flow
     ('conv', 3, 1, 1026, 2, 4, 6, False), ('conv', 3, 1, 770, 2, 28, 20, False), ('conv', 3, 1, 386, 2, 40, 56, False),
     ('conv', 3, 1, 194, 2, 104, 100, False), ('conv', 3, 1, 16, 2, 120, 100, False), ('conv', 3, 1, 32, 2, 101, 103, False),
+    ('conv', 3, 1, 194, 2, 48, 50, False),      # 32 lanes per pixel: 4096 <= pixels < 20000 with Cin < 320
     ('deconv', 4, 2, 2, 2, 4, 6, False),
 ]
 

@@ -763,7 +763,9 @@ int launch2d(const vv_conv2d_params* p, hipStream_t st) {
 extern "C" int vv_conv2d_mfma(const vv_conv2d_params* p, vv_stream stream) {
   if (!p || !p->src.ptr || !p->w || !p->out.ptr) return VV_ERR_BAD_ARG;
   if ((p->kind != 2 && p->CinP % 16) || p->CoutP % 32 || p->src.cstride % 4 || p->src.coff % 4) return VV_ERR_BAD_ARG;
-  if ((int64_t)p->B * p->H * p->W * p->src.cstride >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
+  // the staging loads (VVStagerB::prefetch) form 32-bit BYTE offsets against a descriptor of 2^31 - 1 bytes: from element 2^29 on a
+  // load would come back as zeros, from 2^30 on the offset wraps
+  if ((int64_t)p->B * p->H * p->W * p->src.cstride * 4 >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (p->kind == 1) return launch2d<4, 2, 1, 16>(p, st);
   if (p->kind == 2) {
@@ -793,6 +795,8 @@ template <typename T>
 int launch_n2(const T* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* wq, int32_t C4P,
               const float* bias, float slope, T* out, int32_t out_cstride, int32_t out_coff, hipStream_t st) {
   if (!src || !wq || !out || src_cstride % 4 || C4P * 4 < ((Cin + 31) & ~31)) return VV_ERR_BAD_ARG;
+  // every form addresses the source through 64-bit pointers (vv_fetch4, vv_ld4 on src + (int64_t)pixel * cstride), so no byte limit
+  // applies; the pixel index itself is formed in int, and the limit on elements is kept uniformly for all forms and both element types
   if ((int64_t)B * H * W * src_cstride >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
   const int64_t npix = (int64_t)B * H * W;
   constexpr bool F32 = std::is_same<T, float>::value;

@@ -285,6 +285,8 @@ int launch_f16(const vv_conv2d_params* p, hipStream_t st) {
 extern "C" int vv_conv2d_f16(const vv_conv2d_params* p, vv_stream stream) {
   if (!p || !p->src.ptr || !p->w || !p->out.ptr) return VV_ERR_BAD_ARG;
   if (p->CoutP % 32 || p->src.cstride % 8 || p->src.coff % 8 || p->Cin > p->CinP) return VV_ERR_BAD_ARG;
+  // the loader (issue) addresses src + (int64_t)pixel * cstride with 64-bit pointers, so no byte limit applies here; the limit on
+  // elements (2^32 bytes of halves) is kept
   if ((int64_t)p->B * p->H * p->W * p->src.cstride >= (1ll << 31)) return VV_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (p->kind == 2) {

@@ -273,7 +273,8 @@ class _Runner:
         lib, stream = self.lib, torch.cuda.current_stream(src.t.device).cuda_stream
         bias = self._param(m, 'bias', prec)
         bias = None if bias is None else bias.data_ptr()
-        what = '%s %s %dx%d s%d %d->%d' % (prec.conv, r.kind, r.R, r.R, r.stride, r.K, r.N)
+        what = '%s %s %dx%d s%d %d->%d on a source buffer of %d x %d x %d x %d = %d bytes' % (
+            prec.conv, r.kind, r.R, r.R, r.stride, r.K, r.N, src.B, src.H, src.W, src.cs, src.t.numel() * src.t.element_size())
         if r.kind == 'c2':
             w = self._param(m, 'weight', prec).detach()
             assert w.is_contiguous() and w.dtype == torch.float32
