@@ -203,6 +203,15 @@ def gt_source(c):
     return Source()
 
 
+def test_video_idx(c):
+    """The video of every test frame, in frame order (``[mi355x] smooth_masks``: a temporal window does not cross a video border): the
+    ``frame_video_idx`` of the test split's frame indexer over ``<raw_dataset_dir>/<ds>`` -- what ``gt_source`` carries and
+    ``calc_optical_flow.flow_pairs`` reads.  Any dataset; no frame and no ground truth is decoded."""
+    ds = c['dataset_name']
+    return list(unified_dataset_interface(dataset_name=ds, dir=os.path.join(c['raw_dataset_dir'], ds), context_frame_num=0, mode='test',
+                                          border_mode='hard').frame_video_idx)
+
+
 def frame_cubes(raw_ds, flow_ds, idx, motion_thr, device='cuda'):
     """Cubes of frame ``idx`` that pass the motion test: (raw ``[m,(T,)P,P,3]`` uint8, flow ``[m,(Tf,)P,P,2]`` float32,
     kept box indices).  Flow energy per box = sum of squares over the patch (mean over the context frames when there is a

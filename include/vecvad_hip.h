@@ -674,6 +674,34 @@ int vv_region_match(const int32_t* labels, const double* scores, const int32_t* 
 int vv_region_links(const int32_t* prev_labels, const int32_t* labels, const uint8_t* same_video, int32_t n_frames, int32_t h,
                     int32_t w, uint64_t* links, vv_stream stream);
 
+/* ---- spatio-temporal smoothing of score masks ([mi355x] smooth_masks): the 3-D mean filter the object-centric VAD protocol runs over
+ * the painted map volume before it thresholds anything, restricted to the painted pixels ----
+ * masks double [F][h][w]: a buffer of F consecutive frames (vv_paint_masks output), VV_SMOOTH_UNPAINTED (-100000.0) = "unpainted";
+ * vid int32 [F]: the video of every frame of the buffer.  With p = (M != unpainted), V = p ? M : +0.0, N = p ? 1 : 0, rt = kt / 2,
+ * rs = ks / 2, three separable passes, every sum taken in ascending offset order, left to right in float64, from +0.0 (counts are
+ * integers):
+ *   X:  A[f][y][x] = sum over dx = -rs..rs with 0 <= x+dx < w of V[f][y][x+dx];                          a = the same sum over N
+ *   Y:  B[f][y][x] = sum over dy = -rs..rs with 0 <= y+dy < h of A[f][y+dy][x];                          b = the same sum over a
+ *   T:  C[f][y][x] = sum over dt = -rt..rt with 0 <= f+dt < F and vid[f+dt] == vid[f] of B[f+dt][y][x];  c = the same sum over b
+ *   S[f][y][x] = p[f][y][x] ? C / (double)c : unpainted      (one correctly rounded division, never a reciprocal multiply)
+ * The order is part of the contract: the result equals the plain-numpy restatement (tests/smooth_restatement.py) bit for bit.  The
+ * support is preserved, a frame without a box stays unpainted, kt = ks = 1 returns the masks.  A +big box (a block without a trained
+ * model) raises the mean of every painted pixel whose window reaches it: it floods its neighbourhood, on purpose -- "certainly
+ * anomalous" spreads like any other score.
+ * out double [f1-f0][h][w] receives frames [f0, f1) of the buffer: the caller supplies the temporal halo (frames [f0-rt, f1+rt) cut to
+ * the buffer are read; frames outside the buffer or of another video are left out of the T pass).  fmax double [f1-f0] (NULL: not
+ * wanted) receives the maximum of every output frame, exact (unpainted for a frame without a painted pixel or of no pixels).  work:
+ * vv_smooth_masks_work(F, h, w, kt, ks) bytes, 8-byte aligned (the X/Y sums as double and their counts as uint16 -- b <= 33^2, c <= 33^3
+ * < 2^16 --, and one partial maximum per workgroup: no atomics, bit-identical run to run); -1 for sizes vv_smooth_masks refuses.
+ * VV_ERR_BAD_ARG: NULL masks / vid / out / work with something to do, negative sizes, h * w >= 2^31, f0 < 0, f0 > f1, f1 > F, an even
+ * window or one outside 1..VV_SMOOTH_MAX (at 33 a 32x32 tile with its halo of 16 still fits a workgroup's LDS: a stated condition, not
+ * a measured optimum).  F == 0 or f0 == f1: nothing to do, VV_OK, no pointer is looked at.  NaN mask values are outside the domain. */
+#define VV_SMOOTH_MAX 33
+#define VV_SMOOTH_UNPAINTED (-100000.0)
+int64_t vv_smooth_masks_work(int32_t F, int32_t h, int32_t w, int32_t kt, int32_t ks);
+int vv_smooth_masks(const double* masks, const int32_t* vid, int32_t F, int32_t h, int32_t w, int32_t f0, int32_t f1, int32_t kt,
+                    int32_t ks, double* out, double* fmax, void* work, vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

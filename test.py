@@ -42,6 +42,16 @@ is labelled into regions, matched against the chunk's boxes and linked to the fr
 ``region_match``, ``region_links``); ``results/<ds>/region_scores_<fg>_<method>.npz`` keeps the region, track and false-positive scores
 and ``<modality>_<fg>_<method>_region_results.npz`` the curves and the two numbers.  Regions and tracks are derived from the per-pixel
 ground truth, not read from hand-drawn annotations as for published numbers.  Every other file is what a run without the key writes.
+
+``[mi355x] smooth_masks = True`` (default False) adds the step the object-centric VAD protocol takes before it thresholds anything: the
+``score_mask`` volume is filtered on the GPU by a 3-D mean over the painted pixels (``scoring.smooth_masks``; ``smooth_frames`` frames of
+the same video x ``smooth_pixels`` x ``smooth_pixels`` pixels) and the frame score is the maximum of the filtered mask.  The scored
+groups of the whole test set stay on the device (24 B per cube) and one ``_smooth_stage`` runs after all scoring, chunk by chunk with a
+temporal halo, so neither ``direct_frames_per_chunk`` nor ``direct_max_cubes`` changes the result.  Writes
+``frame_scores_smooth_<fg>_<method>.npy`` and ``<modality>_<fg>_<method>_frame_smooth_results.npz`` (per scene for ShanghaiTech); with
+``pixel_criterion`` ``pixel_scores_smooth_*.npy`` and ``*_pixel_smooth_results.npz``; with ``save_score_masks``
+``results/<ds>/score_mask_smooth/<frame>``.  A box of a block without a trained model (``+BIG``) floods its neighbourhood.  Every other
+file is what a run without the key writes; the two windows are untuned.
 """
 import os
 import sys
@@ -230,10 +240,14 @@ class PixelEval:
     (``frame_video_idx``).  The object then carries the accumulating region state across chunks and across the parts of
     ``score_store`` -- the last label map of the frame before (for the links), and per chunk the region counts, areas, scores, link
     words and false-positive scores --, which ``region_state`` turns into the lists the curves are made of.  Frames must arrive in
-    increasing order, each once.  ``criterion = False`` keeps a ground-truth source without the pixel scores (``out`` not needed)."""
+    increasing order, each once.  ``criterion = False`` keeps a ground-truth source without the pixel scores (``out`` not needed).
+
+    ``smooth`` (``[mi355x] smooth_masks``): every call appends its scored groups -- (off over all test frames, device cube scores, device
+    rectangles), 24 B per cube -- to ``smooth_groups``, across the parts of ``score_store``, for the one ``_smooth_stage`` that runs after
+    all scoring."""
 
     def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64, maps=False, error_dir=None,
-                 out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None):
+                 out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None, smooth=False):
         self.gt, self.percent, self.out, self.labels = gt, int(percent), out, labels
         self.device_masks, self.frames_per_chunk = bool(device_masks), max(1, int(frames_per_chunk))
         self.maps, self.error_dir, self.out_fine = bool(maps), error_dir, out_fine
@@ -247,6 +261,7 @@ class PixelEval:
             raise ValueError('PixelEval: regions need a ground-truth source and the video index of every frame')
         self.prev_labels, self.next_frame = None, 0        # label map of frame next_frame - 1 (device), the frame expected next
         self.region_chunks = []                            # per chunk: (first frame, n_regions, area, score, links, fp scores), host
+        self.smooth_groups = [] if smooth else None        # every scored group of the test set, for _smooth_stage
 
     def region_stage(self, gt, off, scores, rects, a, b):
         """The region stage of frames ``[a, b)``: ``gt`` the chunk's uploaded ground truth, (off, scores, rects) its merged cubes."""
@@ -376,12 +391,50 @@ def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, devi
 
 
 def _mask_lists(result_dir, pixel):
-    """(mask_groups, dev_groups, map_groups) for a call: the host list feeds ``_save_masks``, the device lists ``_pixel_stage``."""
+    """(mask_groups, dev_groups, map_groups) for a call: the host list feeds ``_save_masks``, the device lists ``_pixel_stage`` (and,
+    with ``pixel.smooth_groups``, ``_smooth_stage`` once every call has been made)."""
     device_masks = pixel is not None and pixel.device_masks
     maps = pixel is not None and pixel.maps and (pixel.gt is not None or bool(pixel.error_dir))
+    smooth = pixel is not None and pixel.smooth_groups is not None
     return ([] if result_dir and not device_masks else None,
-            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir) or maps) else None,
+            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir) or maps or smooth) else None,
             [] if maps else None)
+
+
+def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixels, frames_per_chunk, device, gt=None, percent=40,
+                  result_dir=None):
+    """``[mi355x] smooth_masks``: the score masks of all ``n_frames`` test frames, smoothed (``scoring.smooth_masks``), in chunks
+    ``[a, b)`` of ``frames_per_chunk`` frames.  ``groups``: every scored group of the test set ((off over all frames, device cube scores,
+    device rectangles) each); per chunk the frames ``[a - rt, b + rt)`` that exist (``rt = smooth_frames // 2``: the temporal halo) are
+    painted on the device, group by group, and frames ``[a, b)`` of the filtered buffer are kept -- the chunk size changes nothing.
+    ``video_idx``: the video of every test frame.  Returns ``(fs_smooth, ps_smooth)``, host float64 ``[n_frames]``: the smoothed frame
+    scores (the maximum of every smoothed mask) and, with a ground-truth source ``gt``, the pixel criterion on the smoothed masks
+    (``scoring.mask_pixel_scores``; else None).  ``result_dir``: the smoothed masks are saved there per frame, like the ``score_mask`` files."""
+    video_idx = np.asarray(video_idx).reshape(-1)
+    if video_idx.size != n_frames:
+        raise ValueError('[mi355x] smooth_masks: the test split indexes {} frames, {} test frames are scored'.format(video_idx.size,
+                                                                                                                    n_frames))
+    rt = smooth_frames // 2
+    fs = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
+    ps = fs.clone() if gt is not None else None
+    if result_dir:
+        os.makedirs(result_dir, exist_ok=True)
+    for a in range(0, n_frames, frames_per_chunk):
+        b = min(a + frames_per_chunk, n_frames)
+        pa, pb = max(0, a - rt), min(n_frames, b + rt)
+        masks = torch.full((pb - pa, h, w), -float(BIG), dtype=torch.float64, device=device)
+        for off, sc, rc in groups:
+            if off[pb] > off[pa]:
+                scoring.paint_masks(sc, off[pa:pb + 1], rc, h, w, out=masks)
+        smoothed, fmax = scoring.smooth_masks(masks, video_idx[pa:pb], smooth_frames, smooth_pixels, lo=a - pa, hi=b - pa)
+        fs[a:b] = fmax
+        if gt is not None:
+            scoring.mask_pixel_scores(torch.from_numpy(np.stack([gt(i) for i in range(a, b)])).to(device), smoothed, percent, out=ps[a:b])
+        if result_dir:
+            smoothed = smoothed.cpu().numpy()
+            for f in range(a, b):
+                torch.save(smoothed[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))
+    return fs.cpu().numpy(), ps.cpu().numpy() if ps is not None else None
 
 
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
@@ -423,6 +476,8 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
         _save_masks(result_dir, range(n_frames), mask_groups, h, w)
     if dev_groups is not None:
         _pixel_stage(pixel, dev_groups, 0, n_frames, h, w, result_dir, device, map_groups)
+        if pixel.smooth_groups is not None:
+            pixel.smooth_groups += dev_groups
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -497,6 +552,8 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
         _save_masks(result_dir, range(first, end), mask_groups, h, w)
     if dev_groups is not None:
         _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_groups)
+        if pixel.smooth_groups is not None:
+            pixel.smooth_groups += dev_groups
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -550,9 +607,15 @@ def main(config_path='config.cfg', flownet2=None):
     pixel_scores_path = os.path.join(results_dir, ds, 'pixel_scores_{}_{}.npy'.format(fg, method))
     fine_scores_path = os.path.join(results_dir, ds, 'pixel_scores_fine_{}_{}.npy'.format(fg, method))
     region_scores_path = os.path.join(results_dir, ds, 'region_scores_{}_{}.npz'.format(fg, method))
-    ps = ps_fine = regions = None
+    smooth_fs_path = os.path.join(results_dir, ds, 'frame_scores_smooth_{}_{}.npy'.format(fg, method))
+    smooth_ps_path = os.path.join(results_dir, ds, 'pixel_scores_smooth_{}_{}.npy'.format(fg, method))
+    ps = ps_fine = regions = fs_smooth = ps_smooth = None
     if cp.getboolean(ds, 'scores_saved'):
         fs = np.load(frame_scores_path)
+        if c['smooth_masks']:
+            fs_smooth = np.load(smooth_fs_path)
+            if c['pixel_criterion']:
+                ps_smooth = np.load(smooth_ps_path)
         if c['pixel_criterion']:
             ps = np.load(pixel_scores_path)
             if c['pixel_maps']:
@@ -568,7 +631,7 @@ def main(config_path='config.cfg', flownet2=None):
 
         def pixel_eval(n_frames, labels):
             """The ``pixel`` keyword of the scoring calls, or None with both new keys off (today's calls)."""
-            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps:
+            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps and not c['smooth_masks']:
                 return None
             if gt is not None and len(gt) != n_frames:
                 raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
@@ -576,6 +639,8 @@ def main(config_path='config.cfg', flownet2=None):
             # the region keys travel as trailing keywords: with region_criterion off the calls are the ones made before it existed
             rk = dict(criterion=pix_gt, regions=True, region_iou=c['region_iou_percent'], video_idx=gt.frame_video_idx) \
                 if c['region_criterion'] else {}
+            if c['smooth_masks']:      # a trailing keyword too: with the key off the calls are the ones made before it existed
+                rk['smooth'] = True
             if not maps:
                 made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
                                       **rk))
@@ -609,6 +674,20 @@ def main(config_path='config.cfg', flownet2=None):
             if int(regions['n_frames']) != len(fs):
                 raise ValueError('the region stage saw {} of the {} test frames'.format(int(regions['n_frames']), len(fs)))
             np.savez(region_scores_path, **regions)
+        if c['smooth_masks']:
+            # ---- [mi355x] smooth_masks: one stage over the kept groups of the whole test set, after all scoring
+            if gt is not None:
+                video_idx = gt.frame_video_idx
+            else:
+                from foreground import test_video_idx
+                video_idx = test_video_idx(c)
+            fs_smooth, ps_smooth = _smooth_stage(
+                made[0].smooth_groups, video_idx, len(fs), h, w, c['smooth_frames'], c['smooth_pixels'], c['direct_frames_per_chunk'],
+                device, gt if pix_gt else None, c['pixel_overlap_percent'],
+                os.path.join(results_dir, ds, 'score_mask_smooth') if c['save_score_masks'] else None)
+            np.save(smooth_fs_path, fs_smooth)
+            if ps_smooth is not None:
+                np.save(smooth_ps_path, ps_smooth)
 
     def region_results():
         """criterion = 'region' / 'track' (scoring.py module docstring): needs no frame labels, only the saved region file."""
@@ -640,6 +719,12 @@ def main(config_path='config.cfg', flownet2=None):
                 results_dir, ds, '{}_{}_{}_frame_results_scene_{}.npz'.format(mod, fg, method, si))))
         auc = float(np.mean(aucs))
         print('Average frame-level AUC is {}'.format(auc))
+        if fs_smooth is not None:
+            print('Average frame-level AUC of the smoothed masks ({} frames x {} x {} pixels) is {}'.format(
+                c['smooth_frames'], c['smooth_pixels'], c['smooth_pixels'], float(np.mean([save_roc_pr_curve_data(
+                    fs_smooth[scene_idx == si], labels[scene_idx == si], os.path.join(
+                        results_dir, ds, '{}_{}_{}_frame_smooth_results_scene_{}.npz'.format(mod, fg, method, si)))
+                    for si in sorted(set(scene_idx))]))))
     else:
         path = os.path.join(results_dir, ds, '{}_{}_{}_frame_results.npz'.format(mod, fg, method))
         print('Results written to {}:'.format(path))
@@ -647,6 +732,11 @@ def main(config_path='config.cfg', flownet2=None):
         # the same number from the device-side pair count (vv_roc_auc_counts); the .npz above keeps the reference's layout
         auc_dev = scoring.roc_auc(torch.from_numpy(np.asarray(fs, np.float64)).to(device), labels)
         print('AUC@ROC (device pair count) is {}'.format(auc_dev))
+        if fs_smooth is not None:
+            path = os.path.join(results_dir, ds, '{}_{}_{}_frame_smooth_results.npz'.format(mod, fg, method))
+            print('Results written to {}:'.format(path))
+            print('Frame-level AUC of the smoothed masks ({} frames x {} x {} pixels) is {}'.format(
+                c['smooth_frames'], c['smooth_pixels'], c['smooth_pixels'], save_roc_pr_curve_data(fs_smooth, labels, path)))
     if ps is not None:
         # ---- criterion = 'pixel': the ROC of the pixel scores against the same frame labels (scoring.py module docstring)
         print('Evaluating {} by pixel-criterion:'.format(ds))
@@ -664,6 +754,12 @@ def main(config_path='config.cfg', flownet2=None):
         print('Fine pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], fine_auc))
         print('Fine pixel-level AUC@ROC (device pair count) is {}'.format(
             scoring.roc_auc(torch.from_numpy(np.asarray(ps_fine, np.float64)).to(device), labels)))
+    if ps_smooth is not None:
+        # ---- the same criterion on the smoothed masks ([mi355x] smooth_masks)
+        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_smooth_results.npz'.format(mod, fg, method))
+        print('Results written to {}:'.format(path))
+        print('Pixel-level AUC of the smoothed masks (overlap {}%) is {}'.format(c['pixel_overlap_percent'],
+                                                                                 save_roc_pr_curve_data(ps_smooth, labels, path)))
     region_results()
     return auc
 

@@ -115,10 +115,16 @@ def read_config(path='config.cfg'):
              pixel_maps=cp.getboolean('mi355x', 'pixel_maps', fallback=False),
              region_criterion=cp.getboolean('mi355x', 'region_criterion', fallback=False),
              region_iou_percent=cp.getint('mi355x', 'region_iou_percent', fallback=10),
-             track_percent=cp.getint('mi355x', 'track_percent', fallback=10))
+             track_percent=cp.getint('mi355x', 'track_percent', fallback=10),
+             smooth_masks=cp.getboolean('mi355x', 'smooth_masks', fallback=False),
+             smooth_frames=cp.getint('mi355x', 'smooth_frames', fallback=5),
+             smooth_pixels=cp.getint('mi355x', 'smooth_pixels', fallback=9))
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
+    for key in ('smooth_frames', 'smooth_pixels'):      # the windows of vv_smooth_masks (VV_SMOOTH_MAX), checked whatever the switch says
+        if not 1 <= c[key] <= 33 or c[key] % 2 == 0:
+            raise ValueError('[mi355x] {} must be an odd integer in 1..33, got {}'.format(key, c[key]))
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -42,6 +42,10 @@ integers, so every comparison is exact in integer arithmetic.
     Each curve starts at (0, 0), is piecewise linear through its points, is cut at ``fpr = 1`` by linear interpolation on the segment
     that crosses it and extended flat to ``fpr = 1`` when its last point lies left of it; RBDC / TBDC are the trapezoid areas over
     ``fpr`` in [0, 1].  No region at all: ``nan``.  Region scores [3, 1], false positives [2], 2 frames: RBDC = 0.75.
+
+Spatio-temporal smoothing (``[mi355x] smooth_masks``): ``smooth_masks`` filters a painted mask volume with the mean over the painted
+pixels of a 3-D window that stays inside the frame's video -- three separable passes of fixed summation order, so the result is defined
+to the bit -- and returns the maximum of every filtered mask, the smoothed frame score.
 """
 import math
 
@@ -294,6 +298,63 @@ def mask_pixel_scores(gt, masks, percent=40, out=None):
     _lib.check(_lib.lib().vv_mask_kth(gt.data_ptr(), masks.data_ptr(), int(percent), float(BIG), F, int(h), int(w), out.data_ptr(),
                                      cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), 'vv_mask_kth')
     return out, cnt
+
+
+SMOOTH_MAX = 33        # widest window of ``smooth_masks`` (VV_SMOOTH_MAX: a 32 x 32 tile with its halo of 16 fits a workgroup's LDS)
+
+
+def smooth_window(name, v):
+    """``v`` as a window of ``smooth_masks``: an odd integer in 1..``SMOOTH_MAX``, else a one-line ``ValueError`` that names it."""
+    if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= SMOOTH_MAX or int(v) % 2 == 0:
+        raise ValueError('%s must be an odd integer in 1..%d, got %r' % (name, SMOOTH_MAX, v))
+    return int(v)
+
+
+def smooth_masks(masks, video_idx, smooth_frames, smooth_pixels, lo=0, hi=None, out=None):
+    """The spatio-temporal mean filter of a mask volume, restricted to the painted pixels (``[mi355x] smooth_masks``; the 3-D mean
+    filter the object-centric VAD protocol runs over its map volume before it takes frame scores).  masks: CUDA float64 ``[F,h,w]``, a
+    buffer of consecutive frames (``paint_masks``), ``-BIG`` = unpainted; video_idx: ``[F]`` integers, the video of every frame of the
+    buffer; smooth_frames / smooth_pixels: odd windows in 1..33 along time / along both image axes.  A painted pixel becomes the mean of
+    the painted pixels of its window -- frames of the buffer that belong to its video, rows and columns inside the image --, an
+    unpainted pixel stays ``-BIG``: the support is preserved and windows (1, 1) return the masks.  The sums are separable (x, then y,
+    then t), each taken in ascending offset order in float64, and the mean is one division: the result is defined to the bit
+    (``include/vecvad_hip.h``, vv_smooth_masks).  A ``+BIG`` box (a block without a trained model) floods its neighbourhood: every
+    painted pixel whose window reaches it gets a mean far above any trained score, on purpose.
+
+    ``lo`` / ``hi`` (default: the whole buffer): only frames ``[lo, hi)`` are returned, the others serve as temporal halo -- a caller
+    that filters a long volume chunk by chunk passes ``smooth_frames // 2`` extra frames on either side.  Returns ``(smoothed, frame_max)``,
+    CUDA float64 ``[hi-lo,h,w]`` (``out`` when one is given) and ``[hi-lo]``: ``frame_max[f] = smoothed[f].max()`` (``-BIG`` for a frame
+    without a painted pixel), the smoothed frame score.  NaNs are outside the domain."""
+    if not torch.is_tensor(masks) or not masks.is_cuda:
+        raise _lib.VecVadHipError('smooth_masks needs device-resident masks; vec_vad_amd has no CPU path')
+    kt, ks = smooth_window('smooth_masks: smooth_frames', smooth_frames), smooth_window('smooth_masks: smooth_pixels', smooth_pixels)
+    if masks.dim() != 3 or masks.dtype != torch.float64:
+        raise ValueError('smooth_masks: masks must be a float64 [F,h,w] tensor, got %s %s' % (masks.dtype, tuple(masks.shape)))
+    dev = masks.device
+    masks = masks.contiguous()
+    F, h, w = masks.shape
+    if h * w >= 2 ** 31:
+        raise ValueError('smooth_masks: frames of %d x %d pixels, fewer than 2^31 are supported' % (h, w))
+    vid = np.asarray(video_idx.cpu() if torch.is_tensor(video_idx) else video_idx).reshape(-1)
+    if vid.size != F or (vid.size and (vid.dtype.kind not in 'iu' or abs(vid.astype(np.int64)).max() >= 2 ** 31)):
+        raise ValueError('smooth_masks: video_idx must name the video of each of the %d frames as an int32, got %s %s' % (
+            F, vid.dtype, vid.shape))
+    hi = F if hi is None else hi
+    if int(lo) != lo or int(hi) != hi or not 0 <= lo <= hi <= F:
+        raise ValueError('smooth_masks: frames [%r, %r) do not lie in the buffer of %d frames' % (lo, hi, F))
+    lo, hi = int(lo), int(hi)
+    if out is None:
+        out = torch.empty((hi - lo, h, w), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (hi - lo, h, w) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('smooth_masks: out must be a contiguous float64 [%d,%d,%d] tensor on %s' % (hi - lo, h, w, dev))
+    fmax = torch.empty(hi - lo, dtype=torch.float64, device=dev)
+    if hi == lo:
+        return out, fmax
+    work = torch.empty(max(1, int(_lib.lib().vv_smooth_masks_work(F, h, w, kt, ks))), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().vv_smooth_masks(masks.data_ptr(), _dv(vid.astype(np.int32), torch.int32, dev).data_ptr(), F, h, w, lo, hi, kt, ks,
+                                         out.data_ptr(), fmax.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+               'vv_smooth_masks')
+    return out, fmax
 
 
 REGION_MAX = 64        # regions of one frame (the tables of vv_region_match / vv_region_links; one bit each in a link word)
