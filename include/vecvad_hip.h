@@ -702,6 +702,48 @@ int64_t vv_smooth_masks_work(int32_t F, int32_t h, int32_t w, int32_t kt, int32_
 int vv_smooth_masks(const double* masks, const int32_t* vid, int32_t F, int32_t h, int32_t w, int32_t f0, int32_t f1, int32_t kt,
                     int32_t ks, double* out, double* fmax, void* work, vv_stream stream);
 
+/* ---- macro AUROC and bootstrap intervals ([mi355x] auc_statistics): weighted Mann-Whitney counts per replicate and group ----
+ * The weighted form of vv_roc_auc_counts.  For replicate r = r0 + k (k < R) and group g, out[k][g] = (U2, P, N) as int64 with
+ *   P  = sum of w_i over the positive frames of the group, N = the same over its negative frames,
+ *   U2 = sum over its positive frames i of w_i * (2 * Nbelow_i + Ntie_i), Nbelow_i / Ntie_i = the weighted number of negative frames of
+ *        the group with a strictly smaller / an equal score;             the group's AUROC is U2 / (2 * P * N), undefined when P * N == 0.
+ * All arithmetic is integer (LDS and global integer atomics, integer scans): bit-identical run to run and independent of the launch.
+ * Tables, all device pointers, built once per score vector (vec_vad_amd/scoring.py auc_tables):
+ *   order int32 [n]: frame indices, grouped by group and ascending by score inside a group (stable sort);
+ *   tie int32 [n]: dense rank of the score inside its group, along order (equal scores of different groups never share a rank);
+ *   label uint8 [n], in frame order (non-zero = positive); group_off int32 [G+1]: CSR offsets into order;
+ *   video_off int32 [V+1]: the frames of video v are [video_off[v], video_off[v+1]) (test frames are contiguous per video);
+ *   stratum_off int32 [S+1]: CSR offsets over the videos (VV_AUC_UNIT_VIDEO only).  Every group must be a union of whole videos.
+ * The frame weights w_i of replicate r:
+ *   VV_AUC_UNIT_NONE : w_i = 1, the full sample; R must be 1 (seed, the video tables and work are not looked at).
+ *   VV_AUC_UNIT_VIDEO: cluster bootstrap.  In stratum s of V_s videos, draw j = 0..V_s-1 picks video stratum_off[s] + draw(seed, r, s, j,
+ *     V_s); w_i = the number of times the video of frame i was picked.
+ *   VV_AUC_UNIT_BLOCK: moving-block bootstrap inside every video (every video is kept).  For video v of L frames, b = min(block, L) and
+ *     k = ceil(L / b); block j = 0..k-1 covers the b frames from draw(seed, r, 2^32 + v, j, L - b + 1) on; w_i = the number of blocks
+ *     that cover frame i.  The weighted length of the video is k * b >= L: it is NOT trimmed to L.
+ * draw is counter based and stateless, all arithmetic mod 2^64:
+ *   mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31
+ *   draw(seed, r, s, j, m) = ((mix(mix(mix(mix(seed) ^ r) ^ s) ^ j) >> 32) * m) >> 32,   in 0..m-1.
+ * The multiply-shift is biased: a value's probability differs from 1 / m by less than 2^-32 (relative bias below m / 2^32).  This is
+ * documented, not corrected.  The draws do not depend on the scores: two score vectors with the same seed get the same weights.
+ * work: vv_auc_boot_work(n, V, R, unit) bytes, 8-byte aligned: the weights as uint32 [R][n] and, for VV_AUC_UNIT_VIDEO, the
+ * multiplicities as uint32 [R][V]; 0 for VV_AUC_UNIT_NONE, -1 for sizes vv_auc_boot_counts refuses.  A caller bounds it by splitting the
+ * replicates over calls (r0): replicates r0..r0+R-1 in one call equal the same replicates in several.
+ * Capacity: a group and a video may hold any number of frames (tiles of 1024 / 4096); U2 fits int64 when max(V_s) * n < 2^31 (the
+ * caller's check).  V > VV_AUC_BOOT_MAX_VIDEOS, R * G > INT32_MAX or R * V > INT32_MAX: VV_ERR_UNSUPPORTED, nothing is launched.
+ * R == 0 or G == 0: VV_OK, nothing is looked at; n == 0: out is zeroed; an empty group gives (0, 0, 0).  VV_ERR_BAD_ARG: NULL order / tie
+ * / label / group_off / out with n > 0, NULL video_off / work (or stratum_off for VV_AUC_UNIT_VIDEO) with a unit that resamples, negative
+ * sizes, r0 < 1, block < 1, an unknown unit, VV_AUC_UNIT_NONE with R > 1.  Against tables that are no CSRs the kernels only protect
+ * memory. */
+#define VV_AUC_UNIT_NONE 0
+#define VV_AUC_UNIT_VIDEO 1
+#define VV_AUC_UNIT_BLOCK 2
+#define VV_AUC_BOOT_MAX_VIDEOS 65536
+int64_t vv_auc_boot_work(int32_t n, int32_t V, int32_t R, int32_t unit);
+int vv_auc_boot_counts(const int32_t* order, const int32_t* tie, const uint8_t* label, const int32_t* group_off,
+                       const int32_t* video_off, const int32_t* stratum_off, int32_t n, int32_t G, int32_t V, int32_t S, uint64_t seed,
+                       int64_t r0, int32_t R, int32_t unit, int32_t block, int64_t* out, void* work, vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

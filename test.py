@@ -52,6 +52,14 @@ temporal halo, so neither ``direct_frames_per_chunk`` nor ``direct_max_cubes`` c
 ``pixel_criterion`` ``pixel_scores_smooth_*.npy`` and ``*_pixel_smooth_results.npz``; with ``save_score_masks``
 ``results/<ds>/score_mask_smooth/<frame>``.  A box of a block without a trained model (``+BIG``) floods its neighbourhood.  Every other
 file is what a run without the key writes; the two windows are untuned.
+
+``[mi355x] auc_statistics = True`` (default False; any dataset, ShanghaiTech included; also with ``scores_saved = True``) adds, for every
+score vector the run has (``frame``, ``frame_smooth``, ``pixel``, ``pixel_fine``, ``pixel_smooth``) and when the frame labels are there,
+the micro AUROC (per-scene mean for ShanghaiTech) and the macro AUROC (mean of the per-video AUROCs) with bootstrap percentile intervals
+(``scoring.auc_bootstrap``: ``auc_bootstrap`` replicates of a moving-block or video bootstrap whose weighted pair counts come from the
+GPU in integers), and the paired difference of every non-plain vector against its plain counterpart (``scoring.auc_paired``).  Writes
+``<modality>_<fg>_<method>_<name>_bootstrap.npz`` and prints one line per statistic.  Every other file is what a run without the key
+writes.  The default block length is an untuned pick: no accuracy claim follows from an interval made with it.
 """
 import os
 import sys
@@ -437,6 +445,43 @@ def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixel
     return fs.cpu().numpy(), ps.cpu().numpy() if ps is not None else None
 
 
+AUC_PLAIN = {'frame_smooth': 'frame', 'pixel_fine': 'pixel', 'pixel_smooth': 'pixel'}      # the plain counterpart of a score vector
+
+
+def _auc_stage(c, vectors, labels, video_idx, scene_idx, path_format, device, log=print):
+    """``[mi355x] auc_statistics``: micro and macro AUROC with bootstrap intervals (``scoring.auc_bootstrap``) of every score vector of
+    ``vectors`` (name -> host scores ``[n_frames]``; plain vectors in front of the ones derived from them), written to
+    ``path_format.format(name)`` with ``micro_`` / ``macro_`` prefixed keys and printed, one line per statistic.  A vector named in
+    ``AUC_PLAIN`` also gets the paired difference against its plain counterpart (``scoring.auc_paired``; ``paired_`` prefixed keys).
+    ``video_idx`` / ``scene_idx``: the video (and, for ShanghaiTech, the scene) of every test frame.  Returns name -> result."""
+    video_idx = np.asarray(video_idx).reshape(-1)
+    if video_idx.size != len(labels):
+        raise ValueError('[mi355x] auc_statistics: the test split indexes {} frames, {} frame labels are given'.format(video_idx.size, len(labels)))
+    kw = dict(replicates=c['auc_bootstrap'], unit=c['auc_bootstrap_unit'], block=c['auc_bootstrap_block'], seed=c['auc_bootstrap_seed'],
+              confidence=c['auc_confidence'])
+    what = '{}% interval of {} {} replicates'.format(kw['confidence'], kw['replicates'], kw['unit'] + (
+        ' ({} frames)'.format(kw['block']) if kw['unit'] == 'block' else ''))
+    done = {}
+    for name, scores in vectors.items():
+        res = scoring.auc_bootstrap(torch.from_numpy(np.asarray(scores, np.float64)).to(device), labels, video_idx, scene_idx, **kw)
+        flat = scoring.auc_flatten(res)
+        for kind in ('micro', 'macro'):
+            e = res[kind]
+            log('{} {} AUROC is {} [{}, {}] ({}, {} invalid; {} groups with both classes)'.format(
+                name, kind, e['auc'], e['lo'], e['hi'], what, e['n_invalid'], e['n_groups_valid']))
+        if name in AUC_PLAIN:
+            pair = scoring.auc_paired(res, done[AUC_PLAIN[name]])
+            flat.update(scoring.auc_flatten(pair, 'paired_'))
+            for kind in ('micro', 'macro'):
+                e = pair[kind]
+                log('{} - {} {} AUROC is {} [{}, {}] ({} invalid; share of replicates with a difference <= 0: {})'.format(
+                    name, AUC_PLAIN[name], kind, e['diff'], e['lo'], e['hi'], e['n_invalid'], e['frac_le0']))
+        np.savez(path_format.format(name), **flat)
+        log('Results written to {}'.format(path_format.format(name)))
+        done[name] = res
+    return done
+
+
 def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, bbox_set, h, w, w_raw, w_of, useFlow,
                  device, score_batch=2048, scene_idx=None, result_dir=None, log=print, return_device=False, pixel=None):
     """Per-frame anomaly scores.  ``net_set[(s,)hh][ww]`` is a list with 0 or 1 eval-mode networks;
@@ -760,6 +805,18 @@ def main(config_path='config.cfg', flownet2=None):
         print('Results written to {}:'.format(path))
         print('Pixel-level AUC of the smoothed masks (overlap {}%) is {}'.format(c['pixel_overlap_percent'],
                                                                                  save_roc_pr_curve_data(ps_smooth, labels, path)))
+    if c['auc_statistics']:
+        # ---- [mi355x] auc_statistics: macro AUROC and bootstrap intervals of every score vector the run has, from the vectors alone
+        print('Evaluating {} with bootstrap statistics:'.format(ds))
+        if gt is not None:
+            video_idx = gt.frame_video_idx
+        else:
+            from foreground import test_video_idx
+            video_idx = test_video_idx(c)
+        vectors = {'frame': fs, 'frame_smooth': fs_smooth, 'pixel': ps, 'pixel_fine': ps_fine, 'pixel_smooth': ps_smooth}
+        _auc_stage(c, {k: v for k, v in vectors.items() if v is not None}, labels, video_idx,
+                   np.asarray(scene_idx).astype(np.int64) if shanghai else None,
+                   os.path.join(results_dir, ds, '{}_{}_{}_{{}}_bootstrap.npz'.format(mod, fg, method)), device)
     region_results()
     return auc
 

@@ -118,13 +118,30 @@ def read_config(path='config.cfg'):
              track_percent=cp.getint('mi355x', 'track_percent', fallback=10),
              smooth_masks=cp.getboolean('mi355x', 'smooth_masks', fallback=False),
              smooth_frames=cp.getint('mi355x', 'smooth_frames', fallback=5),
-             smooth_pixels=cp.getint('mi355x', 'smooth_pixels', fallback=9))
+             smooth_pixels=cp.getint('mi355x', 'smooth_pixels', fallback=9),
+             auc_statistics=cp.getboolean('mi355x', 'auc_statistics', fallback=False),
+             auc_bootstrap=cp.getint('mi355x', 'auc_bootstrap', fallback=1000),
+             auc_bootstrap_unit=cp.get('mi355x', 'auc_bootstrap_unit', fallback='block').strip().lower(),
+             auc_bootstrap_block=cp.getint('mi355x', 'auc_bootstrap_block', fallback=25),
+             auc_bootstrap_seed=cp.getint('mi355x', 'auc_bootstrap_seed', fallback=0),
+             auc_confidence=cp.getint('mi355x', 'auc_confidence', fallback=95))
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
     for key in ('smooth_frames', 'smooth_pixels'):      # the windows of vv_smooth_masks (VV_SMOOTH_MAX), checked whatever the switch says
         if not 1 <= c[key] <= 33 or c[key] % 2 == 0:
             raise ValueError('[mi355x] {} must be an odd integer in 1..33, got {}'.format(key, c[key]))
+    # the settings of scoring.auc_bootstrap ([mi355x] auc_statistics), checked whatever the switch says
+    if c['auc_bootstrap'] < 0:
+        raise ValueError('[mi355x] auc_bootstrap must be a number of replicates >= 0, got {}'.format(c['auc_bootstrap']))
+    if c['auc_bootstrap_unit'] not in ('block', 'video'):
+        raise ValueError("[mi355x] auc_bootstrap_unit must be 'block' or 'video', got {!r}".format(c['auc_bootstrap_unit']))
+    if c['auc_bootstrap_block'] < 1:
+        raise ValueError('[mi355x] auc_bootstrap_block must be a number of frames >= 1, got {}'.format(c['auc_bootstrap_block']))
+    if not 0 <= c['auc_bootstrap_seed'] < 2 ** 64:
+        raise ValueError('[mi355x] auc_bootstrap_seed must be an integer in 0..2^64-1, got {}'.format(c['auc_bootstrap_seed']))
+    if not 50 <= c['auc_confidence'] <= 99:
+        raise ValueError('[mi355x] auc_confidence must be an integer in 50..99, got {}'.format(c['auc_confidence']))
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

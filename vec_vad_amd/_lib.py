@@ -185,6 +185,9 @@ _SIGS = {
     'vv_region_links': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'vv_smooth_masks_work': (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     'vv_smooth_masks': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vv_auc_boot_work': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    'vv_auc_boot_counts': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.c_uint64, c_i64, c_i32, c_i32, c_i32,
+                                   c_vp, c_vp, c_vp]),
     'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
     'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),

@@ -46,6 +46,12 @@ integers, so every comparison is exact in integer arithmetic.
 Spatio-temporal smoothing (``[mi355x] smooth_masks``): ``smooth_masks`` filters a painted mask volume with the mean over the painted
 pixels of a 3-D window that stays inside the frame's video -- three separable passes of fixed summation order, so the result is defined
 to the bit -- and returns the maximum of every filtered mask, the smoothed frame score.
+
+Macro AUROC and bootstrap intervals (``[mi355x] auc_statistics``): ``auc_bootstrap`` gives the micro AUROC (one group, or the mean over
+the scenes) and the macro AUROC (the mean over the videos) of a score vector with percentile intervals from a moving-block bootstrap
+inside every video or a cluster bootstrap over the videos; ``auc_counts`` computes the weighted, tie-aware pair counts of every replicate
+and group on the GPU in integers (``vv_auc_boot_counts``), the statistic is formed on the host in float64.  ``auc_paired`` compares two
+score vectors replicate by replicate: the draws depend on the seed alone.
 """
 import math
 
@@ -571,6 +577,239 @@ def frame_scores(raw, of, frame_off, cube_stat, stats, paints, w_raw, w_of, out=
                                          float(w_raw), float(w_of), float(BIG), F, out.data_ptr(),
                                          torch.cuda.current_stream(dev).cuda_stream), 'vv_frame_scores')
     return out
+
+
+AUC_UNITS = {'none': 0, 'video': 1, 'block': 2}      # VV_AUC_UNIT_*
+AUC_BOOT_MAX_VIDEOS = 65536                          # VV_AUC_BOOT_MAX_VIDEOS
+AUC_WORK_BYTES = 256 << 20                           # device scratch of one vv_auc_boot_counts call; more replicates take more calls
+
+
+def auc_settings(replicates=1000, unit='block', block=25, seed=0, confidence=95):
+    """The settings of ``auc_bootstrap`` (the ``[mi355x] auc_*`` keys), checked: a dict, or a one-line ``ValueError`` that names the key."""
+    def integer(name, v, lo, hi):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError('%s must be an integer in %d..%d, got %r' % (name, lo, hi, v))
+        return int(v)
+    unit = str(unit).strip().lower()
+    if unit not in ('block', 'video'):
+        raise ValueError("auc_bootstrap_unit must be 'block' or 'video', got %r" % (unit,))
+    return dict(n_replicates=integer('auc_bootstrap', replicates, 0, 2 ** 31 - 1), unit=unit,
+                block=integer('auc_bootstrap_block', block, 1, 2 ** 31 - 1), seed=integer('auc_bootstrap_seed', seed, 0, 2 ** 64 - 1),
+                confidence=integer('auc_confidence', confidence, 50, 99))
+
+
+def _runs(name, idx, n):
+    """Per-frame ids that are constant over contiguous runs -> (run starts with ``n`` appended, id of every run); an id that comes back
+    after another one is a ``ValueError``."""
+    idx = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).reshape(-1)
+    if idx.size != n or (n and idx.dtype.kind not in 'iu'):
+        raise ValueError('%s must name every one of the %d frames with an integer, got %s %s' % (name, n, idx.dtype, idx.shape))
+    start = np.concatenate([[0], np.nonzero(idx[1:] != idx[:-1])[0] + 1]) if n else np.zeros(0, np.int64)
+    ids = idx[start]
+    if np.unique(ids).size != ids.size:
+        raise ValueError('%s: the frames of one video must be contiguous' % name)
+    return np.concatenate([start, [n]]).astype(np.int64), ids
+
+
+def auc_tables(scores, labels, video_idx, groups=None, strata=None):
+    """The host tables of ``vv_auc_boot_counts`` (``include/vecvad_hip.h``) for one score vector, as a dict of numpy arrays: ``order``,
+    ``tie``, ``label``, ``group_off``, ``video_off``, ``stratum_off`` and the sizes ``n``, ``G``, ``V``, ``S``.  scores ``[n]`` floats
+    (no NaN); labels ``[n]`` (non-zero = anomalous); video_idx ``[n]`` integers, the video of every frame (contiguous per video);
+    groups ``[n]`` integers, the group of every frame (None: one group; groups are numbered in ascending order of their ids) and
+    strata ``[n]`` integers likewise (None: one stratum; numbered in order of appearance).  Every group and every stratum must be
+    made of whole videos and the videos of a stratum must follow one another; otherwise, and for more than ``AUC_BOOT_MAX_VIDEOS``
+    videos or ``max(V_s) * n >= 2^31`` (U2 would not fit int64), a one-line ``ValueError``."""
+    scores = np.asarray(scores.cpu() if torch.is_tensor(scores) else scores, np.float64).reshape(-1)
+    n = scores.size
+    if n >= 2 ** 31:
+        raise ValueError('auc_tables: %d frames, fewer than 2^31 are supported' % n)
+    if np.isnan(scores).any():
+        raise ValueError('auc_tables: NaN scores are outside the domain')
+    label = (np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).reshape(-1) != 0).astype(np.uint8)
+    if label.size != n:
+        raise ValueError('auc_tables: %d labels for %d scores' % (label.size, n))
+    video_off, _ = _runs('auc_tables: video_idx', video_idx, n)
+    V = video_off.size - 1
+    if V > AUC_BOOT_MAX_VIDEOS:
+        raise ValueError('auc_tables: %d videos, at most %d are supported' % (V, AUC_BOOT_MAX_VIDEOS))
+    first = video_off[:-1]
+
+    def per_video(name, ids):
+        """ids ``[n]`` -> the id of every video, after checking that it is constant inside every video"""
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
+        if ids.size != n or (n and ids.dtype.kind not in 'iu'):
+            raise ValueError('auc_tables: %s must name every one of the %d frames with an integer, got %s %s' % (name, n, ids.dtype, ids.shape))
+        if n and (ids != np.repeat(ids[first], np.diff(video_off))).any():
+            raise ValueError('auc_tables: every one of the %s must be a union of whole videos' % name)
+        return ids[first]
+
+    if groups is None:
+        grank, G = np.zeros(n, np.int64), 1
+    else:
+        gids = per_video('groups', groups)
+        uniq = np.unique(gids)
+        G = max(1, uniq.size)
+        grank = np.searchsorted(uniq, np.asarray(groups.cpu() if torch.is_tensor(groups) else groups).reshape(-1)).astype(np.int64)
+    if strata is None:
+        stratum_off = np.array([0, V], np.int64)
+    else:
+        sids = per_video('strata', strata)
+        s_start = np.concatenate([[0], np.nonzero(sids[1:] != sids[:-1])[0] + 1]) if V else np.zeros(0, np.int64)
+        if np.unique(sids[s_start]).size != s_start.size:
+            raise ValueError('auc_tables: the videos of one of the strata must follow one another')
+        stratum_off = np.concatenate([s_start, [V]]).astype(np.int64)
+    if V and int(np.diff(stratum_off).max()) * n >= 2 ** 31:
+        raise ValueError('auc_tables: max(V_s) * n = %d * %d >= 2^31: U2 would not fit int64' % (int(np.diff(stratum_off).max()), n))
+    order = np.lexsort((scores, grank))                                    # stable: by group, then ascending by score
+    so, go = scores[order], grank[order]
+    head = np.ones(n, bool)
+    if n:
+        head[1:] = (go[1:] != go[:-1]) | (so[1:] != so[:-1])
+    group_off = np.searchsorted(go, np.arange(G + 1)).astype(np.int64)
+    return dict(order=order.astype(np.int32), tie=(np.cumsum(head) - 1).astype(np.int32), label=label, group_off=group_off.astype(np.int32),
+                video_off=video_off.astype(np.int32), stratum_off=stratum_off.astype(np.int32), n=n, G=G, V=V, S=stratum_off.size - 1)
+
+
+def auc_tables_device(tables, device):
+    """``auc_tables`` output with its six arrays as tensors on ``device`` (uploaded once per score vector)."""
+    dev = dict(tables)
+    for k in ('order', 'tie', 'label', 'group_off', 'video_off', 'stratum_off'):
+        dev[k] = torch.from_numpy(np.ascontiguousarray(tables[k])).to(device)
+    return dev
+
+
+def auc_counts_device(t, unit, block, seed, r0, R, out=None, work=None):
+    """``vv_auc_boot_counts`` on uploaded tables (``auc_tables_device``): the CUDA int64 ``[R, G, 3]`` rows ``(U2, P, N)`` of replicates
+    ``r0 .. r0+R-1``, in as many calls as keep the scratch of one below ``AUC_WORK_BYTES`` (``work``: a uint8 scratch tensor to reuse)."""
+    dev = t['order'].device
+    if dev.type != 'cuda':
+        raise _lib.VecVadHipError('auc_counts needs a GPU; vec_vad_amd has no CPU path')
+    if unit not in AUC_UNITS:
+        raise ValueError("auc_counts: unit must be 'none', 'video' or 'block', got %r" % (unit,))
+    if isinstance(R, bool) or int(R) != R or R < 0 or int(r0) != r0 or r0 < 1 or int(block) != block or not 1 <= block < 2 ** 31:
+        raise ValueError('auc_counts: r0 >= 1, R >= 0 and 1 <= block < 2^31 must be integers, got r0 = %r, R = %r, block = %r' % (r0, R, block))
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError('auc_counts: seed must be an integer in 0..2^64-1, got %r' % (seed,))
+    if unit == 'none' and R != 1:
+        raise ValueError("auc_counts: unit 'none' is the full sample, R must be 1, got %r" % (R,))
+    R, n, G, V = int(R), t['n'], t['G'], t['V']
+    if out is None:
+        out = torch.empty((R, G, 3), dtype=torch.int64, device=dev)
+    l = _lib.lib()
+    per = int(l.vv_auc_boot_work(n, V, 1, AUC_UNITS[unit]))
+    if per < 0:
+        raise _lib.VecVadHipError('vv_auc_boot_work refuses n = %d, V = %d' % (n, V))
+    step = max(1, min(R, AUC_WORK_BYTES // max(1, per), (2 ** 31 - 1) // max(1, G, V)))
+    for k in range(0, R, step):
+        m = min(step, R - k)
+        need = int(l.vv_auc_boot_work(n, V, m, AUC_UNITS[unit]))
+        if work is None or work.numel() < need:
+            work = torch.empty(max(8, need), dtype=torch.uint8, device=dev)
+        _lib.check(l.vv_auc_boot_counts(t['order'].data_ptr(), t['tie'].data_ptr(), t['label'].data_ptr(), t['group_off'].data_ptr(),
+                                        t['video_off'].data_ptr(), t['stratum_off'].data_ptr(), n, G, V, t['S'], int(seed), int(r0) + k,
+                                        m, AUC_UNITS[unit], int(block), out[k:].data_ptr(), work.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream), 'vv_auc_boot_counts')
+    return out
+
+
+def auc_counts(scores, labels, video_idx, groups, unit, block, seed, r0, R, strata=None):
+    """Weighted Mann-Whitney counts of bootstrap replicates on the GPU: host int64 ``[R, G, 3]``, row ``(U2, P, N)`` of replicate ``r0 +
+    k`` and group ``g`` -- ``P`` / ``N`` the weighted positive / negative frames of the group, ``U2`` = twice the weighted pairs
+    (positive above negative) plus the tied ones; the group's AUROC is ``U2 / (2 P N)``.  scores / labels / video_idx / groups / strata:
+    as for ``auc_tables``.  unit: ``'none'`` (the full sample, every weight 1, ``R = 1``), ``'video'`` (cluster bootstrap: in every
+    stratum as many videos are drawn with replacement as it holds) or ``'block'`` (moving-block bootstrap inside every video: ``ceil(L /
+    b)`` blocks of ``b = min(block, L)`` frames; the weighted length ``k * b`` is not trimmed to ``L``).  The draws are a counter-based
+    function of ``(seed, replicate, stratum or video, draw)`` (``include/vecvad_hip.h``): they do not depend on the scores, and
+    replicates ``1..R`` in one call equal ``1..k`` and ``k+1..R`` in two."""
+    if not torch.cuda.is_available():
+        raise _lib.VecVadHipError('auc_counts needs a GPU; vec_vad_amd has no CPU path')
+    dev = scores.device if torch.is_tensor(scores) and scores.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    t = auc_tables_device(auc_tables(scores, labels, video_idx, groups, strata), dev)
+    return auc_counts_device(t, unit, block, seed, r0, R).cpu().numpy()
+
+
+def auc_statistic(counts):
+    """The statistic of one replicate from its ``[G, 3]`` counts, in float64 on the host: the mean (``math.fsum``) over the valid groups
+    -- ``P > 0 and N > 0`` -- of ``float(U2) / (2.0 * float(P) * float(N))``; a group with one class only is skipped, a replicate
+    without a valid group is invalid: ``(nan, 0)``.  Returns ``(statistic, valid groups)``."""
+    aucs = [float(int(u2)) / (2.0 * float(int(p)) * float(int(q))) for u2, p, q in np.asarray(counts).reshape(-1, 3) if p > 0 and q > 0]
+    return (math.fsum(aucs) / len(aucs), len(aucs)) if aucs else (float('nan'), 0)
+
+
+def auc_interval(replicates, confidence, what='auc_bootstrap'):
+    """The percentile interval of ``[R]`` replicate statistics (NaN = invalid): with ``a`` the ascending valid ones and ``M`` their number,
+    ``k = ((100 - confidence) * (M - 1)) // 200``, ``lo = a[k]``, ``hi = a[M - 1 - k]``.  When more than 5 % of the replicates are invalid
+    (``n_invalid * 20 > R``) or none is valid the interval is NaN, and in the first case a warning names the count.  Returns ``(lo, hi,
+    n_invalid)``."""
+    reps = np.asarray(replicates, np.float64).reshape(-1)
+    a = np.sort(reps[~np.isnan(reps)])
+    n_invalid = int(reps.size - a.size)
+    if n_invalid * 20 > reps.size:
+        import warnings
+        warnings.warn('%s: %d of %d replicates are invalid (more than 5 %%): no interval is given' % (what, n_invalid, reps.size))
+        return float('nan'), float('nan'), n_invalid
+    if a.size == 0:
+        return float('nan'), float('nan'), n_invalid
+    k = ((100 - int(confidence)) * (a.size - 1)) // 200
+    return float(a[k]), float(a[a.size - 1 - k]), n_invalid
+
+
+def auc_bootstrap(scores, labels, video_idx, scene_idx=None, replicates=1000, unit='block', block=25, seed=0, confidence=95):
+    """Micro and macro AUROC of a score vector with bootstrap percentile intervals (``[mi355x] auc_statistics``).  Returns ``{'micro':
+    entry, 'macro': entry}``.  micro: one group -- or, with ``scene_idx`` (``[n]`` integers), one group per scene, the reference's
+    per-scene mean, with the scenes as the strata of the video bootstrap; macro: one group per video, the mean of the per-video AUROCs.
+    An entry holds ``auc`` (the full-sample statistic, ``auc_statistic``), ``replicates`` (float64 ``[R]``, NaN where a replicate has no
+    valid group), ``lo`` / ``hi`` / ``n_invalid`` (``auc_interval``), ``n_groups_valid`` (groups of the full sample with both classes)
+    and the settings ``n_replicates``, ``unit``, ``block``, ``seed``, ``confidence``.  ``replicates = 0``: the statistics alone.  The
+    pair counts of every replicate come from the GPU as integers (``auc_counts``); the statistic is formed here in float64.  A group
+    with one class only -- a video without an anomalous frame, say -- is skipped in the mean, in the full sample and in every
+    replicate on its own.  ``block = 25`` is an untuned pick and no claim of coverage is made for it."""
+    st = auc_settings(replicates, unit, block, seed, confidence)
+    if not torch.cuda.is_available():
+        raise _lib.VecVadHipError('auc_bootstrap needs a GPU; vec_vad_amd has no CPU path')
+    dev = scores.device if torch.is_tensor(scores) and scores.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    scores = np.asarray(scores.cpu() if torch.is_tensor(scores) else scores, np.float64).reshape(-1)
+    starts, _ = _runs('auc_bootstrap: video_idx', video_idx, scores.size)
+    video = np.repeat(np.arange(starts.size - 1), np.diff(starts))
+    out, work = {}, None
+    for name, groups in (('micro', scene_idx), ('macro', video)):
+        t = auc_tables_device(auc_tables(scores, labels, video, groups, scene_idx), dev)
+        full = auc_counts_device(t, 'none', 1, 0, 1, 1).cpu().numpy()[0]
+        auc, n_valid = auc_statistic(full)
+        reps = np.zeros(0, np.float64)
+        if st['n_replicates']:
+            work = torch.empty(min(AUC_WORK_BYTES, max(8, int(_lib.lib().vv_auc_boot_work(t['n'], t['V'], st['n_replicates'],
+                                                                                         AUC_UNITS[st['unit']])))),
+                               dtype=torch.uint8, device=dev) if work is None else work
+            counts = auc_counts_device(t, st['unit'], st['block'], st['seed'], 1, st['n_replicates'], work=work).cpu().numpy()
+            reps = np.array([auc_statistic(c)[0] for c in counts], np.float64)
+        lo, hi, n_invalid = auc_interval(reps, st['confidence'], 'auc_bootstrap (%s)' % name) if reps.size else (float('nan'), float('nan'), 0)
+        out[name] = dict(auc=auc, replicates=reps, lo=lo, hi=hi, n_invalid=n_invalid, n_groups_valid=n_valid, **st)
+    return out
+
+
+def auc_paired(boot_a, boot_b):
+    """The paired comparison ``a - b`` of two ``auc_bootstrap`` results (or of two of their entries) made with the same seed and settings:
+    the draws do not depend on the scores, so replicate ``r`` of both saw the same resample.  Per entry: ``diff`` (``a.auc - b.auc``),
+    ``replicates`` (the per-replicate differences, NaN where either side is invalid), ``lo`` / ``hi`` / ``n_invalid`` by the rule of
+    ``auc_interval`` on the differences, and ``frac_le0``: the share of the replicates valid on both sides whose difference is ``<= 0``
+    (NaN without one).  That share is reported as it is; it is not a p-value."""
+    if 'micro' in boot_a or 'micro' in boot_b:
+        return {k: auc_paired(boot_a[k], boot_b[k]) for k in ('micro', 'macro')}
+    keys = ('n_replicates', 'unit', 'block', 'seed', 'confidence')
+    if any(boot_a[k] != boot_b[k] for k in keys) or len(boot_a['replicates']) != len(boot_b['replicates']):
+        raise ValueError('auc_paired: the two results were made with different settings: %s against %s' % (
+            {k: boot_a[k] for k in keys}, {k: boot_b[k] for k in keys}))
+    d = np.asarray(boot_a['replicates'], np.float64) - np.asarray(boot_b['replicates'], np.float64)
+    lo, hi, n_invalid = auc_interval(d, boot_a['confidence'], 'auc_paired') if d.size else (float('nan'), float('nan'), 0)
+    ok = d[~np.isnan(d)]
+    return dict(diff=float(boot_a['auc']) - float(boot_b['auc']), replicates=d, lo=lo, hi=hi, n_invalid=n_invalid,
+                frac_le0=float((ok <= 0).sum()) / ok.size if ok.size else float('nan'))
+
+
+def auc_flatten(result, prefix=''):
+    """``{'micro': entry, 'macro': entry}`` -> one flat dict of arrays with ``micro_`` / ``macro_`` prefixed keys, for ``np.savez``."""
+    return {'%s%s_%s' % (prefix, name, k): np.asarray(v) for name in ('micro', 'macro') for k, v in result[name].items()}
 
 
 def roc_auc(scores, labels):
