@@ -212,6 +212,21 @@ def test_video_idx(c):
                                           border_mode='hard').frame_video_idx)
 
 
+def render_sources(c, flow=False):
+    """What ``[mi355x] render`` decodes: ``(frames, flows)``, the test split's frame indexer over ``raw_datasets/<ds>`` without a context
+    (the raw dataset of ``_datasets`` at ``context_frame_num = 0``: ``get_inputs(frames.all_frame_addr[i])`` is frame ``i`` as the
+    extractors decode it, BGR uint8 ``[h,w,3]``) and, with ``flow``, the same over ``optical_flow/<ds>`` (float32 ``[h,w,2]`` per frame: the
+    field ``calc_optical_flow`` stores for it), else None.  No box, no ground truth; nothing is decoded here."""
+    ds = c['dataset_name']
+    kw = dict(dataset_name=ds, mode='test', border_mode='hard', context_frame_num=0)
+    frames = unified_dataset_interface(dir=os.path.join('raw_datasets', ds), file_format=frame_size[ds][2], **kw)
+    flows = unified_dataset_interface(dir=os.path.join('optical_flow', ds), file_format='.npy', **kw) if flow else None
+    if flows is not None and len(flows) != len(frames):
+        raise ValueError('[mi355x] render_flow = True: optical_flow/{} holds the flow of {} test frames, raw_datasets/{} {} frames'.format(
+            ds, len(flows), ds, len(frames)))
+    return frames, flows
+
+
 def frame_cubes(raw_ds, flow_ds, idx, motion_thr, device='cuda'):
     """Cubes of frame ``idx`` that pass the motion test: (raw ``[m,(T,)P,P,3]`` uint8, flow ``[m,(Tf,)P,P,2]`` float32,
     kept box indices).  Flow energy per box = sum of squares over the patch (mean over the context frames when there is a

@@ -744,6 +744,45 @@ int vv_auc_boot_counts(const int32_t* order, const int32_t* tie, const uint8_t* 
                        const int32_t* video_off, const int32_t* stratum_off, int32_t n, int32_t G, int32_t V, int32_t S, uint64_t seed,
                        int64_t r0, int32_t R, int32_t unit, int32_t block, int64_t* out, void* work, vv_stream stream);
 
+/* ---- pictures ([mi355x] render): flow fields in the Middlebury colour coding, and frames with the score mask, the scored boxes and
+ * the ground-truth contour drawn over them.  Both outputs are uint8 [n][h][w][3] in RGB order ----
+ * vv_flow_color: flow float [n][h][w][2] (u, v), 8-byte aligned -> out.  Per image, in float32:
+ *   a pixel with |u| > 1e7 or |v| > 1e7 is "unknown": it counts as (0, 0) for the maximum and is painted (0, 0, 0).  A pixel with a NaN
+ *   component is treated the same way -- a stated deviation: in the original flow_to_image one NaN turns the whole image black;
+ *   R = maxrad when maxrad > 0 (one fixed radius for every image, so that a video does not flicker; the original has no such mode), else
+ *     R = max(-1, max over the image of sqrt(u*u + v*v)), product and sum rounded separately (no fused multiply-add), one reduction per
+ *     image through one partial maximum per 4096 pixels in `work`: exact, bit-identical run to run, and an image never sees another's;
+ *   u, v /= (R + 2^-52); rad = sqrt(u*u + v*v); a = atan2(-v, -u) / pi; fk = (a + 1) / 2 * 54 + 1; k0 = floor(fk); k1 = k0 + 1 (56 -> 1);
+ *   f = fk - k0; per channel col = (1 - f) * wheel[k0-1] / 255 + f * wheel[k1-1] / 255; rad <= 1 ? col = 1 - rad * (1 - col) : col *= 0.75;
+ *   the byte is floor(255 * col).  wheel: the 55 x 3 Middlebury table (RY 15, YG 6, GC 4, CB 11, BM 13, MR 6), in constant memory.
+ *   The sign of a zero counts: v = +0.0 and v = -0.0 with u > 0 land on opposite ends of the wheel (atan2(-/+0, -u) = -/+pi), as in the
+ *   original.  Against the float64 original a byte differs by at most 1, except where rad lies within rounding of 1 (the branch above).
+ *   work: vv_flow_color_work(n, h, w) bytes, 4-byte aligned; not looked at (NULL allowed) when maxrad > 0; -1 for sizes vv_flow_color
+ *   refuses.  VV_ERR_BAD_ARG: negative sizes, h * w > 2^31 - 4097, a NaN maxrad, NULL flow / out (/ work in per-image mode) with something
+ *   to do, a misaligned flow or work.  n == 0 or h * w == 0: VV_OK, no pointer is looked at.
+ * vv_render_overlay: frames uint8 [n][h][w][c], c = 1 (grey, replicated) or 3 (bgr != 0: stored B, G, R, the project's order; else R, G,
+ *   B); mask double [n][h][w] (vv_paint_masks / vv_smooth_masks output), VV_RENDER_UNPAINTED = unpainted; gt uint8 [n][h][w] or NULL;
+ *   rects int32 [n_boxes][4] rows (y0, y1, x0, x1), 16-byte aligned and resolved by the host as for vv_paint_masks, scores double
+ *   [n_boxes], frame_off int32 [n + 1] CSR offsets of every frame's boxes (n_boxes == 0: none of the three is looked at, NULL allowed);
+ *   lut uint8 [256][3] RGB.  With q(v) = 0 for v <= lo, 255 for v >= hi, else (int)floor((v - lo) / (hi - lo) * 255.0) in double, every
+ *   operation rounded once (a +100000 box comes out as 255), later rules win, per pixel:
+ *     1. the frame's RGB;
+ *     2. mask != unpainted: every channel becomes (base * (256 - alpha) + lut[q(mask)] * alpha + 128) >> 8;
+ *     3. the pixel lies on the outline of a non-empty rectangle of its frame -- inside it and on row y0 or y1 - 1 or column x0 or x1 - 1
+ *        --: lut[q(s)], opaque, s = the largest score among those rectangles;
+ *     4. gt given, gt != 0 here and a 4-neighbour is zero or outside the frame: white.
+ *   Integer arithmetic and single IEEE double operations: the result is exact (tests/render_restatement.py, bit for bit).  Any number
+ *   of boxes per frame, staged through LDS 256 at a time; no atomics; no work buffer.  NaN mask values and scores are outside the
+ *   domain.  VV_ERR_BAD_ARG: negative sizes, h * w > 2^31 - 1025, c outside {1, 3}, alpha outside 0..256, hi <= lo (or a NaN), NULL
+ *   frames / mask / lut / out with something to do, NULL rects / scores / frame_off with n_boxes > 0, misaligned rects; nothing is
+ *   written.  n == 0 or h * w == 0: VV_OK. */
+#define VV_RENDER_UNPAINTED (-100000.0)
+int64_t vv_flow_color_work(int32_t n, int32_t h, int32_t w);
+int vv_flow_color(const float* flow, int32_t n, int32_t h, int32_t w, float maxrad, uint8_t* out, void* work, vv_stream stream);
+int vv_render_overlay(const uint8_t* frames, int32_t c, int32_t bgr, const double* mask, const uint8_t* gt, const int32_t* rects,
+                      const double* scores, const int32_t* frame_off, int32_t n_boxes, const uint8_t* lut, double lo, double hi,
+                      int32_t alpha, int32_t n, int32_t h, int32_t w, uint8_t* out, vv_stream stream);
+
 /* library self-description */
 const char* vv_version(void);
 /* text for a value returned by any entry point (a pure function of its argument: pointer to a static string; for

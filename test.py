@@ -60,6 +60,14 @@ the micro AUROC (per-scene mean for ShanghaiTech) and the macro AUROC (mean of t
 GPU in integers), and the paired difference of every non-plain vector against its plain counterpart (``scoring.auc_paired``).  Writes
 ``<modality>_<fg>_<method>_<name>_bootstrap.npz`` and prints one line per statistic.  Every other file is what a run without the key
 writes.  The default block length is an untuned pick: no accuracy claim follows from an interval made with it.
+
+``[mi355x] render = True`` (default False) writes pictures a person can look at: after all scoring (and after the smooth stage) one
+``_render_stage`` runs over the kept groups and writes ``results/<ds>/render/<frame>.png`` for every ``render_every``-th test frame -- the
+frame with the score mask (``render_source``: ``score`` or ``smooth``) blended over it through a colour table that spans ``render_range``,
+the outlines of the scored boxes, the contour of the per-pixel ground truth where the tree has one (UCSDped2 / avenue) and, with
+``render_flow``, the Middlebury colour image of the frame's flow field to the right (``vec_vad_amd/render.py``; both composed on the GPU).
+Staged route, direct route and direct route in parts write the same pictures.  With ``scores_saved = True`` nothing is scored, so nothing
+is rendered.  Every other file is what a run without the key writes.
 """
 import os
 import sys
@@ -250,9 +258,9 @@ class PixelEval:
     words and false-positive scores --, which ``region_state`` turns into the lists the curves are made of.  Frames must arrive in
     increasing order, each once.  ``criterion = False`` keeps a ground-truth source without the pixel scores (``out`` not needed).
 
-    ``smooth`` (``[mi355x] smooth_masks``): every call appends its scored groups -- (off over all test frames, device cube scores, device
+    ``smooth`` (``[mi355x] smooth_masks`` and ``render``): every call appends its scored groups -- (off over all test frames, device cube scores, device
     rectangles), 24 B per cube -- to ``smooth_groups``, across the parts of ``score_store``, for the one ``_smooth_stage`` that runs after
-    all scoring."""
+    all scoring, and for ``_render_stage`` after it."""
 
     def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64, maps=False, error_dir=None,
                  out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None, smooth=False):
@@ -409,6 +417,16 @@ def _mask_lists(result_dir, pixel):
             [] if maps else None)
 
 
+def _paint_frames(groups, a, b, h, w, device):
+    """The score masks of frames ``[a, b)`` on the device, float64 ``[b-a,h,w]``: every scored group of ``groups`` ((off over all frames, device
+    cube scores, device rectangles) each) painted into one buffer of ``-BIG``."""
+    masks = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
+    for off, sc, rc in groups:
+        if off[b] > off[a]:
+            scoring.paint_masks(sc, off[a:b + 1], rc, h, w, out=masks)
+    return masks
+
+
 def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixels, frames_per_chunk, device, gt=None, percent=40,
                   result_dir=None):
     """``[mi355x] smooth_masks``: the score masks of all ``n_frames`` test frames, smoothed (``scoring.smooth_masks``), in chunks
@@ -430,10 +448,7 @@ def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixel
     for a in range(0, n_frames, frames_per_chunk):
         b = min(a + frames_per_chunk, n_frames)
         pa, pb = max(0, a - rt), min(n_frames, b + rt)
-        masks = torch.full((pb - pa, h, w), -float(BIG), dtype=torch.float64, device=device)
-        for off, sc, rc in groups:
-            if off[pb] > off[pa]:
-                scoring.paint_masks(sc, off[pa:pb + 1], rc, h, w, out=masks)
+        masks = _paint_frames(groups, pa, pb, h, w, device)
         smoothed, fmax = scoring.smooth_masks(masks, video_idx[pa:pb], smooth_frames, smooth_pixels, lo=a - pa, hi=b - pa)
         fs[a:b] = fmax
         if gt is not None:
@@ -443,6 +458,96 @@ def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixel
             for f in range(a, b):
                 torch.save(smoothed[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))
     return fs.cpu().numpy(), ps.cpu().numpy() if ps is not None else None
+
+
+def _render_range(groups, setting):
+    """``[mi355x] render_range``: the ``(lo, hi)`` the colour table spans.  ``'auto'``: the smallest and the largest cube score of the
+    run (``groups`` as for ``_smooth_stage``) among those with ``|v| < BIG`` -- the same for both sources; ``(0, 1)`` when there is none
+    or they are equal."""
+    if setting != 'auto':
+        return float(setting[0]), float(setting[1])
+    lo = hi = None
+    for _, sc, _ in groups:
+        v = sc[sc.abs() < BIG]
+        if v.numel():
+            lo = float(v.min()) if lo is None else min(lo, float(v.min()))
+            hi = float(v.max()) if hi is None else max(hi, float(v.max()))
+    return (0.0, 1.0) if lo is None or lo == hi else (lo, hi)
+
+
+def _render_stage(c, groups, n_frames, h, w, device, out_dir, gt=None, video_idx=None, flownet2=None):
+    """``[mi355x] render``: ``<out_dir>/<frame>.png`` for every ``render_every``-th test frame -- the frame with its score mask, the
+    outlines of its scored boxes and the contour of its ground truth drawn over it (``render.overlay``) and, with ``render_flow``, the
+    colour image of its flow field to the right (``render.flow_color``; ``[h, 2w, 3]``).  ``groups``: every scored group of the test set,
+    as for ``_smooth_stage``.  Per chunk of ``direct_frames_per_chunk`` frames the picked frames are decoded and uploaded once, the chunk's
+    masks are painted on the device (``render_source = smooth``: painted with the temporal halo and filtered as ``_smooth_stage`` does, so
+    the values are those of the ``score_mask_smooth`` files; ``video_idx``: the video of every test frame), the pictures are composed on
+    the device, come to the host in one copy and are written with Pillow (PNG: lossless).  ``gt``: a ground-truth source or None.  The
+    flow of a frame is the field ``calc_optical_flow`` stores for it: read from ``optical_flow/``, or with ``direct_flow`` recomputed from
+    the frames (``calc_optical_flow.flow_pairs`` + ``chunk_flows`` with ``flownet2``, ``direct_flow_pairs`` pairs per launch).  Returns the
+    number of pictures written."""
+    from PIL import Image
+    from foreground import render_sources
+    from vad_datasets import get_inputs
+    from vec_vad_amd import render
+    flow_files = c['render_flow'] and not c['direct_flow']
+    frames_ds, flows_ds = render_sources(c, flow=flow_files)
+    if len(frames_ds) != n_frames:
+        raise ValueError('[mi355x] render: the test split indexes {} frames, {} test frames are scored'.format(len(frames_ds), n_frames))
+    if c['render_flow'] and not flow_files:
+        from calc_optical_flow import chunk_flows, flow_pairs, load_flownet2
+        if flownet2 is None:
+            flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
+    smooth = c['render_source'] == 'smooth'
+    if smooth:
+        video_idx = np.asarray(video_idx).reshape(-1)
+        if video_idx.size != n_frames:
+            raise ValueError('[mi355x] render: the test split indexes {} frames, {} test frames are scored'.format(video_idx.size, n_frames))
+    rt = c['smooth_frames'] // 2 if smooth else 0
+    lo, hi = _render_range(groups, c['render_range'])
+    alpha = (256 * c['render_alpha'] + 50) // 100
+    lut = render.colormap()
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for a in range(0, n_frames, c['direct_frames_per_chunk']):
+        b = min(a + c['direct_frames_per_chunk'], n_frames)
+        sel = [f for f in range(a, b) if f % c['render_every'] == 0]
+        if not sel:
+            continue
+        whole = len(sel) == b - a
+        pa, pb = max(0, a - rt), min(n_frames, b + rt)
+        masks = _paint_frames(groups, pa, pb, h, w, device)
+        if smooth:
+            masks, _ = scoring.smooth_masks(masks, video_idx[pa:pb], c['smooth_frames'], c['smooth_pixels'], lo=a - pa, hi=b - pa)
+        if not whole:
+            masks = masks.index_select(0, torch.tensor([f - a for f in sel], device=device))
+        off_s, sc_s, rc_s = scoring.merge_groups([], n_frames=len(sel), device=device)      # no box
+        if c['render_boxes']:
+            off_m, sc_s, rc_s = scoring.merge_groups([(off[a:b + 1], sc, rc) for off, sc, rc in groups], n_frames=b - a, device=device)
+            if not whole:
+                idx = torch.from_numpy(np.concatenate([np.arange(off_m[f - a], off_m[f - a + 1], dtype=np.int64) for f in sel])).to(device)
+                sc_s, rc_s = sc_s.index_select(0, idx), rc_s.index_select(0, idx)
+            off_s = np.concatenate([[0], np.cumsum(np.diff(off_m)[[f - a for f in sel]])]).astype(np.int32)
+        # every frame the chunk needs -- the picked ones and, for a recomputed flow, their partners -- is decoded once
+        pairs = flow_pairs(frames_ds, sel) if c['render_flow'] and not flow_files else []
+        used = sorted(set(sel) | {f for p in pairs for f in p})
+        local = {f: k for k, f in enumerate(used)}
+        decoded = torch.from_numpy(np.ascontiguousarray(np.stack([get_inputs(frames_ds.all_frame_addr[f]) for f in used]))).to(device)
+        picked = decoded if used == sel else decoded.index_select(0, torch.tensor([local[f] for f in sel], device=device))
+        g = torch.from_numpy(np.stack([gt(f) for f in sel])).to(device) if gt is not None else None
+        img = render.overlay(picked, masks, rc_s, sc_s, off_s, lo, hi, alpha, gt=g, lut=lut, bgr=True)
+        if c['render_flow']:
+            if flow_files:
+                fl = torch.from_numpy(np.stack([np.asarray(get_inputs(flows_ds.all_frame_addr[f]), np.float32) for f in sel])).to(device)
+            else:
+                fl = torch.empty((len(sel), h, w, 2), dtype=torch.float32, device=device)
+                chunk_flows(flownet2, decoded, [(local[p], local[q]) for p, q in pairs], np.arange(len(sel)), fl, max(1, c['direct_flow_pairs']))
+            img = torch.cat([img, render.flow_color(fl, c['render_flow_max'])], dim=2)
+        img = img.cpu().numpy()
+        for k, f in enumerate(sel):
+            Image.fromarray(img[k]).save(os.path.join(out_dir, '{}.png'.format(f)))
+        written += len(sel)
+    return written
 
 
 AUC_PLAIN = {'frame_smooth': 'frame', 'pixel_fine': 'pixel', 'pixel_smooth': 'pixel'}      # the plain counterpart of a score vector
@@ -676,7 +781,7 @@ def main(config_path='config.cfg', flownet2=None):
 
         def pixel_eval(n_frames, labels):
             """The ``pixel`` keyword of the scoring calls, or None with both new keys off (today's calls)."""
-            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps and not c['smooth_masks']:
+            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps and not c['smooth_masks'] and not c['render']:
                 return None
             if gt is not None and len(gt) != n_frames:
                 raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
@@ -684,8 +789,8 @@ def main(config_path='config.cfg', flownet2=None):
             # the region keys travel as trailing keywords: with region_criterion off the calls are the ones made before it existed
             rk = dict(criterion=pix_gt, regions=True, region_iou=c['region_iou_percent'], video_idx=gt.frame_video_idx) \
                 if c['region_criterion'] else {}
-            if c['smooth_masks']:      # a trailing keyword too: with the key off the calls are the ones made before it existed
-                rk['smooth'] = True
+            if c['smooth_masks'] or c['render']:      # a trailing keyword too: with both keys off the calls are the ones made before they existed
+                rk['smooth'] = True                   # (the keyword keeps the scored groups: both stages run on them)
             if not maps:
                 made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
                                       **rk))
@@ -733,6 +838,25 @@ def main(config_path='config.cfg', flownet2=None):
             np.save(smooth_fs_path, fs_smooth)
             if ps_smooth is not None:
                 np.save(smooth_ps_path, ps_smooth)
+        if c['render']:
+            # ---- [mi355x] render: pictures of the kept groups, after all scoring (and after the smooth stage, whose masks it may draw)
+            render_gt = gt
+            if render_gt is None and not shanghai:
+                from foreground import gt_source
+                try:
+                    render_gt = gt_source(c)      # the contour is drawn where the tree holds per-pixel ground truth
+                except ValueError:
+                    render_gt = None
+            if c['render_source'] != 'smooth':
+                video_idx = None
+            elif render_gt is not None:
+                video_idx = render_gt.frame_video_idx
+            else:
+                from foreground import test_video_idx
+                video_idx = test_video_idx(c)
+            render_dir = os.path.join(results_dir, ds, 'render')
+            print('Rendered {} frames to {}'.format(_render_stage(c, made[0].smooth_groups, len(fs), h, w, device, render_dir, render_gt,
+                                                                    video_idx, flownet2), render_dir))
 
     def region_results():
         """criterion = 'region' / 'track' (scoring.py module docstring): needs no frame labels, only the saved region file."""

@@ -124,7 +124,15 @@ def read_config(path='config.cfg'):
              auc_bootstrap_unit=cp.get('mi355x', 'auc_bootstrap_unit', fallback='block').strip().lower(),
              auc_bootstrap_block=cp.getint('mi355x', 'auc_bootstrap_block', fallback=25),
              auc_bootstrap_seed=cp.getint('mi355x', 'auc_bootstrap_seed', fallback=0),
-             auc_confidence=cp.getint('mi355x', 'auc_confidence', fallback=95))
+             auc_confidence=cp.getint('mi355x', 'auc_confidence', fallback=95),
+             render=cp.getboolean('mi355x', 'render', fallback=False),
+             render_source=cp.get('mi355x', 'render_source', fallback='score').strip().lower(),
+             render_alpha=cp.getint('mi355x', 'render_alpha', fallback=50),
+             render_range=cp.get('mi355x', 'render_range', fallback='auto').strip().lower(),
+             render_every=cp.getint('mi355x', 'render_every', fallback=1),
+             render_boxes=cp.getboolean('mi355x', 'render_boxes', fallback=True),
+             render_flow=cp.getboolean('mi355x', 'render_flow', fallback=False),
+             render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0))
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
@@ -142,6 +150,25 @@ def read_config(path='config.cfg'):
         raise ValueError('[mi355x] auc_bootstrap_seed must be an integer in 0..2^64-1, got {}'.format(c['auc_bootstrap_seed']))
     if not 50 <= c['auc_confidence'] <= 99:
         raise ValueError('[mi355x] auc_confidence must be an integer in 50..99, got {}'.format(c['auc_confidence']))
+    # the settings of the render stage ([mi355x] render), checked whatever the switch says
+    if c['render_source'] not in ('score', 'smooth'):
+        raise ValueError("[mi355x] render_source must be 'score' or 'smooth', got {!r}".format(c['render_source']))
+    if not 0 <= c['render_alpha'] <= 100:
+        raise ValueError('[mi355x] render_alpha must be an integer percent in 0..100, got {}'.format(c['render_alpha']))
+    if c['render_range'] != 'auto':
+        try:
+            lo, hi = (float(t) for t in c['render_range'].split(','))
+        except ValueError:
+            lo = hi = float('nan')
+        if not lo < hi or not abs(lo) < float('inf') or not abs(hi) < float('inf'):
+            raise ValueError("[mi355x] render_range must be 'auto' or two finite numbers lo,hi with lo < hi, got {!r}".format(c['render_range']))
+        c['render_range'] = (lo, hi)
+    if c['render_every'] < 1:
+        raise ValueError('[mi355x] render_every must be a frame stride >= 1, got {}'.format(c['render_every']))
+    if not c['render_flow_max'] >= 0 or c['render_flow_max'] == float('inf'):
+        raise ValueError('[mi355x] render_flow_max must be a finite radius >= 0 (0: every image by its own), got {}'.format(c['render_flow_max']))
+    if c['render'] and c['render_source'] == 'smooth' and not c['smooth_masks']:
+        raise ValueError('[mi355x] render_source = smooth needs smooth_masks = True: only that stage forms the smoothed masks')
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -188,6 +188,10 @@ _SIGS = {
     'vv_auc_boot_work': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     'vv_auc_boot_counts': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.c_uint64, c_i64, c_i32, c_i32, c_i32,
                                    c_vp, c_vp, c_vp]),
+    'vv_flow_color_work': (c_i64, [c_i32, c_i32, c_i32]),
+    'vv_flow_color': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    'vv_render_overlay': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_f64, c_f64, c_i32, c_i32, c_i32, c_i32,
+                                  c_vp, c_vp]),
     'vv_conv2d_f16': (c_i32, [C.POINTER(Conv2dParams), c_vp]),
     'vv_pack_conv2d_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'vv_conv2d_splitk_finish_f16': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_i32, c_vp]),
