@@ -69,6 +69,7 @@ the outlines of the scored boxes, the contour of the per-pixel ground truth wher
 Staged route, direct route and direct route in parts write the same pictures.  With ``scores_saved = True`` nothing is scored, so nothing
 is rendered.  Every other file is what a run without the key writes.
 """
+import collections
 import os
 import sys
 
@@ -121,6 +122,34 @@ def load_artifacts(base, fg, method, shanghai, build_net, device, h_block=1, w_b
     return over(build, weights, weights, depth), over(stat, raw_tr, weights, depth), over(stat, of_tr, weights, depth)
 
 
+def _blank(device, *shape):
+    """Scores ``[n_frames]`` before any cube has been seen, or masks ``[k,h,w]`` without a painted pixel: float64 of ``-BIG``."""
+    return torch.full((*shape,), -float(BIG), dtype=torch.float64, device=device)
+
+
+class _Gathered:
+    """The results of the launches that score a list of ``n`` cubes: raw scores, flow scores and, with ``maps``, the two per-pixel
+    error maps behind them, on the device.  A flow tensor is allocated when the first launch returns one, so it stays None for a bank
+    without a flow branch."""
+
+    def __init__(self, n, maps, device):
+        self.n, self.maps, self.device = n, maps, device
+        self.parts = [torch.empty(n, device=device), None, torch.empty((n, 32, 32), device=device) if maps else None, None]
+
+    def put(self, s0, m, *launch):
+        """The first ``m`` results of a launch -- (raw, of | None), with ``maps`` followed by (e_raw, e_of | None) -- are those of
+        cubes ``[s0, s0 + m)``."""
+        for k, x in enumerate(launch):
+            if x is not None:
+                if self.parts[k] is None:
+                    self.parts[k] = torch.empty((self.n,) + x.shape[1:], device=self.device)
+                self.parts[k][s0:s0 + m] = x[:m]
+
+    def result(self):
+        """(raw [n], of [n] | None), with ``maps`` followed by (e_raw [n,32,32], e_of [n,32,32] | None)."""
+        return tuple(self.parts if self.maps else self.parts[:2])
+
+
 def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=None, maps=False):
     """cube_list / flow_list: per-frame arrays [n_i,5,32,32,3] uint8 / [n_i,(Tf,)32,32,2] fp32 (n_i may be 0).
     The cubes go to the GPU in bounded super-chunks (``chunk_cubes``, default 32 launches' worth, >= 4096: ~55 KB per cube for the
@@ -149,32 +178,20 @@ def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=N
     r0, f0 = prep(keep[0])
     rawd = torch.empty((cap,) + r0.shape[1:], dtype=torch.uint8, device=dev)
     flowd = torch.empty((cap,) + f0.shape[1:], dtype=torch.float32, device=dev)
-    r_all = torch.empty(n, device=dev)
-    o_all = None
-    er_all, eo_all = torch.empty((n, 32, 32), device=dev) if maps else None, None
+    gathered = _Gathered(n, maps, dev)
     done = 0
     pend_r, pend_f, pend_n = [], [], 0
 
     def flush():
-        nonlocal done, pend_r, pend_f, pend_n, o_all, eo_all
+        nonlocal done, pend_r, pend_f, pend_n
         m_tot = pend_n
         if not m_tot:
             return
         rawd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_r))))
         flowd[:m_tot].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate(pend_f))))
         # launches of B cubes whatever the chunk holds: B comes from the whole list, and the bank picks its kernels by it
-        r, o, *e = score_index_list(trainer, rawd, flowd, torch.arange(m_tot, device=dev), score_batch, batch=B, maps=maps)
-        r_all[done:done + m_tot] = r
-        if maps:
-            er_all[done:done + m_tot] = e[0]
-            if e[1] is not None:
-                if eo_all is None:
-                    eo_all = torch.empty((n, 32, 32), device=dev)
-                eo_all[done:done + m_tot] = e[1]
-        if o is not None:
-            if o_all is None:
-                o_all = torch.empty(n, device=dev)
-            o_all[done:done + m_tot] = o
+        gathered.put(done, m_tot, *score_index_list(trainer, rawd, flowd, torch.arange(m_tot, device=dev), score_batch, batch=B,
+                                                    maps=maps))
         done += m_tot
         pend_r, pend_f, pend_n = [], [], 0
 
@@ -190,7 +207,7 @@ def score_cubes_device(trainer, cube_list, flow_list, score_batch, chunk_cubes=N
             if pend_n == cap:
                 flush()
     flush()
-    return (r_all, o_all, er_all, eo_all) if maps else (r_all, o_all)
+    return gathered.result()
 
 
 def score_cubes_batched(trainer, cube_list, flow_list, score_batch):
@@ -229,9 +246,18 @@ def _mask_scores(r, o, stats, w_raw, w_of, trained):
     return sc
 
 
+def _save_frames(out_dir, first_frame, masks):
+    """THE mask writer: ``<out_dir>/<first_frame + k>`` for every mask of ``masks`` (float64 ``[k,h,w]``, device tensor, host tensor or
+    array; a device tensor comes to the host in one copy).  Every file is the torch pickle of an array of its own, C-contiguous, as
+    the reference saves its masks (test.py:358).  ``out_dir`` exists: the stage that writes there makes it once."""
+    masks = masks.cpu().numpy() if torch.is_tensor(masks) else masks
+    for k in range(len(masks)):
+        torch.save(masks[k].copy(), os.path.join(out_dir, '{}'.format(first_frame + k)))
+
+
 def _save_masks(result_dir, frames, mask_groups, h, w):
-    """``<result_dir>/<frame>`` for every frame of ``frames``: one h x w float64 mask alive at a time, like the reference
-    (test.py:350-358).  mask_groups: (off indexed by frame, host cube scores, boxes) per scored group."""
+    """``<result_dir>/<frame>`` for every frame of ``frames``, painted on the host: one h x w float64 mask alive at a time, like the
+    reference (test.py:350-358).  mask_groups: (off indexed by frame, host cube scores, boxes) per scored group."""
     os.makedirs(result_dir, exist_ok=True)
     for f in frames:
         fmap = -1.0 * np.ones((h, w)) * BIG
@@ -239,7 +265,29 @@ def _save_masks(result_dir, frames, mask_groups, h, w):
             if off[f + 1] > off[f]:
                 sl = slice(off[f], off[f + 1])
                 np.maximum(fmap, paint_frame(sc[sl], boxes[sl], h, w), out=fmap)
-        torch.save(fmap, os.path.join(result_dir, '{}'.format(f)))
+        _save_frames(result_dir, f, fmap[None])
+
+
+def _frame_chunks(first, end, per_chunk, halo=0):
+    """Frames ``[first, end)`` in chunks of ``per_chunk``: ``(a, b, pa, pb)`` per chunk ``[a, b)``, with ``[pa, pb)`` the chunk widened by
+    ``halo`` frames on either side and clamped to the frames that exist, ``[0, end)`` -- what a temporal window around the chunk's
+    frames reads."""
+    for a in range(first, end, per_chunk):
+        b = min(a + per_chunk, end)
+        yield a, b, max(0, a - halo), min(end, b + halo)
+
+
+def _gt_chunk(gt, frames, device):
+    """The per-pixel ground truth of ``frames`` (``gt``: a ground-truth source) on the device, uint8 ``[len(frames),h,w]``, in one upload."""
+    return torch.from_numpy(np.stack([gt(i) for i in frames])).to(device)
+
+
+def _video_idx(c, gt):
+    """The video of every test frame: the open ground-truth source knows it, otherwise the test split is indexed for it."""
+    if gt is not None:
+        return gt.frame_video_idx
+    from foreground import test_video_idx
+    return test_video_idx(c)
 
 
 class PixelEval:
@@ -258,12 +306,12 @@ class PixelEval:
     words and false-positive scores --, which ``region_state`` turns into the lists the curves are made of.  Frames must arrive in
     increasing order, each once.  ``criterion = False`` keeps a ground-truth source without the pixel scores (``out`` not needed).
 
-    ``smooth`` (``[mi355x] smooth_masks`` and ``render``): every call appends its scored groups -- (off over all test frames, device cube scores, device
-    rectangles), 24 B per cube -- to ``smooth_groups``, across the parts of ``score_store``, for the one ``_smooth_stage`` that runs after
-    all scoring, and for ``_render_stage`` after it."""
+    ``keep_groups`` (``[mi355x] smooth_masks`` or ``render``): every call appends its scored groups -- (off over all test frames, device
+    cube scores, device rectangles), 24 B per cube -- to ``groups``, across the parts of ``score_store``.  Both ``_smooth_stage`` and
+    ``_render_stage`` read them, once, after all scoring; without the keyword ``groups`` is None."""
 
     def __init__(self, gt=None, percent=40, out=None, labels=None, device_masks=False, frames_per_chunk=64, maps=False, error_dir=None,
-                 out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None, smooth=False):
+                 out_fine=None, criterion=True, regions=False, region_iou=10, video_idx=None, keep_groups=False):
         self.gt, self.percent, self.out, self.labels = gt, int(percent), out, labels
         self.device_masks, self.frames_per_chunk = bool(device_masks), max(1, int(frames_per_chunk))
         self.maps, self.error_dir, self.out_fine = bool(maps), error_dir, out_fine
@@ -277,7 +325,7 @@ class PixelEval:
             raise ValueError('PixelEval: regions need a ground-truth source and the video index of every frame')
         self.prev_labels, self.next_frame = None, 0        # label map of frame next_frame - 1 (device), the frame expected next
         self.region_chunks = []                            # per chunk: (first frame, n_regions, area, score, links, fp scores), host
-        self.smooth_groups = [] if smooth else None        # every scored group of the test set, for _smooth_stage
+        self.groups = [] if keep_groups else None          # every scored group of the test set, for _smooth_stage and _render_stage
 
     def region_stage(self, gt, off, scores, rects, a, b):
         """The region stage of frames ``[a, b)``: ``gt`` the chunk's uploaded ground truth, (off, scores, rects) its merged cubes."""
@@ -322,13 +370,12 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
         os.makedirs(result_dir, exist_ok=True)
     if map_groups is not None and pixel.error_dir:
         os.makedirs(pixel.error_dir, exist_ok=True)
-    for a in range(first, end, pixel.frames_per_chunk):
-        b = min(a + pixel.frames_per_chunk, end)
+    for a, b, _, _ in _frame_chunks(first, end, pixel.frames_per_chunk):
         sub = [(off[a:b + 1], sc, rc) for off, sc, rc in dev_groups]
         gt = None
         if pixel.gt is not None:
             off, sc, rc = scoring.merge_groups(sub, n_frames=b - a, device=device)
-            gt = torch.from_numpy(np.stack([pixel.gt(i) for i in range(a, b)])).to(device)
+            gt = _gt_chunk(pixel.gt, range(a, b), device)
             if pixel.regions:
                 pixel.region_stage(gt, off, sc, rc, a, b)
             cnt = None
@@ -340,15 +387,9 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
                     raise ValueError('frame {}: its label and its per-pixel ground truth disagree on whether it is anomalous'.format(
                         a + int(bad[0])))
         if paint:
-            masks = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
-            for off, sc, rc in sub:
-                if off[-1] > off[0]:
-                    scoring.paint_masks(sc, off, rc, h, w, out=masks)
-            masks = masks.cpu().numpy()
-            for f in range(a, b):
-                torch.save(masks[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))      # its own array, as _save_masks saves
+            _save_frames(result_dir, a, _paint_frames(dev_groups, a, b, h, w, device))
         if map_groups is not None:
-            fine = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
+            fine = _blank(device, b - a, h, w)
             for (off, _, rc), kept in zip(sub, map_groups):
                 lo, hi = int(off[0]), int(off[-1])
                 if hi <= lo:
@@ -364,9 +405,7 @@ def _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_gr
             if gt is not None and pixel.criterion:
                 scoring.mask_pixel_scores(gt, fine, pixel.percent, out=pixel.out_fine[a:b])
             if pixel.error_dir:
-                fine = fine.cpu().numpy()
-                for f in range(a, b):
-                    torch.save(fine[f - a].copy(), os.path.join(pixel.error_dir, '{}'.format(f)))
+                _save_frames(pixel.error_dir, a, fine)
 
 
 def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, trainers, fs_dev, mask_groups, dev_groups=None,
@@ -408,19 +447,19 @@ def _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, devi
 
 def _mask_lists(result_dir, pixel):
     """(mask_groups, dev_groups, map_groups) for a call: the host list feeds ``_save_masks``, the device lists ``_pixel_stage`` (and,
-    with ``pixel.smooth_groups``, ``_smooth_stage`` once every call has been made)."""
+    with ``pixel.groups``, ``_smooth_stage`` and ``_render_stage`` once every call has been made)."""
     device_masks = pixel is not None and pixel.device_masks
     maps = pixel is not None and pixel.maps and (pixel.gt is not None or bool(pixel.error_dir))
-    smooth = pixel is not None and pixel.smooth_groups is not None
+    keep = pixel is not None and pixel.groups is not None
     return ([] if result_dir and not device_masks else None,
-            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir) or maps or smooth) else None,
+            [] if pixel is not None and (pixel.gt is not None or (device_masks and result_dir) or maps or keep) else None,
             [] if maps else None)
 
 
 def _paint_frames(groups, a, b, h, w, device):
-    """The score masks of frames ``[a, b)`` on the device, float64 ``[b-a,h,w]``: every scored group of ``groups`` ((off over all frames, device
-    cube scores, device rectangles) each) painted into one buffer of ``-BIG``."""
-    masks = torch.full((b - a, h, w), -float(BIG), dtype=torch.float64, device=device)
+    """THE mask painter: the score masks of frames ``[a, b)`` on the device, float64 ``[b-a,h,w]`` -- every scored group of ``groups``
+    ((off over all frames, device cube scores, device rectangles) each) painted into one buffer of ``-BIG``."""
+    masks = _blank(device, b - a, h, w)
     for off, sc, rc in groups:
         if off[b] > off[a]:
             scoring.paint_masks(sc, off[a:b + 1], rc, h, w, out=masks)
@@ -440,23 +479,18 @@ def _smooth_stage(groups, video_idx, n_frames, h, w, smooth_frames, smooth_pixel
     if video_idx.size != n_frames:
         raise ValueError('[mi355x] smooth_masks: the test split indexes {} frames, {} test frames are scored'.format(video_idx.size,
                                                                                                                     n_frames))
-    rt = smooth_frames // 2
-    fs = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
+    fs = _blank(device, n_frames)
     ps = fs.clone() if gt is not None else None
     if result_dir:
         os.makedirs(result_dir, exist_ok=True)
-    for a in range(0, n_frames, frames_per_chunk):
-        b = min(a + frames_per_chunk, n_frames)
-        pa, pb = max(0, a - rt), min(n_frames, b + rt)
+    for a, b, pa, pb in _frame_chunks(0, n_frames, frames_per_chunk, halo=smooth_frames // 2):
         masks = _paint_frames(groups, pa, pb, h, w, device)
         smoothed, fmax = scoring.smooth_masks(masks, video_idx[pa:pb], smooth_frames, smooth_pixels, lo=a - pa, hi=b - pa)
         fs[a:b] = fmax
         if gt is not None:
-            scoring.mask_pixel_scores(torch.from_numpy(np.stack([gt(i) for i in range(a, b)])).to(device), smoothed, percent, out=ps[a:b])
+            scoring.mask_pixel_scores(_gt_chunk(gt, range(a, b), device), smoothed, percent, out=ps[a:b])
         if result_dir:
-            smoothed = smoothed.cpu().numpy()
-            for f in range(a, b):
-                torch.save(smoothed[f - a].copy(), os.path.join(result_dir, '{}'.format(f)))
+            _save_frames(result_dir, a, smoothed)
     return fs.cpu().numpy(), ps.cpu().numpy() if ps is not None else None
 
 
@@ -509,13 +543,11 @@ def _render_stage(c, groups, n_frames, h, w, device, out_dir, gt=None, video_idx
     lut = render.colormap()
     os.makedirs(out_dir, exist_ok=True)
     written = 0
-    for a in range(0, n_frames, c['direct_frames_per_chunk']):
-        b = min(a + c['direct_frames_per_chunk'], n_frames)
+    for a, b, pa, pb in _frame_chunks(0, n_frames, c['direct_frames_per_chunk'], halo=rt):
         sel = [f for f in range(a, b) if f % c['render_every'] == 0]
         if not sel:
             continue
         whole = len(sel) == b - a
-        pa, pb = max(0, a - rt), min(n_frames, b + rt)
         masks = _paint_frames(groups, pa, pb, h, w, device)
         if smooth:
             masks, _ = scoring.smooth_masks(masks, video_idx[pa:pb], c['smooth_frames'], c['smooth_pixels'], lo=a - pa, hi=b - pa)
@@ -534,7 +566,7 @@ def _render_stage(c, groups, n_frames, h, w, device, out_dir, gt=None, video_idx
         local = {f: k for k, f in enumerate(used)}
         decoded = torch.from_numpy(np.ascontiguousarray(np.stack([get_inputs(frames_ds.all_frame_addr[f]) for f in used]))).to(device)
         picked = decoded if used == sel else decoded.index_select(0, torch.tensor([local[f] for f in sel], device=device))
-        g = torch.from_numpy(np.stack([gt(f) for f in sel])).to(device) if gt is not None else None
+        g = _gt_chunk(gt, sel, device) if gt is not None else None
         img = render.overlay(picked, masks, rc_s, sc_s, off_s, lo, hi, alpha, gt=g, lut=lut, bgr=True)
         if c['render_flow']:
             if flow_files:
@@ -550,14 +582,43 @@ def _render_stage(c, groups, n_frames, h, w, device, out_dir, gt=None, video_idx
     return written
 
 
-AUC_PLAIN = {'frame_smooth': 'frame', 'pixel_fine': 'pixel', 'pixel_smooth': 'pixel'}      # the plain counterpart of a score vector
+class Vector(collections.namedtuple('Vector', 'name scores needs header summary per_scene device_line plain')):
+    """One row of ``VECTORS``.  ``name``: also the stem of the ROC file; ``scores``: the stem of the score file; ``needs``: the config
+    keys that must all be on for a run to have the vector; ``header`` / ``summary``: the line printed before / after its ROC is written
+    (None: no line; formatted with the config and ``auc``); ``per_scene``: the summary of the per-scene evaluation that ShanghaiTech
+    gets instead (None: evaluated like any dataset); ``device_line``: what the device pair-count line that follows calls the number
+    (None: no such line); ``plain``: the vector its paired bootstrap difference is taken against."""
+    __slots__ = ()
+
+    def scores_path(self, ds, fg, method):
+        return os.path.join('results', ds, '{}_{}_{}.npy'.format(self.scores, fg, method))
+
+    def results_path(self, ds, mod, fg, method, scene=None):
+        return os.path.join('results', ds, '{}_{}_{}_{}_results{}.npz'.format(mod, fg, method, self.name,
+                                                                              '' if scene is None else '_scene_{}'.format(scene)))
+
+
+_SMOOTHED = ' of the smoothed masks ({smooth_frames} frames x {smooth_pixels} x {smooth_pixels} pixels) is {auc}'
+# every score vector a run can have, by name, in the order they are evaluated: plain vectors in front of the ones derived from them
+VECTORS = {v.name: v for v in (
+    Vector('frame', 'frame_scores', (), 'Evaluating {dataset_name} by frame-criterion:', None,
+           'Average frame-level AUC is {auc}', 'AUC@ROC', None),
+    Vector('frame_smooth', 'frame_scores_smooth', ('smooth_masks',), None, 'Frame-level AUC' + _SMOOTHED,
+           'Average frame-level AUC' + _SMOOTHED, None, 'frame'),
+    Vector('pixel', 'pixel_scores', ('pixel_criterion',), 'Evaluating {dataset_name} by pixel-criterion:',
+           'Pixel-level AUC (overlap {pixel_overlap_percent}%) is {auc}', None, 'Pixel-level AUC@ROC', None),
+    Vector('pixel_fine', 'pixel_scores_fine', ('pixel_criterion', 'pixel_maps'), None,
+           'Fine pixel-level AUC (overlap {pixel_overlap_percent}%) is {auc}', None, 'Fine pixel-level AUC@ROC', 'pixel'),
+    Vector('pixel_smooth', 'pixel_scores_smooth', ('pixel_criterion', 'smooth_masks'), None,
+           'Pixel-level AUC of the smoothed masks (overlap {pixel_overlap_percent}%) is {auc}', None, None, 'pixel'),
+)}
 
 
 def _auc_stage(c, vectors, labels, video_idx, scene_idx, path_format, device, log=print):
     """``[mi355x] auc_statistics``: micro and macro AUROC with bootstrap intervals (``scoring.auc_bootstrap``) of every score vector of
     ``vectors`` (name -> host scores ``[n_frames]``; plain vectors in front of the ones derived from them), written to
-    ``path_format.format(name)`` with ``micro_`` / ``macro_`` prefixed keys and printed, one line per statistic.  A vector named in
-    ``AUC_PLAIN`` also gets the paired difference against its plain counterpart (``scoring.auc_paired``; ``paired_`` prefixed keys).
+    ``path_format.format(name)`` with ``micro_`` / ``macro_`` prefixed keys and printed, one line per statistic.  A vector with a
+    ``plain`` counterpart in ``VECTORS`` also gets the paired difference against it (``scoring.auc_paired``; ``paired_`` prefixed keys).
     ``video_idx`` / ``scene_idx``: the video (and, for ShanghaiTech, the scene) of every test frame.  Returns name -> result."""
     video_idx = np.asarray(video_idx).reshape(-1)
     if video_idx.size != len(labels):
@@ -566,6 +627,7 @@ def _auc_stage(c, vectors, labels, video_idx, scene_idx, path_format, device, lo
               confidence=c['auc_confidence'])
     what = '{}% interval of {} {} replicates'.format(kw['confidence'], kw['replicates'], kw['unit'] + (
         ' ({} frames)'.format(kw['block']) if kw['unit'] == 'block' else ''))
+    plain = {name: VECTORS[name].plain for name in vectors if name in VECTORS and VECTORS[name].plain}
     done = {}
     for name, scores in vectors.items():
         res = scoring.auc_bootstrap(torch.from_numpy(np.asarray(scores, np.float64)).to(device), labels, video_idx, scene_idx, **kw)
@@ -574,13 +636,13 @@ def _auc_stage(c, vectors, labels, video_idx, scene_idx, path_format, device, lo
             e = res[kind]
             log('{} {} AUROC is {} [{}, {}] ({}, {} invalid; {} groups with both classes)'.format(
                 name, kind, e['auc'], e['lo'], e['hi'], what, e['n_invalid'], e['n_groups_valid']))
-        if name in AUC_PLAIN:
-            pair = scoring.auc_paired(res, done[AUC_PLAIN[name]])
+        if name in plain:
+            pair = scoring.auc_paired(res, done[plain[name]])
             flat.update(scoring.auc_flatten(pair, 'paired_'))
             for kind in ('micro', 'macro'):
                 e = pair[kind]
                 log('{} - {} {} AUROC is {} [{}, {}] ({} invalid; share of replicates with a difference <= 0: {})'.format(
-                    name, AUC_PLAIN[name], kind, e['diff'], e['lo'], e['hi'], e['n_invalid'], e['frac_le0']))
+                    name, plain[name], kind, e['diff'], e['lo'], e['hi'], e['n_invalid'], e['frac_le0']))
         np.savez(path_format.format(name), **flat)
         log('Results written to {}'.format(path_format.format(name)))
         done[name] = res
@@ -602,7 +664,7 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
     n_frames = len(foreground_set)
     mask_groups, dev_groups, map_groups = _mask_lists(result_dir, pixel)      # per scored group: (frame -> slice, host cube scores, boxes); masks are painted one frame at a time
     maps = map_groups is not None
-    fs_dev = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
+    fs_dev = _blank(device, n_frames)
     hb, wb = len(foreground_set[0]), len(foreground_set[0][0])
     group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {}, fs_dev, mask_groups, dev_groups,
                           map_groups)
@@ -626,8 +688,8 @@ def score_frames(net_set, stats_raw, stats_of, foreground_set, foreground_set2, 
         _save_masks(result_dir, range(n_frames), mask_groups, h, w)
     if dev_groups is not None:
         _pixel_stage(pixel, dev_groups, 0, n_frames, h, w, result_dir, device, map_groups)
-        if pixel.smooth_groups is not None:
-            pixel.smooth_groups += dev_groups
+        if pixel.groups is not None:
+            pixel.groups += dev_groups
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -641,26 +703,15 @@ def score_index_list(trainer, raw_store, flow_store, idx, score_batch, batch=Non
     n = len(idx)
     B = int(batch) if batch is not None else (n if n < score_batch else int(score_batch))
     idx_d = (idx if torch.is_tensor(idx) else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))).to(dev)
-    r_all, o_all = torch.empty(n, device=dev), None
-    er_all, eo_all = torch.empty((n, 32, 32), device=dev) if maps else None, None
+    gathered = _Gathered(n, maps, dev)
     for s0 in range(0, n, B):
         m = min(B, n - s0)
         sel = idx_d[s0:s0 + m]
         if m < B:
             sel = torch.cat([sel, sel[-1:].expand(B - m)])
-        r, o, *e = trainer.score_cubes(raw_store, flow_store, sel, maps=True) if maps else trainer.score_cubes(raw_store, flow_store, sel)
-        r_all[s0:s0 + m] = r[:m]
-        if o is not None:
-            if o_all is None:
-                o_all = torch.empty(n, device=dev)
-            o_all[s0:s0 + m] = o[:m]
-        if maps:
-            er_all[s0:s0 + m] = e[0][:m]
-            if e[1] is not None:
-                if eo_all is None:
-                    eo_all = torch.empty((n, 32, 32), device=dev)
-                eo_all[s0:s0 + m] = e[1][:m]
-    return (r_all, o_all, er_all, eo_all) if maps else (r_all, o_all)
+        gathered.put(s0, m, *(trainer.score_cubes(raw_store, flow_store, sel, maps=True) if maps
+                              else trainer.score_cubes(raw_store, flow_store, sel)))
+    return gathered.result()
 
 
 def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw, w_of, useFlow, device, score_batch=2048,
@@ -686,7 +737,7 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
         n_frames = frame_range[1]
     else:
         raise ValueError('score_store: no group, no out and no frame_range to tell the number of frames')
-    fs_dev = out if out is not None else torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device)
+    fs_dev = out if out is not None else _blank(device, n_frames)
     mask_groups, dev_groups, map_groups = _mask_lists(result_dir, pixel)
     maps = map_groups is not None
     group = _group_scorer(net_set, stats_raw, stats_of, h, w, w_raw, w_of, useFlow, device, {} if trainers is None else trainers,
@@ -702,8 +753,8 @@ def score_store(net_set, stats_raw, stats_of, store, groups, boxes, h, w, w_raw,
         _save_masks(result_dir, range(first, end), mask_groups, h, w)
     if dev_groups is not None:
         _pixel_stage(pixel, dev_groups, first, end, h, w, result_dir, device, map_groups)
-        if pixel.smooth_groups is not None:
-            pixel.smooth_groups += dev_groups
+        if pixel.groups is not None:
+            pixel.groups += dev_groups
     return fs_dev if return_device else fs_dev.cpu().numpy()
 
 
@@ -720,7 +771,7 @@ def score_direct(c, device, mask_dir=None, log=print, flownet2=None, pixel=None)
     info, parts = extract_device(c, 'test', device, log, flownet2=flownet2)
     net_set, st_r, st_o = load_artifacts(base, fg, method, ds == 'ShanghaiTech', lambda: build_network(c), device, c['h_block'],
                                          c['w_block'])
-    fs_dev = torch.full((info['n_frames'],), -float(BIG), dtype=torch.float64, device=device)
+    fs_dev = _blank(device, info['n_frames'])
     trainers = {}
     pixel = pixel(info['n_frames'], info['labels']) if pixel is not None else None
     for part in parts:
@@ -730,14 +781,172 @@ def score_direct(c, device, mask_dir=None, log=print, flownet2=None, pixel=None)
     return fs_dev.cpu().numpy()
 
 
+def _region_scores_path(c):
+    return os.path.join('results', c['dataset_name'], 'region_scores_{}_{}.npz'.format(c['mode_fg'], c['method']))
+
+
+def _load_scores(c):
+    """``scores_saved = True``: what an earlier run left under ``results/<ds>/`` -> (name -> score vector for every row of ``VECTORS``
+    whose keys are on, region scores | None)."""
+    ds, fg, method = c['dataset_name'], c['mode_fg'], c['method']
+    vectors = {v.name: np.load(v.scores_path(ds, fg, method)) for v in VECTORS.values() if all(c[key] for key in v.needs)}
+    return vectors, dict(np.load(_region_scores_path(c))) if c['region_criterion'] else None
+
+
+def _score(c, gt, device, flownet2=None):
+    """Scores the test set on the staged or the direct route, then runs the stages that read the kept groups of the whole set
+    (``smooth_masks``, ``render``).  ``gt``: the open ground-truth source or None.  Every score vector is saved under its ``VECTORS``
+    path as soon as it exists.  Returns (name -> score vector, region scores | None) like ``_load_scores``."""
+    ds, fg, method = c['dataset_name'], c['mode_fg'], c['method']
+    shanghai = ds == 'ShanghaiTech'
+    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+    h, w, _, _ = frame_size[ds]
+    if not c['direct_test'] and not c['cp'].getboolean(ds, 'test_foreground_saved'):   # test.py:98-176
+        from foreground import extract_test
+        extract_test(c, device)
+    out_dir = os.path.join('results', ds)
+    mask_dir = os.path.join(out_dir, 'score_mask') if c['save_score_masks'] else None
+    error_dir = os.path.join(out_dir, 'error_mask') if c['save_score_masks'] and c['pixel_maps'] else None
+    pix_gt = gt is not None and c['pixel_criterion']      # the pixel scores are wanted (the source may be open for the regions alone)
+    maps = c['pixel_maps'] and (error_dir is not None or pix_gt)      # neither a file nor a score to form them for: off
+    pixel = None
+
+    def pixel_eval(n_frames, labels):
+        """The ``pixel`` keyword of the scoring calls: None when no key asks for anything a ``PixelEval`` does."""
+        nonlocal pixel
+        if gt is None and not (c['device_score_masks'] and mask_dir) and not maps and not c['smooth_masks'] and not c['render']:
+            return None
+        if gt is not None and len(gt) != n_frames:
+            raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
+        out = _blank(device, n_frames) if pix_gt else None
+        pixel = PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
+                          maps=maps, error_dir=error_dir, out_fine=out.clone() if maps and pix_gt else None, criterion=pix_gt,
+                          regions=c['region_criterion'], region_iou=c['region_iou_percent'],
+                          video_idx=gt.frame_video_idx if c['region_criterion'] else None, keep_groups=c['smooth_masks'] or c['render'])
+        return pixel
+
+    if c['direct_test']:      # frames -> scores without cube files
+        fs = score_direct(c, device, mask_dir, flownet2=flownet2, pixel=pixel_eval)
+    else:
+        fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
+        fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
+        bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)
+        scene_idx = np.load(base + 'scene_idx.npy') if shanghai else None
+        net_set, st_r, st_o = load_artifacts(base, fg, method, shanghai, lambda: build_network(c), device, c['h_block'], c['w_block'])
+        lab_file = base + 'frame_labels_test.npy'
+        fs = score_frames(net_set, st_r, st_o, fset, fset2, bset, h, w, c['w_raw'], c['w_of'], c['useFlow'], device,
+                          c['score_batch'], scene_idx, mask_dir,
+                          pixel=pixel_eval(len(fset), np.load(lab_file).astype(bool) if os.path.exists(lab_file) else None))
+    os.makedirs(out_dir, exist_ok=True)
+    vectors, regions = {}, None
+
+    def put(name, scores):
+        vectors[name] = scores
+        np.save(VECTORS[name].scores_path(ds, fg, method), scores)
+
+    put('frame', fs)
+    if pix_gt:
+        put('pixel', pixel.out.cpu().numpy())
+        if pixel.maps:
+            put('pixel_fine', pixel.out_fine.cpu().numpy())
+    if c['region_criterion']:
+        regions = pixel.region_state(c['track_percent'])
+        if int(regions['n_frames']) != len(fs):
+            raise ValueError('the region stage saw {} of the {} test frames'.format(int(regions['n_frames']), len(fs)))
+        np.savez(_region_scores_path(c), **regions)
+    if c['smooth_masks']:      # one stage over the kept groups of the whole test set, after all scoring
+        fs_smooth, ps_smooth = _smooth_stage(
+            pixel.groups, _video_idx(c, gt), len(fs), h, w, c['smooth_frames'], c['smooth_pixels'], c['direct_frames_per_chunk'],
+            device, gt if pix_gt else None, c['pixel_overlap_percent'],
+            os.path.join(out_dir, 'score_mask_smooth') if c['save_score_masks'] else None)
+        put('frame_smooth', fs_smooth)
+        if ps_smooth is not None:
+            put('pixel_smooth', ps_smooth)
+    if c['render']:            # pictures of the kept groups, after all scoring (and after the smooth stage, whose masks it may draw)
+        render_gt = gt
+        if render_gt is None and not shanghai:
+            from foreground import gt_source
+            try:
+                render_gt = gt_source(c)      # the contour is drawn where the tree holds per-pixel ground truth
+            except ValueError:
+                render_gt = None
+        render_dir = os.path.join(out_dir, 'render')
+        print('Rendered {} frames to {}'.format(_render_stage(
+            c, pixel.groups, len(fs), h, w, device, render_dir, render_gt,
+            _video_idx(c, render_gt) if c['render_source'] == 'smooth' else None, flownet2), render_dir))
+    return vectors, regions
+
+
+def _scene_auc(scores, labels, scene_idx, path_of):
+    """The ShanghaiTech protocol (test.py:366-392): the ROC of every scene on its own, written to ``path_of(scene)``; the mean AUROC."""
+    return float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], path_of(si))
+                          for si in sorted(set(scene_idx))]))
+
+
+def _region_results(c, regions):
+    """criterion = 'region' / 'track' (scoring.py module docstring): needs no frame labels, only the region scores."""
+    if regions is None:
+        return
+    ds = c['dataset_name']
+    print('Evaluating {} by region- and track-criterion (regions and tracks derived from the per-pixel ground truth):'.format(ds))
+    path = os.path.join('results', ds, '{}_{}_{}_region_results.npz'.format(c['modality'], c['mode_fg'], c['method']))
+    fpr, rbdr, tbdr, rbdc, tbdc = scoring.region_curves(regions['region_score'], regions['track_score'], regions['fp_score'],
+                                                        int(regions['n_frames']))
+    np.savez(path, fpr=fpr, rbdr=rbdr, tbdr=tbdr, rbdc=rbdc, tbdc=tbdc)
+    print('Results written to {}:'.format(path))
+    print('RBDC (IoU {}%) is {}'.format(c['region_iou_percent'], rbdc))
+    print('TBDC (IoU {}%, {}% of a track) is {}'.format(c['region_iou_percent'], c['track_percent'], tbdc))
+
+
+def _evaluate(c, vectors, regions, gt, device):
+    """The evaluation (test.py:362-399): every vector of ``vectors`` against the frame labels, row by row of ``VECTORS`` -- its ROC
+    file and its printed lines --, then ``auc_statistics`` and the region criteria.  Returns the frame-level AUROC (the mean over the
+    scenes for ShanghaiTech), or None without frame labels."""
+    ds, fg, mod, method = c['dataset_name'], c['mode_fg'], c['modality'], c['method']
+    base = os.path.join(c['data_root_dir'], mod, ds + '_')
+    lab_path = base + 'frame_labels_test.npy'
+    if not os.path.exists(lab_path):
+        print('no {} -> frame-level evaluation skipped (ground-truth masks need the dataset frame indexers)'.format(lab_path))
+        _region_results(c, regions)
+        return None
+    labels = np.load(lab_path).astype(bool)
+    scene_idx = np.load(base + 'scene_idx.npy') if ds == 'ShanghaiTech' else None
+    vectors = {name: vectors[name] for name in VECTORS if name in vectors}      # in the table's order
+    auc = {}
+    for name, scores in vectors.items():
+        v = VECTORS[name]
+        if v.header:
+            print(v.header.format(**c))
+        if scene_idx is not None and v.per_scene:
+            auc[name] = _scene_auc(scores, labels, scene_idx, lambda si: v.results_path(ds, mod, fg, method, scene=si))
+            print(v.per_scene.format(auc=auc[name], **c))
+            continue
+        path = v.results_path(ds, mod, fg, method)
+        print('Results written to {}:'.format(path))
+        auc[name] = save_roc_pr_curve_data(scores, labels, path)
+        if v.summary:
+            print(v.summary.format(auc=auc[name], **c))
+        if v.device_line:
+            # the same number from the device-side pair count (vv_roc_auc_counts); the .npz above keeps the reference's layout
+            print('{} (device pair count) is {}'.format(v.device_line, scoring.roc_auc(
+                torch.from_numpy(np.asarray(scores, np.float64)).to(device), labels)))
+    if c['auc_statistics']:      # macro AUROC and bootstrap intervals of every score vector the run has, from the vectors alone
+        print('Evaluating {} with bootstrap statistics:'.format(ds))
+        _auc_stage(c, vectors, labels, _video_idx(c, gt), np.asarray(scene_idx).astype(np.int64) if scene_idx is not None else None,
+                   os.path.join('results', ds, '{}_{}_{}_{{}}_bootstrap.npz'.format(mod, fg, method)), device)
+    _region_results(c, regions)
+    return auc['frame']
+
+
 def main(config_path='config.cfg', flownet2=None):
     c = read_config(config_path)
-    cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
     if c['direct_flow'] and not c['direct_test']:
         raise ValueError('[mi355x] direct_flow = True needs direct_test = True: only the direct test path computes the flow on the GPU')
+    ds = c['dataset_name']
+    saved = c['cp'].getboolean(ds, 'scores_saved')
     gt = None
     want_gt = c['pixel_criterion'] or c['region_criterion']      # either one opens the ground-truth source
-    if want_gt and not cp.getboolean(ds, 'scores_saved'):
+    if want_gt and not saved:
         from foreground import gt_source
         gt = gt_source(c)                 # ShanghaiTech / a tree without per-pixel ground truth: refused before any GPU work
     elif want_gt and ds == 'ShanghaiTech':
@@ -745,204 +954,8 @@ def main(config_path='config.cfg', flownet2=None):
         raise ValueError(PIXEL_GT_SHANGHAI)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
-    direct = c['direct_test'] and not cp.getboolean(ds, 'scores_saved')       # frames -> scores without cube files
-    if not direct and not cp.getboolean(ds, 'test_foreground_saved') and not cp.getboolean(ds, 'scores_saved'):   # test.py:98-176
-        from foreground import extract_test
-        extract_test(c, device)
-    base = os.path.join(root, mod, ds + '_')
-    h, w, _, _ = frame_size[ds]
-    results_dir = 'results'
-    shanghai = ds == 'ShanghaiTech'
-    frame_scores_path = os.path.join(results_dir, ds, 'frame_scores_{}_{}.npy'.format(fg, method))
-    pixel_scores_path = os.path.join(results_dir, ds, 'pixel_scores_{}_{}.npy'.format(fg, method))
-    fine_scores_path = os.path.join(results_dir, ds, 'pixel_scores_fine_{}_{}.npy'.format(fg, method))
-    region_scores_path = os.path.join(results_dir, ds, 'region_scores_{}_{}.npz'.format(fg, method))
-    smooth_fs_path = os.path.join(results_dir, ds, 'frame_scores_smooth_{}_{}.npy'.format(fg, method))
-    smooth_ps_path = os.path.join(results_dir, ds, 'pixel_scores_smooth_{}_{}.npy'.format(fg, method))
-    ps = ps_fine = regions = fs_smooth = ps_smooth = None
-    if cp.getboolean(ds, 'scores_saved'):
-        fs = np.load(frame_scores_path)
-        if c['smooth_masks']:
-            fs_smooth = np.load(smooth_fs_path)
-            if c['pixel_criterion']:
-                ps_smooth = np.load(smooth_ps_path)
-        if c['pixel_criterion']:
-            ps = np.load(pixel_scores_path)
-            if c['pixel_maps']:
-                ps_fine = np.load(fine_scores_path)
-        if c['region_criterion']:
-            regions = dict(np.load(region_scores_path))
-    else:
-        mask_dir = os.path.join(results_dir, ds, 'score_mask') if c['save_score_masks'] else None
-        error_dir = os.path.join(results_dir, ds, 'error_mask') if c['save_score_masks'] and c['pixel_maps'] else None
-        pix_gt = gt is not None and c['pixel_criterion']      # the pixel scores are wanted (the source may be open for the regions alone)
-        maps = c['pixel_maps'] and (error_dir is not None or pix_gt)      # neither a file nor a score to form them for: off
-        made = []
-
-        def pixel_eval(n_frames, labels):
-            """The ``pixel`` keyword of the scoring calls, or None with both new keys off (today's calls)."""
-            if gt is None and not (c['device_score_masks'] and mask_dir) and not maps and not c['smooth_masks'] and not c['render']:
-                return None
-            if gt is not None and len(gt) != n_frames:
-                raise ValueError('per-pixel ground truth for {} frames, {} test frames are scored'.format(len(gt), n_frames))
-            out = torch.full((n_frames,), -float(BIG), dtype=torch.float64, device=device) if pix_gt else None
-            # the region keys travel as trailing keywords: with region_criterion off the calls are the ones made before it existed
-            rk = dict(criterion=pix_gt, regions=True, region_iou=c['region_iou_percent'], video_idx=gt.frame_video_idx) \
-                if c['region_criterion'] else {}
-            if c['smooth_masks'] or c['render']:      # a trailing keyword too: with both keys off the calls are the ones made before they existed
-                rk['smooth'] = True                   # (the keyword keeps the scored groups: both stages run on them)
-            if not maps:
-                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
-                                      **rk))
-            else:
-                made.append(PixelEval(gt, c['pixel_overlap_percent'], out, labels, c['device_score_masks'], c['direct_frames_per_chunk'],
-                                      maps=True, error_dir=error_dir, out_fine=out.clone() if pix_gt else None, **rk))
-            return made[0]
-
-        if direct:
-            fs = score_direct(c, device, mask_dir, flownet2=flownet2, pixel=pixel_eval)
-        else:
-            fset = np.load(base + 'foreground_test_{}-raw.npy'.format(fg), allow_pickle=True)
-            fset2 = np.load(base + 'foreground_test_{}-flow.npy'.format(fg), allow_pickle=True)
-            bset = np.load(base + 'foreground_bbox_test_{}.npy'.format(fg), allow_pickle=True)
-            scene_idx = np.load(base + 'scene_idx.npy') if shanghai else None
-            net_set, st_r, st_o = load_artifacts(base, fg, method, shanghai, lambda: build_network(c), device, c['h_block'], c['w_block'])
-            lab_file = base + 'frame_labels_test.npy'
-            fs = score_frames(net_set, st_r, st_o, fset, fset2, bset, h, w, c['w_raw'], c['w_of'], c['useFlow'], device,
-                              c['score_batch'], scene_idx, mask_dir,
-                              pixel=pixel_eval(len(fset), np.load(lab_file).astype(bool) if os.path.exists(lab_file) else None))
-        os.makedirs(os.path.join(results_dir, ds), exist_ok=True)
-        np.save(frame_scores_path, fs)
-        if pix_gt:
-            ps = made[0].out.cpu().numpy()
-            np.save(pixel_scores_path, ps)
-            if made[0].maps:
-                ps_fine = made[0].out_fine.cpu().numpy()
-                np.save(fine_scores_path, ps_fine)
-        if c['region_criterion']:
-            regions = made[0].region_state(c['track_percent'])
-            if int(regions['n_frames']) != len(fs):
-                raise ValueError('the region stage saw {} of the {} test frames'.format(int(regions['n_frames']), len(fs)))
-            np.savez(region_scores_path, **regions)
-        if c['smooth_masks']:
-            # ---- [mi355x] smooth_masks: one stage over the kept groups of the whole test set, after all scoring
-            if gt is not None:
-                video_idx = gt.frame_video_idx
-            else:
-                from foreground import test_video_idx
-                video_idx = test_video_idx(c)
-            fs_smooth, ps_smooth = _smooth_stage(
-                made[0].smooth_groups, video_idx, len(fs), h, w, c['smooth_frames'], c['smooth_pixels'], c['direct_frames_per_chunk'],
-                device, gt if pix_gt else None, c['pixel_overlap_percent'],
-                os.path.join(results_dir, ds, 'score_mask_smooth') if c['save_score_masks'] else None)
-            np.save(smooth_fs_path, fs_smooth)
-            if ps_smooth is not None:
-                np.save(smooth_ps_path, ps_smooth)
-        if c['render']:
-            # ---- [mi355x] render: pictures of the kept groups, after all scoring (and after the smooth stage, whose masks it may draw)
-            render_gt = gt
-            if render_gt is None and not shanghai:
-                from foreground import gt_source
-                try:
-                    render_gt = gt_source(c)      # the contour is drawn where the tree holds per-pixel ground truth
-                except ValueError:
-                    render_gt = None
-            if c['render_source'] != 'smooth':
-                video_idx = None
-            elif render_gt is not None:
-                video_idx = render_gt.frame_video_idx
-            else:
-                from foreground import test_video_idx
-                video_idx = test_video_idx(c)
-            render_dir = os.path.join(results_dir, ds, 'render')
-            print('Rendered {} frames to {}'.format(_render_stage(c, made[0].smooth_groups, len(fs), h, w, device, render_dir, render_gt,
-                                                                    video_idx, flownet2), render_dir))
-
-    def region_results():
-        """criterion = 'region' / 'track' (scoring.py module docstring): needs no frame labels, only the saved region file."""
-        if regions is None:
-            return
-        print('Evaluating {} by region- and track-criterion (regions and tracks derived from the per-pixel ground truth):'.format(ds))
-        path = os.path.join(results_dir, ds, '{}_{}_{}_region_results.npz'.format(mod, fg, method))
-        fpr, rbdr, tbdr, rbdc, tbdc = scoring.region_curves(regions['region_score'], regions['track_score'], regions['fp_score'],
-                                                            int(regions['n_frames']))
-        np.savez(path, fpr=fpr, rbdr=rbdr, tbdr=tbdr, rbdc=rbdc, tbdc=tbdc)
-        print('Results written to {}:'.format(path))
-        print('RBDC (IoU {}%) is {}'.format(c['region_iou_percent'], rbdc))
-        print('TBDC (IoU {}%, {}% of a track) is {}'.format(c['region_iou_percent'], c['track_percent'], tbdc))
-
-    # ---- evaluation (test.py:362-399), criterion = 'frame'
-    lab_path = base + 'frame_labels_test.npy'
-    if not os.path.exists(lab_path):
-        print('no {} -> frame-level evaluation skipped (ground-truth masks need the dataset frame indexers)'.format(lab_path))
-        region_results()
-        return None
-    labels = np.load(lab_path).astype(bool)
-    print('Evaluating {} by frame-criterion:'.format(ds))
-    if shanghai:
-        scene_idx = np.load(base + 'scene_idx.npy')
-        aucs = []
-        for si in sorted(set(scene_idx)):
-            sel = scene_idx == si
-            aucs.append(save_roc_pr_curve_data(fs[sel], labels[sel], os.path.join(
-                results_dir, ds, '{}_{}_{}_frame_results_scene_{}.npz'.format(mod, fg, method, si))))
-        auc = float(np.mean(aucs))
-        print('Average frame-level AUC is {}'.format(auc))
-        if fs_smooth is not None:
-            print('Average frame-level AUC of the smoothed masks ({} frames x {} x {} pixels) is {}'.format(
-                c['smooth_frames'], c['smooth_pixels'], c['smooth_pixels'], float(np.mean([save_roc_pr_curve_data(
-                    fs_smooth[scene_idx == si], labels[scene_idx == si], os.path.join(
-                        results_dir, ds, '{}_{}_{}_frame_smooth_results_scene_{}.npz'.format(mod, fg, method, si)))
-                    for si in sorted(set(scene_idx))]))))
-    else:
-        path = os.path.join(results_dir, ds, '{}_{}_{}_frame_results.npz'.format(mod, fg, method))
-        print('Results written to {}:'.format(path))
-        auc = save_roc_pr_curve_data(fs, labels, path)
-        # the same number from the device-side pair count (vv_roc_auc_counts); the .npz above keeps the reference's layout
-        auc_dev = scoring.roc_auc(torch.from_numpy(np.asarray(fs, np.float64)).to(device), labels)
-        print('AUC@ROC (device pair count) is {}'.format(auc_dev))
-        if fs_smooth is not None:
-            path = os.path.join(results_dir, ds, '{}_{}_{}_frame_smooth_results.npz'.format(mod, fg, method))
-            print('Results written to {}:'.format(path))
-            print('Frame-level AUC of the smoothed masks ({} frames x {} x {} pixels) is {}'.format(
-                c['smooth_frames'], c['smooth_pixels'], c['smooth_pixels'], save_roc_pr_curve_data(fs_smooth, labels, path)))
-    if ps is not None:
-        # ---- criterion = 'pixel': the ROC of the pixel scores against the same frame labels (scoring.py module docstring)
-        print('Evaluating {} by pixel-criterion:'.format(ds))
-        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_results.npz'.format(mod, fg, method))
-        print('Results written to {}:'.format(path))
-        pixel_auc = save_roc_pr_curve_data(ps, labels, path)
-        print('Pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], pixel_auc))
-        print('Pixel-level AUC@ROC (device pair count) is {}'.format(
-            scoring.roc_auc(torch.from_numpy(np.asarray(ps, np.float64)).to(device), labels)))
-    if ps_fine is not None:
-        # ---- the same criterion on the fine masks ([mi355x] pixel_maps)
-        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_fine_results.npz'.format(mod, fg, method))
-        print('Results written to {}:'.format(path))
-        fine_auc = save_roc_pr_curve_data(ps_fine, labels, path)
-        print('Fine pixel-level AUC (overlap {}%) is {}'.format(c['pixel_overlap_percent'], fine_auc))
-        print('Fine pixel-level AUC@ROC (device pair count) is {}'.format(
-            scoring.roc_auc(torch.from_numpy(np.asarray(ps_fine, np.float64)).to(device), labels)))
-    if ps_smooth is not None:
-        # ---- the same criterion on the smoothed masks ([mi355x] smooth_masks)
-        path = os.path.join(results_dir, ds, '{}_{}_{}_pixel_smooth_results.npz'.format(mod, fg, method))
-        print('Results written to {}:'.format(path))
-        print('Pixel-level AUC of the smoothed masks (overlap {}%) is {}'.format(c['pixel_overlap_percent'],
-                                                                                 save_roc_pr_curve_data(ps_smooth, labels, path)))
-    if c['auc_statistics']:
-        # ---- [mi355x] auc_statistics: macro AUROC and bootstrap intervals of every score vector the run has, from the vectors alone
-        print('Evaluating {} with bootstrap statistics:'.format(ds))
-        if gt is not None:
-            video_idx = gt.frame_video_idx
-        else:
-            from foreground import test_video_idx
-            video_idx = test_video_idx(c)
-        vectors = {'frame': fs, 'frame_smooth': fs_smooth, 'pixel': ps, 'pixel_fine': ps_fine, 'pixel_smooth': ps_smooth}
-        _auc_stage(c, {k: v for k, v in vectors.items() if v is not None}, labels, video_idx,
-                   np.asarray(scene_idx).astype(np.int64) if shanghai else None,
-                   os.path.join(results_dir, ds, '{}_{}_{}_{{}}_bootstrap.npz'.format(mod, fg, method)), device)
-    region_results()
-    return auc
+    vectors, regions = _load_scores(c) if saved else _score(c, gt, device, flownet2)
+    return _evaluate(c, vectors, regions, gt, device)
 
 
 if __name__ == '__main__':

@@ -140,11 +140,11 @@ def test_mask_lists_keep_the_groups_only_with_the_key_on():
     assert S._mask_lists('d', S.PixelEval(gt, out=out)) == ([], [], None)
     assert S._mask_lists(None, S.PixelEval(maps=True, error_dir='e')) == (None, [], [])
     assert S._mask_lists('d', S.PixelEval(maps=True)) == ([], None, None)
-    assert S.PixelEval().smooth_groups is None and S.PixelEval(gt, out=out, smooth=False).smooth_groups is None
+    assert S.PixelEval().groups is None and S.PixelEval(gt, out=out, keep_groups=False).groups is None
     # with it on, the device groups are kept whatever else is asked for
-    on = S.PixelEval(smooth=True)
-    assert on.smooth_groups == [] and S._mask_lists(None, on) == (None, [], None) and S._mask_lists('d', on) == ([], [], None)
-    assert S._mask_lists('d', S.PixelEval(device_masks=True, smooth=True)) == (None, [], None)
+    on = S.PixelEval(keep_groups=True)
+    assert on.groups == [] and S._mask_lists(None, on) == (None, [], None) and S._mask_lists('d', on) == ([], [], None)
+    assert S._mask_lists('d', S.PixelEval(device_masks=True, keep_groups=True)) == (None, [], None)
 
 
 def test_smooth_stage_refuses_an_indexer_of_another_length():
