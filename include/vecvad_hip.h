@@ -558,6 +558,31 @@ int vv_flow_pairs_prep(const uint8_t* frames, int32_t F, int32_t H, int32_t W, i
 int vv_flow_resize_back(const float* flow, int32_t N, int32_t fh, int32_t fw, const int32_t* rows, int32_t H, int32_t W,
                         float* out, int64_t out_rows, vv_stream stream);
 
+/* ---- frame-by-frame scoring (vec_vad_amd/stream.py): one frame's boxes from a ring of recent frames to a frame score ----
+ * Every table below lives in device memory and is read by the kernels, so the launch arguments stay the same from frame to frame.
+ * vv_stream_cut: for the n[0] <= cap boxes of one frame (n[0] is clamped to [0, cap]) the raw cube and the flow cube of box b go into
+ *   slot b of a fixed store in CubeStore layout, and keep[b] = the motion test of vv_cube_energy at `thr`.
+ *   raw_ring  uint8 [R][H][W][C], flow_ring float32 [Rf][H][W][2]: the recent frames and their flow fields
+ *   crops     int32 [cap][4] as for vv_crop_resize (rows >= n[0] are not read)
+ *   raw_win   int32 [T], flow_win int32 [Tf]: the ring slots of the frame's two context windows (clamped to the rings; repeats allowed)
+ *   raw_store uint8 [cap][T][P][P][C] = the bytes vv_cube_cut writes for the same frames, crop and window; flow_store float32
+ *             [cap][Tf][P][P][2] likewise; keep uint8 [cap]; energy double [cap] or NULL = the value of vv_cube_energy (same device
+ *             function: same float64 sum in the same order).  Slots >= n[0] of all four are not written.  A crop outside the frame
+ *             (the caller checks) is dropped: keep 0, nothing cut.  P <= 1024, T * P * P and Tf * P * P <= INT32_MAX.
+ * vv_stream_scores: raw / of float32 [cap] = the per-cube error sums of a scoring launch over the store (of == NULL drops the flow
+ *   term), stats double [4] = (mu_r, sd_r, mu_o, sd_o) of the block's model or NULL for a block without one, mask uint8 [cap] = the
+ *   boxes that belong to the block.  Box b counts iff b < n[0], keep[b] and mask[b]; then box_scores[b] = the score of vv_cube_scores
+ *   (the same device function; +big without a model) and frame_score[0] = max(frame_score[0], box_scores[b]); a box below n[0] that
+ *   does not count gets -big and its errors are not read, slots >= n[0] are not written: whatever they hold, NaN and Inf included, stays
+ *   out of the maximum.  The caller starts frame_score[0] at -big; one workgroup, no atomics. */
+int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
+                  const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win, int32_t cap, int32_t T,
+                  int32_t Tf, int32_t P, double thr, uint8_t* raw_store, float* flow_store, uint8_t* keep, double* energy,
+                  vv_stream stream);
+int vv_stream_scores(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
+                     const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cap, double* box_scores, double* frame_score,
+                     vv_stream stream);
+
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.
  *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats

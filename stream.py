@@ -1,0 +1,89 @@
+#!/usr/bin/env python
+"""``python stream.py`` -- the configured test split scored frame by frame, as a camera would deliver it.
+
+Every video of the split is pushed through a ``vec_vad_amd.stream.StreamScorer`` one frame at a time (one scorer per scene for
+ShanghaiTech): boxes from ``foreground.load_bboxes``, videos from the split's frame indexer, the models and statistics ``train.py``
+wrote.  The score of a frame comes back one push later (the flow of a frame needs the next frame; the last frame of a video comes
+back at its end).  Writes ``results/<ds>/stream_scores_<fg>_<method>.npy`` and, when the split has frame labels, the frame-level ROC
+``results/<ds>/<modality>_<fg>_<method>_stream_results.npz`` (per scene for ShanghaiTech, as ``test.py`` evaluates it) and prints its
+AUROC.  ``main`` returns the score vector.  Nothing under ``optical_flow/`` and no cube file is read or written.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from train import read_config, build_network  # noqa: E402
+from utils import save_roc_pr_curve_data  # noqa: E402
+
+
+def results_path(c, scene=None):
+    return os.path.join('results', c['dataset_name'], '{}_{}_{}_stream_results{}.npz'.format(
+        c['modality'], c['mode_fg'], c['method'], '' if scene is None else '_scene_{}'.format(scene)))
+
+
+def scores_path(c):
+    return os.path.join('results', c['dataset_name'], 'stream_scores_{}_{}.npy'.format(c['mode_fg'], c['method']))
+
+
+def main(config_path='config.cfg', flownet2=None):
+    c = read_config(config_path)                      # a bad [mi355x] stream_max_boxes raises here, before any GPU work
+    import foreground as FG
+    from test import BIG, load_artifacts
+    from vad_datasets import get_inputs
+    from vec_vad_amd.stream import StreamScorer
+    ds = c['dataset_name']
+    shanghai = ds == 'ShanghaiTech'
+    device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
+    torch.cuda.set_device(device)
+    st = FG._stage(c, 'test', direct_flow=True)       # boxes and the frame indexer over the raw tree; no flow file is globbed
+    scene_idx, labels = FG._write_frame_index(st, ds, 'test')
+    indexer, n = st.raw_ds, len(st.raw_ds)
+    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+    net_set, st_r, st_o = load_artifacts(base, c['mode_fg'], c['method'], shanghai, lambda: build_network(c), device, c['h_block'],
+                                         c['w_block'])
+    if flownet2 is None:
+        from calc_optical_flow import load_flownet2
+        flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
+    scores = np.full(n, -float(BIG), np.float64)
+    scorers, pushed, results = {}, {}, []             # per scene: the scorer, the test frames it was given in push order
+    last = None                                       # the scene of the frame before
+    for i in range(n):
+        frame = get_inputs(indexer.all_frame_addr[i])
+        key = int(scene_idx[i]) - 1 if shanghai else None
+        if i > 0 and indexer.frame_video_idx[i] != indexer.frame_video_idx[i - 1]:
+            results += [(last, r) for r in scorers[last].end_video()]
+        if key not in scorers:
+            scorers[key] = StreamScorer(c, net_set, st_r, st_o, frame.shape, flownet2=flownet2, scene=key, device=device)
+            pushed[key] = []
+        pushed[key].append(i)
+        results += [(key, r) for r in scorers[key].push(frame, st.boxes[i])]
+        last = key
+    if n:
+        results += [(last, r) for r in scorers[last].end_video()]
+    for key, r in results:
+        scores[pushed[key][r.frame]] = r.wait()[0]
+    os.makedirs(os.path.join('results', ds), exist_ok=True)
+    np.save(scores_path(c), scores)
+    if labels is None:
+        print('no frame labels for {} -> frame-level evaluation of the stream skipped'.format(ds))
+        return scores
+    print('Evaluating the stream of {} by frame-criterion:'.format(ds))
+    if shanghai:
+        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si))
+                             for si in sorted(set(scene_idx))]))
+        print('Average frame-level AUC of the stream is {}'.format(auc))
+    else:
+        print('Results written to {}:'.format(results_path(c)))
+        auc = save_roc_pr_curve_data(scores, labels, results_path(c))
+        print('Frame-level AUC of the stream is {}'.format(auc))
+    return scores
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,139 @@
+#!/usr/bin/env python
+"""Time the frame-by-frame scorer (``vec_vad_amd.stream.StreamScorer``) next to the closest batch equivalent, on the synthetic
+UCSDped2-shaped tree of ``tools/synthetic_tree.py`` (240x360 grey .tif frames, one test video).  FlowNet2 carries seeded random weights
+(``torch.manual_seed(0)``): its run time does not depend on them.  After one epoch of ``train.py`` (a child process) the legs alternate
+in one process, ``--reps`` times:
+
+  batch   ``test.main`` with ``direct_test``, ``direct_flow``, ``direct_flow_pairs = 1`` and ``direct_frames_per_chunk = 1``: wall time
+          of the call over the number of test frames (decoding, model loading, engine set-up and evaluation included);
+  stream  every test frame, decoded beforehand, through one ``StreamScorer``: per frame the host clock from before ``push`` to after the
+          ``wait()`` of the result that push returned (the score of the frame before: one frame of look-ahead), median and 95th
+          percentile over the frames after ``--warm``; and the wall time of the whole loop with the constructor over the frames.
+
+With ``--no-flow-branch`` the same is repeated on a tree trained and scored with ``useFlow = False`` (the flow UNets are gone; FlowNet2
+still runs, because the motion test reads its flow).  Prints one JSON line; needs the GPU.
+
+    timeout 900 python tools/time_stream.py --frames 200 [--boxes 12] [--reps 2] [--no-flow-branch] [--out stream.json]
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+from synthetic_tree import make_tree
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCORES = 'results/UCSDped2/frame_scores_obj_det_with_motion_SelfComplete.npy'
+
+
+def batch_leg(net, n):
+    import torch
+    import test as S
+    t0 = time.perf_counter()
+    with contextlib.redirect_stdout(io.StringIO()):
+        S.main('config.cfg', flownet2=net)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    return dict(wall_s=wall, ms_per_frame=1e3 * wall / n), np.load(SCORES)
+
+
+def stream_leg(net, warm):
+    import torch
+    import foreground as FG
+    import test as S
+    import train as T
+    from vad_datasets import get_inputs
+    from vec_vad_amd.stream import StreamScorer
+    c = T.read_config('config.cfg')
+    with contextlib.redirect_stdout(io.StringIO()):
+        st = FG._stage(c, 'test', direct_flow=True)
+    frames = [get_inputs(a) for a in st.raw_ds.all_frame_addr]
+    n = len(frames)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    arts = S.load_artifacts(os.path.join(c['data_root_dir'], c['modality'], 'UCSDped2_'), c['mode_fg'], c['method'], False,
+                            lambda: T.build_network(c), torch.device('cuda'))
+    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net)
+    torch.cuda.synchronize()
+    setup = time.perf_counter() - t0
+    scores, lat = np.zeros(n), []
+    for i in range(n):
+        t = time.perf_counter()
+        for r in sc.push(frames[i], st.boxes[i]):
+            scores[r.frame] = r.wait()[0]
+        lat.append(time.perf_counter() - t)
+    for r in sc.end_video():
+        scores[r.frame] = r.wait()[0]
+    wall = time.perf_counter() - t0
+    steady = 1e3 * np.array(lat[warm:])
+    return dict(setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
+                push_to_wait_ms_p95=float(np.percentile(steady, 95)), push_to_wait_ms_max=float(steady.max()),
+                frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap), scores
+
+
+def measure(a, use_flow):
+    import torch
+    from FlowNet2_src import FlowNet2
+    work = tempfile.mkdtemp(prefix='stream_tree_')
+    os.chdir(work)
+    try:
+        make_tree({'train': (6, 6), 'test': (a.frames,)}, a.boxes, flow=True)
+        cfg = open(os.path.join(ROOT, 'config.cfg')).read()
+        cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('save_score_masks = True', 'save_score_masks = False')
+        if not use_flow:
+            cfg = cfg.replace('useFlow = True', 'useFlow = False')
+        open('config.cfg', 'w').write(cfg)
+        subprocess.run([sys.executable, os.path.join(ROOT, 'train.py')], check=True, env=dict(os.environ, PYTHONPATH=ROOT),
+                       stdout=subprocess.DEVNULL, timeout=600)
+        shutil.rmtree(os.path.join('optical_flow', 'UCSDped2', 'Test'))      # neither leg may need a flow file of the test split
+        cfg = cfg.replace('direct_test = False', 'direct_test = True').replace('direct_flow = False', 'direct_flow = True')
+        cfg = cfg.replace('direct_flow_pairs = 4', 'direct_flow_pairs = 1').replace('direct_frames_per_chunk = 64', 'direct_frames_per_chunk = 1')
+        open('config.cfg', 'w').write(cfg)
+        torch.manual_seed(0)
+        net = FlowNet2().cuda().eval()
+        res = {'useFlow': use_flow, 'batch': [], 'stream': []}
+        for _ in range(a.reps):
+            b, sb = batch_leg(net, a.frames)
+            s, ss = stream_leg(net, a.warm)
+            res['batch'].append(b)
+            res['stream'].append(s)
+            res['largest_score_difference'] = float(np.abs(sb - ss).max())
+        return res
+    finally:
+        os.chdir(ROOT)
+        shutil.rmtree(work)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=200)
+    ap.add_argument('--boxes', type=int, default=12)
+    ap.add_argument('--reps', type=int, default=2)
+    ap.add_argument('--warm', type=int, default=20)
+    ap.add_argument('--no-flow-branch', action='store_true')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    from vec_vad_amd import build as B
+    out_path = os.path.abspath(a.out) if a.out else None
+    res = {'frames': a.frames, 'boxes_per_frame': a.boxes, 'library_hash': B.wanted()[1][:16], 'runs': [measure(a, True)]}
+    if a.no_flow_branch:
+        print(json.dumps(res), flush=True)               # the first tree's figures, should the second one fail
+        res['runs'].append(measure(a, False))
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        with open(out_path, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()

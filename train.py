@@ -132,7 +132,8 @@ def read_config(path='config.cfg'):
              render_every=cp.getint('mi355x', 'render_every', fallback=1),
              render_boxes=cp.getboolean('mi355x', 'render_boxes', fallback=True),
              render_flow=cp.getboolean('mi355x', 'render_flow', fallback=False),
-             render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0))
+             render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0),
+             stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip())
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
@@ -169,6 +170,13 @@ def read_config(path='config.cfg'):
         raise ValueError('[mi355x] render_flow_max must be a finite radius >= 0 (0: every image by its own), got {}'.format(c['render_flow_max']))
     if c['render'] and c['render_source'] == 'smooth' and not c['smooth_masks']:
         raise ValueError('[mi355x] render_source = smooth needs smooth_masks = True: only that stage forms the smoothed masks')
+    # cubes per scoring launch of a streamed frame (stream.py), checked whatever route runs
+    try:
+        c['stream_max_boxes'] = int(c['stream_max_boxes'])
+    except ValueError:
+        pass
+    if not isinstance(c['stream_max_boxes'], int) or c['stream_max_boxes'] < 1:
+        raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(c['stream_max_boxes']))
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -2,93 +2,19 @@
 // (reference vad_datasets.py:70-93 get_foreground; calc_optical_flow.py:46-59,82 whole-frame resizes); vv_cube_cut / vv_cube_energy
 // do the same for the boxes of many consecutive frames at once, every box with its own frame window (test.py's direct path).
 // HBM-bound gather: every output element reads <= 4 source elements that neighbouring lanes share through L2/TCP.
-// The uint8 path is bit-exact fixed point; the float path rounds every product and sum to fp32 (no FMA contraction, see
-// the pragma below) like the C++ it replaces.
+// The uint8 path is bit-exact fixed point; the float path rounds every product and sum to fp32 (no FMA contraction: the pragma
+// of vv_resize.h, where the arithmetic lives) like the C++ it replaces.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/vecvad_hip.h"
 #include "vv_common.h"
 
-// Every product and sum below must be rounded separately, like the host arithmetic it replaces: forbid FMA contraction
-// for this translation unit.  (ROCm's __fmul_rn/__fadd_rn are plain operators defined in a header, i.e. BEFORE this
-// pragma, and do get fused after inlining -- hence ordinary operators here.)
-#pragma clang fp contract(off)
+#include "vv_resize.h"      // Tap / resize_pixel / crop_ok / box_energy, shared with vv_stream.hip; switches FMA contraction off
 
 namespace {
 
-struct Tap {
-  int s0, s1;
-  float w0, w1;
-};
-
-// one axis of cv::resize's linear table: d -> (s0, s1, 1-f, f)
-__device__ inline Tap axis_tap(int d, int dst, int src, bool horizontal) {
-  double scale = 1.0 / ((double)dst / (double)src);
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f = f - (float)s;
-  Tap t;
-  if (horizontal) {
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= src - 1) { f = 0.f; s = src - 1; }
-    t.s0 = s;
-    t.s1 = min(s + 1, src - 1);
-  } else {
-    t.s0 = min(max(s, 0), src - 1);
-    t.s1 = min(max(s + 1, 0), src - 1);
-  }
-  t.w0 = 1.f - f;
-  t.w1 = f;
-  return t;
-}
-
-__device__ inline int fixed11(float w) {
-  int v = __float2int_rn(w * 2048.f);
-  return min(max(v, -32768), 32767);
-}
-
-// One output pixel (all C channels) of cv::resize(crop, (ow, oh)): src = the crop's top-left element inside its frame, rs = the
-// frame's row stride in elements.  emit(c, v) receives each channel value -- a store (vv_crop_resize, vv_cube_cut) or a sum
-// (vv_cube_energy) -- so every caller shares one arithmetic.
-template <typename T, typename Emit>
-__device__ inline void resize_pixel(const T* __restrict__ src, int64_t rs, int C, int cw, int ch, int oh, int ow, int dy, int dx,
-                                    Emit emit) {
-  if (cw == ow && ch == oh) {                       // same size: plain copy
-    for (int c = 0; c < C; ++c) emit(c, src[dy * rs + (int64_t)dx * C + c]);
-    return;
-  }
-  if (cw == 2 * ow && ch == 2 * oh) {               // exact 2x decimation -> INTER_AREA
-    const T* p = src + (2 * dy) * rs + (int64_t)(2 * dx) * C;
-    for (int c = 0; c < C; ++c) {
-      if constexpr (sizeof(T) == 1) {
-        emit(c, (T)(((int)p[c] + (int)p[C + c] + (int)p[rs + c] + (int)p[rs + C + c] + 2) >> 2));
-      } else {
-        emit(c, (((p[c] + p[C + c]) + p[rs + c]) + p[rs + C + c]) * 0.25f);
-      }
-    }
-    return;
-  }
-  Tap tx = axis_tap(dx, ow, cw, true), ty = axis_tap(dy, oh, ch, false);
-  const T* r0 = src + ty.s0 * rs;
-  const T* r1 = src + ty.s1 * rs;
-  int64_t o0 = (int64_t)tx.s0 * C, o1 = (int64_t)tx.s1 * C;
-  if constexpr (sizeof(T) == 1) {
-    int a0 = fixed11(tx.w0), a1 = fixed11(tx.w1), b0 = fixed11(ty.w0), b1 = fixed11(ty.w1);
-    for (int c = 0; c < C; ++c) {
-      int h0 = (int)r0[o0 + c] * a0 + (int)r0[o1 + c] * a1;
-      int h1 = (int)r1[o0 + c] * a0 + (int)r1[o1 + c] * a1;
-      int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-      emit(c, (T)min(max(v, 0), 255));
-    }
-  } else {
-    for (int c = 0; c < C; ++c) {
-      float h0 = r0[o0 + c] * tx.w0 + r0[o1 + c] * tx.w1;
-      float h1 = r1[o0 + c] * tx.w0 + r1[o1 + c] * tx.w1;
-      emit(c, h0 * ty.w0 + h1 * ty.w1);
-    }
-  }
-}
+using namespace vv_resize;
 
 template <typename T>
 __global__ void __launch_bounds__(256) crop_resize_kernel(const T* __restrict__ frames, int nT, int H, int W, int C,
@@ -106,13 +32,6 @@ __global__ void __launch_bounds__(256) crop_resize_kernel(const T* __restrict__ 
   const T* src = frames + (((int64_t)t * H + y_min) * W + x_min) * C;
   T* dst = out + gid * C;
   resize_pixel(src, (int64_t)W * C, C, cw, ch, oh, ow, dy, dx, [dst](int c, T v) { dst[c] = v; });
-}
-
-// a crop that does not lie inside the frame reads nothing.  The Python wrappers refuse such a table before they launch
-// (extract.check_tables); this guard, the slot guard and the window clamp below only keep a caller of the bare C ABI with a wrong
-// table from touching memory outside its buffers.
-__device__ inline bool crop_ok(int x0, int y0, int x1, int y1, int H, int W) {
-  return 0 <= x0 && x0 < x1 && x1 <= W && 0 <= y0 && y0 < y1 && y1 <= H;
 }
 
 // vv_cube_cut: one thread per output pixel of (box i, context frame t); every box brings its own frame window and store slot.
@@ -146,28 +65,9 @@ __global__ void __launch_bounds__(256) cube_energy_kernel(const float* __restric
                                                           uint8_t* __restrict__ keep) {
   __shared__ double part[256];
   int i = blockIdx.x;
-  int x_min = crops[4 * i + 0], y_min = crops[4 * i + 1], x_max = crops[4 * i + 2], y_max = crops[4 * i + 3];
-  double acc = 0.0;
-  if (crop_ok(x_min, y_min, x_max, y_max, H, W)) {       // the same for every thread of the workgroup
-    int per = nT * P * P;                                // fits: vv_cube_energy refuses T * P * P > INT32_MAX
-    for (int j = threadIdx.x; j < per; j += 256) {
-      int dx = j % P, dy = (j / P) % P, t = j / (P * P);
-      int f = min(max(win[(int64_t)i * nT + t], 0), F - 1);
-      const float* src = frames + (((int64_t)f * H + y_min) * W + x_min) * C;
-      resize_pixel(src, (int64_t)W * C, C, x_max - x_min, y_max - y_min, P, P, dy, dx, [&acc](int, float v) {
-        double d = (double)v;
-        acc = acc + d * d;
-      });
-    }
-  }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + s];
-    __syncthreads();
-  }
+  double e = box_energy(frames, F, H, W, C, crops[4 * i + 0], crops[4 * i + 1], crops[4 * i + 2], crops[4 * i + 3],
+                        win + (int64_t)i * nT, nT, P, part, nullptr);
   if (threadIdx.x == 0) {
-    double e = part[0] / (double)nT;
     energy[i] = e;
     keep[i] = e > thr ? 1 : 0;
   }

@@ -11,23 +11,11 @@
 #include "../../include/vecvad_hip.h"
 #include "vv_common.h"
 
-// Products and sums are rounded separately like numpy's: no FMA contraction in this translation unit.
-#pragma clang fp contract(off)
+#include "vv_score_fn.h"      // cube_score, shared with vv_stream.hip; switches FMA contraction off (products and sums rounded like numpy's)
 
 namespace {
 
-// The z-normalised, weighted score of cube m (test.py:338-348), float64 like numpy's (float32 error - float64 mean) / float64
-// std: THE one place the expression lives, so vv_frame_scores, vv_cube_scores and what is painted from them agree to the bit.
-__device__ __forceinline__ double cube_score(const float* __restrict__ raw, const float* __restrict__ of,
-                                             const int32_t* __restrict__ cube_stat, const double* __restrict__ stats,
-                                             double w_raw, double w_of, double big, int m) {
-  const int s = cube_stat[m];
-  if (s < 0) return big;                            // no model for this block: anomaly by construction (test.py:346-348)
-  const double* st = stats + 4 * (int64_t)s;
-  double sc = w_raw * (((double)raw[m] - st[0]) / st[1]);
-  if (of) sc = sc + w_of * (((double)of[m] - st[2]) / st[3]);
-  return sc;
-}
+using namespace vv_score_fn;
 
 // The reference paints score m into mask[ceil(y1):ceil(y2), ceil(x1):ceil(x2)] (background -1e5), max-combines the masks
 // and later takes mask.max(): that is max over the cubes whose painted rectangle is non-empty, and -1e5 for frames with

@@ -1,0 +1,114 @@
+// Frame-by-frame scoring (vec_vad_amd/stream.py): the two launches that stand between a ring of recent frames and a frame score without
+// a host decision in between.  vv_stream_cut cuts the raw and the flow cube of every box of ONE frame into fixed store slots and applies
+// the motion test; vv_stream_scores turns the error sums of a fixed-size scoring launch into box scores and max-accumulates the frame
+// score under a validity mask.  Both read the number of boxes, the crops, the window slots and the masks from device memory, so their
+// launch arguments never change from frame to frame (they can sit in a captured graph).  Both are small and latency-bound (5-30 boxes a
+// frame): the point is one launch each.  The arithmetic is that of vv_cube_cut / vv_cube_energy / vv_cube_scores, through the shared
+// headers: the same bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/vecvad_hip.h"
+#include "vv_common.h"
+
+#include "vv_resize.h"        // resize_pixel / crop_ok / box_energy, shared with vv_extract.hip; switches FMA contraction off
+#include "vv_score_fn.h"      // cube_score_row, shared with vv_score.hip
+
+namespace {
+
+using namespace vv_resize;
+using namespace vv_score_fn;
+
+// One workgroup per store slot b; slots >= n leave at once and write nothing.  The flow cube is stored by the loop that sums its
+// squares (box_energy: the order and the bits of vv_cube_energy), then the raw cube is cut, thread j taking pixels j, j + 256, ... of
+// the [T][P][P] patch.  All boxes share the frame's two windows.
+__global__ void __launch_bounds__(256) stream_cut_kernel(const uint8_t* __restrict__ raw_ring, int R, const float* __restrict__ flow_ring,
+                                                         int Rf, int H, int W, int C, const int32_t* __restrict__ n_ptr,
+                                                         const int32_t* __restrict__ crops, const int32_t* __restrict__ raw_win,
+                                                         const int32_t* __restrict__ flow_win, int cap, int T, int Tf, int P, double thr,
+                                                         uint8_t* __restrict__ raw_store, float* __restrict__ flow_store,
+                                                         uint8_t* __restrict__ keep, double* __restrict__ energy) {
+  __shared__ double part[256];
+  const int b = blockIdx.x;
+  const int n = min(max(n_ptr[0], 0), cap);
+  if (b >= n) return;                                    // the same for every thread of the workgroup
+  const int x_min = crops[4 * b + 0], y_min = crops[4 * b + 1], x_max = crops[4 * b + 2], y_max = crops[4 * b + 3];
+  if (!crop_ok(x_min, y_min, x_max, y_max, H, W)) {      // a wrong table (the wrapper refuses it): the box is dropped, nothing is read
+    if (threadIdx.x == 0) {
+      keep[b] = 0;
+      if (energy) energy[b] = 0.0;
+    }
+    return;
+  }
+  const int64_t per_f = (int64_t)Tf * P * P, per_r = (int64_t)T * P * P;
+  const double e = box_energy(flow_ring, Rf, H, W, 2, x_min, y_min, x_max, y_max, flow_win, Tf, P, part, flow_store + b * per_f * 2);
+  if (threadIdx.x == 0) {
+    keep[b] = e > thr ? 1 : 0;
+    if (energy) energy[b] = e;
+  }
+  for (int j = threadIdx.x; j < (int)per_r; j += 256) {
+    const int dx = j % P, dy = (j / P) % P, t = j / (P * P);
+    const int f = min(max(raw_win[t], 0), R - 1);
+    const uint8_t* src = raw_ring + (((int64_t)f * H + y_min) * W + x_min) * C;
+    uint8_t* dst = raw_store + (b * per_r + j) * C;
+    resize_pixel(src, (int64_t)W * C, C, x_max - x_min, y_max - y_min, P, P, dy, dx, [dst](int c, uint8_t v) { dst[c] = v; });
+  }
+}
+
+// One workgroup.  Box b counts iff b < n, keep[b] and mask[b]: only then is its error read at all, so whatever the padded slots of the
+// scoring launch, a dropped box or a box of another block hold (NaN, Inf) cannot reach the maximum.  A counted box gets the score of
+// vv_cube_scores (stats == nullptr: the block has no model, +big), another box below n gets -big, slots >= n are not written.  The
+// maximum of the counted scores meets in an LDS tree and is max-accumulated into the frame's cell (launches on one stream are ordered,
+// a cell has one writer at a time).
+__global__ void __launch_bounds__(256) stream_scores_kernel(const float* __restrict__ raw, const float* __restrict__ of,
+                                                            const double* __restrict__ stats, double w_raw, double w_of, double big,
+                                                            const uint8_t* __restrict__ keep, const int32_t* __restrict__ n_ptr,
+                                                            const uint8_t* __restrict__ mask, int cap, double* __restrict__ box_scores,
+                                                            double* __restrict__ frame_score) {
+  __shared__ double part[256];
+  const int n = min(max(n_ptr[0], 0), cap);
+  double best = -INFINITY;
+  for (int b = threadIdx.x; b < n; b += 256) {
+    double s = -big;
+    if (keep[b] && mask[b]) {
+      s = stats ? cube_score_row(raw, of, stats, w_raw, w_of, b) : big;
+      best = fmax(best, s);
+    }
+    box_scores[b] = s;
+  }
+  part[threadIdx.x] = best;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] = fmax(part[threadIdx.x], part[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) frame_score[0] = fmax(frame_score[0], part[0]);
+}
+
+}  // namespace
+
+extern "C" int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
+                             const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win, int32_t cap,
+                             int32_t T, int32_t Tf, int32_t P, double thr, uint8_t* raw_store, float* flow_store, uint8_t* keep,
+                             double* energy, vv_stream stream) {
+  if (R <= 0 || Rf <= 0 || H <= 0 || W <= 0 || C <= 0 || cap < 0 || T <= 0 || Tf <= 0 || P <= 0 || P > 1024) return VV_ERR_BAD_ARG;
+  if ((int64_t)T * P * P > 0x7fffffff || (int64_t)Tf * P * P > 0x7fffffff) return VV_ERR_BAD_ARG;      // a box's patch is indexed with an int
+  if (cap == 0) return VV_OK;
+  if (!raw_ring || !flow_ring || !n || !crops || !raw_win || !flow_win || !raw_store || !flow_store || !keep) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_cut_kernel, dim3((unsigned)cap), dim3(256), 0, (hipStream_t)stream, raw_ring, R, flow_ring, Rf, H, W, C, n, crops,
+            raw_win, flow_win, cap, T, Tf, P, thr, raw_store, flow_store, keep, energy);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_stream_scores(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
+                                const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cap, double* box_scores,
+                                double* frame_score, vv_stream stream) {
+  if (cap < 0) return VV_ERR_BAD_ARG;
+  if (cap == 0) return VV_OK;
+  if (!keep || !n || !mask || !box_scores || !frame_score || (stats && !raw)) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_scores_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, raw, of, stats, w_raw, w_of, big, keep, n, mask, cap,
+            box_scores, frame_score);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}

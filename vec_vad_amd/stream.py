@@ -1,0 +1,407 @@
+"""Frame-by-frame scoring on the GPU: one frame and its boxes in, that frame's anomaly score out (``StreamScorer``).
+
+Every other route through this code base scores a finished test split.  A stream is a sequence of videos of one camera; for frame ``t``
+of a video the scorer builds the cubes ``test.py`` builds for it -- the raw window ``context_range(t, 'predict', context_frame_num)``
+inside the video (the first frame repeated at its start), the flow window the same over ``context_of_num``, the flow field of a frame
+computed from the pair ``calc_optical_flow.flow_pairs`` names for it -- and scores them with the models, statistics, weights, motion
+threshold and block grid of the configuration, exactly as ``test.py`` does.
+
+Look-ahead.  The pair of a frame that is not the last of its video contains the NEXT frame, so the score of frame ``t`` is issued when
+frame ``t + 1`` is pushed, and the last frame of a video when ``end_video()`` is called: a latency floor of one frame.  A video that
+ends after one frame has no pair the batch route accepts next to another video; ``end_video()`` raises a one-line ``ValueError``.
+
+Rings.  The last ``ring_frames(context_frame_num) = context_frame_num + 2`` frames live in a device ring: the ``context_frame_num + 1``
+frames of the raw window of the frame that is being issued plus the one frame of look-ahead behind it.  The flow fields live in a second
+ring of ``flow_ring_frames(context_of_num) = context_of_num + 1`` slots -- the flow window of the frame being issued, whose own field is
+written in place when it is issued (``vv_flow_pairs_prep`` -> FlowNet2's captured graph at one pair per launch -> ``vv_flow_resize_back``:
+the launches of ``calc_optical_flow.chunk_flows``, so the fields are those of ``direct_flow_pairs = 1``).  ``RingSchedule`` is that
+bookkeeping as a pure class.
+
+No host decision between upload and read-back.  ``push`` copies the frame into its ring slot and sends ONE small descriptor per issued
+frame through a pinned staging buffer: the box rectangles as ``boxes_to_crops`` forms them, their number, the ring slots of the two
+windows, the flow pair and the per-block masks.  Everything else is enqueued on the current stream: ``vv_stream_cut`` cuts the cubes of
+the boxes into slots ``0..n-1`` of a fixed store of ``max_boxes`` cubes and applies the motion test; every block of the grid that has a
+model scores the WHOLE store in its own fixed-size launch (the eval-mode graph of ``FusedTrainer.score_cubes``), and
+``vv_stream_scores`` turns the error sums into box scores and max-accumulates the frame score under ``keep`` and the block's mask, with
+no compaction.  The scores go to pinned host memory behind an event; ``StreamResult.wait()`` waits on that event and on nothing else.
+A frame with more boxes than ``max_boxes`` takes ``ceil(n / max_boxes)`` rounds of the same launches, max-accumulated on the device.
+
+What is not here: the detector (boxes are the caller's; ``vec_vad_amd.motion`` has the motion stage), decoding, several cameras per
+scorer, and the pixel-level, smoothing and rendering stages of ``test.py``.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .extract import boxes_to_crops
+from .scoring import BIG, box_paints
+
+
+def ring_frames(context_frame_num):
+    """Frames the raw ring holds: the ``context_frame_num + 1`` frames of the 'predict' window of the frame being issued, plus the
+    frame pushed behind it (the second frame of its flow pair)."""
+    return int(context_frame_num) + 2
+
+
+def flow_ring_frames(context_of_num):
+    """Flow fields the flow ring holds: the ``context_of_num + 1`` fields of the flow window of the frame being issued (its own field
+    is computed when it is issued, into the slot of the field that left the window)."""
+    return int(context_of_num) + 1
+
+
+def check_max_boxes(v):
+    """``stream_max_boxes`` as an integer >= 1, else a one-line ``ValueError``; no GPU is touched."""
+    if isinstance(v, str):
+        try:
+            v = int(v.strip())
+        except ValueError:
+            pass
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(v))
+    return int(v)
+
+
+def _dev(name, t, dtype, numel=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() < numel):
+        raise ValueError('{} must be a contiguous CUDA {} tensor{}'.format(name, dtype, '' if numel is None else ' of at least %d elements' % numel))
+    return t
+
+
+def stream_cut(raw_ring, flow_ring, n, crops, raw_win, flow_win, thr, raw_store, flow_store, keep, energy=None):
+    """``vv_stream_cut``: the cubes of the ``n[0]`` boxes of one frame from the two rings into slots ``0..n-1`` of a fixed store, and the
+    motion test.  raw_ring uint8 ``[R,H,W,C]``, flow_ring float32 ``[Rf,H,W,2]``; the tables are DEVICE tensors that the kernel reads
+    (int32: ``n`` ``[1]``, ``crops`` ``[cap,4]`` as ``boxes_to_crops`` forms them, ``raw_win`` ``[T]`` and ``flow_win`` ``[Tf]`` ring
+    slots), so nothing here looks at their values; raw_store uint8 ``[cap,T,P,P,C]``, flow_store float32 ``[cap,Tf,P,P,2]``, keep uint8
+    ``[cap]``, energy float64 ``[cap]`` or None.  Written: slots below ``n[0]`` -- the bytes of ``extract.cube_cut`` and the values of
+    ``extract.cube_energy`` for the same frames, crops and windows; everything else keeps what it holds."""
+    _dev('raw_ring', raw_ring, torch.uint8), _dev('flow_ring', flow_ring, torch.float32)
+    if raw_ring.dim() != 4 or flow_ring.dim() != 4 or tuple(flow_ring.shape[1:]) != tuple(raw_ring.shape[1:3]) + (2,):
+        raise ValueError('the rings must be [R,H,W,C] frames and [Rf,H,W,2] flow fields of one frame size')
+    R, H, W, C = raw_ring.shape
+    _dev('raw_store', raw_store, torch.uint8), _dev('flow_store', flow_store, torch.float32)
+    if raw_store.dim() != 5 or flow_store.dim() != 5:
+        raise ValueError('the stores must be [cap,T,P,P,C] and [cap,Tf,P,P,2] tensors')
+    cap, T, P = raw_store.shape[0], raw_store.shape[1], raw_store.shape[2]
+    Tf = flow_store.shape[1]
+    if tuple(raw_store.shape) != (cap, T, P, P, C) or tuple(flow_store.shape) != (cap, Tf, P, P, 2):
+        raise ValueError('the stores must be [cap,T,P,P,%d] and [cap,Tf,P,P,2] tensors of one cap and P' % C)
+    _dev('n', n, torch.int32, 1), _dev('crops', crops, torch.int32, 4 * cap)
+    _dev('raw_win', raw_win, torch.int32, T), _dev('flow_win', flow_win, torch.int32, Tf), _dev('keep', keep, torch.uint8, cap)
+    if energy is not None:
+        _dev('energy', energy, torch.float64, cap)
+    _lib.check(_lib.lib().vv_stream_cut(raw_ring.data_ptr(), R, flow_ring.data_ptr(), flow_ring.shape[0], H, W, C, n.data_ptr(),
+                                        crops.data_ptr(), raw_win.data_ptr(), flow_win.data_ptr(), cap, T, Tf, P, float(thr),
+                                        raw_store.data_ptr(), flow_store.data_ptr(), keep.data_ptr(),
+                                        energy.data_ptr() if energy is not None else None,
+                                        torch.cuda.current_stream(raw_ring.device).cuda_stream), 'vv_stream_cut')
+
+
+def stream_scores(raw, of, stats, w_raw, w_of, keep, n, mask, box_scores, frame_score):
+    """``vv_stream_scores``: one block's share of a frame score.  raw / of: float32 ``[cap]`` error sums of a scoring launch over the
+    store (``of`` None drops the flow term; ``raw`` may be None with ``stats`` None); stats: float64 ``[4]`` device tensor ``(mu_r, sd_r,
+    mu_o, sd_o)`` or None for a block without a model; keep uint8 ``[cap]``, n int32 ``[1]``, mask uint8 ``[cap]`` = the boxes of the
+    block, all on the device; box_scores float64 ``[cap]`` and frame_score float64 ``[1]`` are written in place: box ``b < n[0]`` gets
+    the score of ``scoring.cube_scores`` when ``keep[b]`` and ``mask[b]`` (``+BIG`` without a model) and enters ``frame_score[0] =
+    max(frame_score[0], ...)``, else ``-BIG``; slots ``>= n[0]`` are not written and nothing they hold is read."""
+    cap = _dev('box_scores', box_scores, torch.float64).numel()
+    _dev('frame_score', frame_score, torch.float64, 1), _dev('keep', keep, torch.uint8, cap), _dev('mask', mask, torch.uint8, cap)
+    _dev('n', n, torch.int32, 1)
+    if stats is not None:
+        _dev('stats', stats, torch.float64, 4), _dev('raw', raw, torch.float32, cap)
+        if of is not None:
+            _dev('of', of, torch.float32, cap)
+    _lib.check(_lib.lib().vv_stream_scores(raw.data_ptr() if stats is not None else None,
+                                           of.data_ptr() if (stats is not None and of is not None) else None,
+                                           stats.data_ptr() if stats is not None else None, float(w_raw), float(w_of), float(BIG),
+                                           keep.data_ptr(), n.data_ptr(), mask.data_ptr(), cap, box_scores.data_ptr(),
+                                           frame_score.data_ptr(), torch.cuda.current_stream(box_scores.device).cuda_stream),
+               'vv_stream_scores')
+
+
+class RingSchedule:
+    """The ring bookkeeping of one camera, pure (no GPU).  ``push()`` -> ``(slot, issue | None)``: the raw ring slot the new frame goes
+    into, and the frame that can now be issued (the previous frame of the video).  ``end_video()`` -> the issue of the video's last
+    frame (None for a video without frames; ``ValueError`` for a video of one frame), after which the next push starts a video.
+
+    An issue is a dict with video-local frame numbers and ring slots: ``frame``; ``raw_frames`` / ``raw_slots`` (the raw window);
+    ``flow_frames`` / ``flow_slots`` (the flow window); ``pair_frames`` / ``pair_slots`` (the two frames FlowNet2 sees for the flow of
+    ``frame``) and ``flow_slot`` (where that flow is written before the window is read).  Frame ``k`` of a video lives in raw slot
+    ``k % R``, its flow in flow slot ``k % Rf``."""
+
+    def __init__(self, context_frame_num=4, context_of_num=0):
+        self.T, self.Tf = int(context_frame_num) + 1, int(context_of_num) + 1
+        self.R, self.Rf = ring_frames(context_frame_num), flow_ring_frames(context_of_num)
+        self.count = 0            # frames of the current video pushed so far
+
+    def _issue(self, t, last):
+        raw = [max(t - self.T + 1 + i, 0) for i in range(self.T)]            # 'predict': up to and including t, first frame repeated
+        flow = [max(t - self.Tf + 1 + i, 0) for i in range(self.Tf)]
+        pair = (t - 1, t) if last else ((t, t) if t == 0 else (t, t + 1))     # calc_optical_flow.flow_pairs
+        return dict(frame=t, raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
+                    flow_slots=[f % self.Rf for f in flow], pair_frames=pair, pair_slots=(pair[0] % self.R, pair[1] % self.R),
+                    flow_slot=t % self.Rf)
+
+    def push(self):
+        k = self.count
+        self.count += 1
+        return k % self.R, (self._issue(k - 1, False) if k >= 1 else None)
+
+    def end_video(self):
+        k, self.count = self.count, 0
+        if k == 0:
+            return None
+        if k == 1:
+            raise ValueError('a video that ends after one frame cannot be scored: the flow of a frame needs a second frame of its video')
+        return self._issue(k - 1, True)
+
+
+class StreamResult:
+    """The scores of one frame, on their way to the host.  ``frame``: the running index of the frame (pushes are counted from 0 across
+    videos).  ``wait()`` blocks until the frame's copy has landed and returns ``(score, box_scores, kept)``: the frame score (float64;
+    ``-BIG`` when no box was kept), the score of every box (float64 ``[n]``: the largest over the blocks the box belongs to, ``+BIG`` in
+    a block without a model, ``-BIG`` for a box that was not kept or paints no pixel) and the motion test's flags (bool ``[n]``)."""
+
+    def __init__(self, frame, n, rows, width, host, host_keep, event):
+        self.frame, self._n, self._rows, self._width = frame, n, rows, width
+        self._host, self._host_keep, self._event = host, host_keep, event
+
+    def wait(self):
+        self._event.synchronize()
+        a = self._host.numpy()
+        n = self._n
+        box = np.full(n, -float(BIG), np.float64)
+        if self._rows and n:
+            box = a[1:].reshape(self._rows, self._width)[:, :n].max(axis=0)
+        return float(a[0]), box.copy(), self._host_keep.numpy()[:n].astype(bool)
+
+
+class _Staging:
+    """Pinned host buffers for uploads that are still in flight when the host moves on: a buffer is handed out again only once the
+    event recorded behind its last copy has completed (asked, never waited for); otherwise a new one is made."""
+
+    def __init__(self):
+        self.items = {}
+
+    def get(self, key, shape, dtype):
+        pool = self.items.setdefault((key, tuple(shape), dtype), [])
+        for it in pool:
+            if it[1] is None or it[1].query():
+                it[1] = None
+                return it
+        it = [torch.empty(tuple(shape), dtype=dtype, pin_memory=True), None]
+        pool.append(it)
+        return it
+
+
+class StreamScorer:
+    """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda')``.
+
+    ``c``: the dict of ``train.read_config``; ``net_set`` / ``stats_raw`` / ``stats_of``: what ``test.load_artifacts`` returns;
+    ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3); ``flownet2``: the network (None loads
+    ``[mi355x] flownet2_checkpoint``, in fp16 mode with ``direct_flow_fp16``); ``scene``: ShanghaiTech's per-scene model set, 0-based
+    like ``foreground.block_groups``, None for the other datasets; ``max_boxes``: cubes per scoring launch (None: ``[mi355x]
+    stream_max_boxes``).  ``useFlow``, ``context_of_num`` 0 and 4, ``w_raw`` / ``w_of``, ``motionThr``, ``precision`` and the ``h_block x
+    w_block`` grid are honoured as ``test.py`` honours them; like there, the grid cells and the painted-rectangle test are those of the
+    dataset's nominal frame size (``vad_datasets.frame_size``).
+
+    ``push(frame_u8 [H,W,C], boxes float [n,>=4])`` -> a list with 0 or 1 ``StreamResult`` (the previous frame of the video);
+    ``end_video()`` -> a list with the video's last frame, and the rings start over.  Neither synchronises the host with the device."""
+
+    def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda'):
+        self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
+        from vad_datasets import frame_size
+        from vec_vad_amd.trainer import FusedTrainer
+        cp, ds, method = c['cp'], c['dataset_name'], c['method']
+        if cp.get(method, 'border_mode') != 'predict':
+            raise ValueError("a stream scores with border_mode = predict only (a centred window needs frames that have not arrived), got "
+                             "{!r}".format(cp.get(method, 'border_mode')))
+        H, W, C = (int(v) for v in frame_shape)
+        if C not in (1, 3):
+            raise ValueError('frames must have 1 or 3 channels, got frame_shape {!r}'.format(tuple(frame_shape)))
+        self.H, self.W, self.C = H, W, C
+        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'))
+        self.P = cp.getint(ds, 'patch_size')
+        self.thr = cp.getfloat(ds, 'motionThr')
+        self.hb, self.wb = c['h_block'], c['w_block']
+        self.grid_h, self.grid_w = frame_size[ds][0], frame_size[ds][1]
+        self.h_step, self.w_step = self.grid_h / self.hb, self.grid_w / self.wb
+        self.block_mode = cp.getint(ds, 'test_block_mode')
+        self.w_raw, self.w_of, self.use_flow = float(c['w_raw']), float(c['w_of']), bool(c['useFlow'])
+        dev = torch.device(device)
+        self.device = dev = dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
+        if flownet2 is None:
+            from calc_optical_flow import load_flownet2
+            flownet2 = load_flownet2(c['flownet2_checkpoint'], device=dev, fp16=c['direct_flow_fp16'])
+        from calc_optical_flow import FLOW_H, FLOW_W
+        self.flow_h, self.flow_w = FLOW_H, FLOW_W
+        self.flow_in, self.flow_out, self.flow_graph = flownet2.graph_entry((1, 3, 2, FLOW_H, FLOW_W))
+        self.flownet2 = flownet2
+        sc, cap, P = self.sched, self.cap, self.P
+        self.raw_ring = torch.zeros((sc.R, H, W, C), dtype=torch.uint8, device=dev)
+        self.flow_ring = torch.zeros((sc.Rf, H, W, 2), dtype=torch.float32, device=dev)
+        self.store_raw = torch.zeros((cap, sc.T, P, P, C), dtype=torch.uint8, device=dev)
+        self.store_flow = torch.zeros((cap, sc.Tf, P, P, 2), dtype=torch.float32, device=dev)
+        self.idx = torch.arange(cap, dtype=torch.long, device=dev)
+        # per block of the grid: (trainer, device statistics) or None for a block without a model -- built as test._group_scorer does
+        nets = net_set[scene] if scene is not None else net_set
+        s_raw = stats_raw[scene] if scene is not None else stats_raw
+        s_of = stats_of[scene] if scene is not None else stats_of
+        trainers, self.blocks = {}, {}
+        for hh in range(self.hb):
+            for ww in range(self.wb):
+                models = nets[hh][ww]
+                if len(models) == 0:
+                    self.blocks[(hh, ww)] = None
+                    continue
+                net = models[0]
+                if id(net) not in trainers:
+                    trainers[id(net)] = FusedTrainer(net)
+                st_r = s_raw[hh][ww]
+                st_o = s_of[hh][ww] if self.use_flow else (0.0, 1.0)
+                stats = torch.from_numpy(np.array([st_r[0], st_r[1], st_o[0], st_o[1]], np.float64)).to(dev)
+                self.blocks[(hh, ww)] = (trainers[id(net)], stats)
+        # descriptor of one round, in int32 words: n, 3 unused | crops [cap][4] | raw window [T] | flow window [Tf] | masks [hb*wb][cap] bytes
+        self.w_crops = 4
+        self.w_rwin = self.w_crops + 4 * cap
+        self.w_fwin = self.w_rwin + sc.T
+        self.w_mask = (self.w_fwin + sc.Tf + 3) // 4 * 4
+        self.D = self.w_mask + (self.hb * self.wb * cap + 3) // 4
+        self.desc = torch.zeros(4 + self.D, dtype=torch.int32, device=dev)      # header: pair (2), flow row, rounds; grows with the rounds
+        self.staging = _Staging()
+        self.held = None          # (boxes, crops, blocks) of the frame that waits for its look-ahead
+        self.frames = 0           # frames pushed so far, across videos
+        # warm-up: every engine runs its eager launches and captures its graph here, so that push only replays
+        for ent in self.blocks.values():
+            if ent is not None:
+                for _ in range(3):
+                    ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
+        torch.cuda.synchronize(dev)
+
+    @classmethod
+    def from_config(cls, config_path='config.cfg', frame_shape=None, flownet2=None, scene=None):
+        """The scorer of a configuration: the artifacts ``train.py`` wrote under ``<data_root_dir>/<modality>/`` are loaded as ``test.py``
+        loads them.  ``frame_shape`` None: the dataset's nominal frame size with 3 channels.  A bad ``stream_max_boxes`` raises before
+        any GPU work."""
+        from train import build_network, read_config
+        c = read_config(config_path)
+        from test import load_artifacts
+        from vad_datasets import frame_size
+        ds = c['dataset_name']
+        device = torch.device('cuda', torch.cuda.current_device())
+        base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+        net_set, st_r, st_o = load_artifacts(base, c['mode_fg'], c['method'], ds == 'ShanghaiTech', lambda: build_network(c), device,
+                                             c['h_block'], c['w_block'])
+        if frame_shape is None:
+            frame_shape = (frame_size[ds][0], frame_size[ds][1], 3)
+        return cls(c, net_set, st_r, st_o, frame_shape, flownet2=flownet2, scene=scene, device=device)
+
+    # ---- host side of a frame: everything that can be refused is refused before a ring is touched
+    def _prepare(self, frame_u8, boxes):
+        from utils import calc_block_idx
+        frame = np.asarray(frame_u8)
+        if frame.ndim == 2 and self.C == 1:
+            frame = frame[:, :, None]
+        if frame.dtype != np.uint8 or tuple(frame.shape) != (self.H, self.W, self.C):
+            raise ValueError('push takes uint8 frames of shape {}, got {} {}'.format((self.H, self.W, self.C), frame.dtype, tuple(frame.shape)))
+        boxes = np.asarray(boxes, np.float64)
+        boxes = boxes.reshape(-1, boxes.shape[-1])[:, :4] if boxes.ndim == 2 and boxes.shape[0] else np.zeros((0, 4), np.float64)
+        crops = boxes_to_crops(boxes, self.H, self.W)
+        paints = box_paints(boxes, self.grid_h, self.grid_w)
+        blocks = []
+        for b, bb in enumerate(boxes):
+            cells = calc_block_idx(bb[0], bb[2], bb[1], bb[3], self.h_step, self.w_step, mode=self.block_mode)
+            if any(not (0 <= hi < self.hb and 0 <= wi < self.wb) for hi, wi in cells):
+                raise IndexError('box {} falls outside the {}x{} block grid'.format(b, self.hb, self.wb))
+            blocks.append(sorted(cells) if paints[b] else [])
+        return frame, (boxes, crops, blocks)
+
+    def push(self, frame_u8, boxes):
+        frame, held = self._prepare(frame_u8, boxes)
+        slot, issue = self.sched.push()
+        st = self.staging.get('frame', frame.shape, torch.uint8)
+        st[0].numpy()[...] = frame
+        self.raw_ring[slot].copy_(st[0], non_blocking=True)
+        st[1] = torch.cuda.Event()
+        st[1].record()
+        out = [self._issue(issue, self.held)] if issue is not None else []
+        self.held = held
+        self.frames += 1
+        return out
+
+    def end_video(self):
+        held, self.held = self.held, None
+        issue = self.sched.end_video()
+        return [self._issue(issue, held)] if issue is not None else []
+
+    def _issue(self, issue, held):
+        _, crops, blocks = held
+        lib, cap, sc, D = _lib.lib(), self.cap, self.sched, self.D
+        n = len(crops)
+        rounds = (n + cap - 1) // cap
+        words = 4 + max(rounds, 1) * D
+        if self.desc.numel() < words:
+            self.desc = torch.zeros(words, dtype=torch.int32, device=self.device)
+        st = self.staging.get('desc', (words,), torch.int32)
+        d = st[0].numpy()
+        d[:] = 0
+        d[0:2] = issue['pair_slots']
+        d[2] = issue['flow_slot']
+        d[3] = rounds
+        rows = sorted({cell for cells in blocks for cell in cells})          # the blocks this frame's boxes belong to
+        used = []                                                              # per round: the rows with a box of that round
+        for r in range(rounds):
+            o = 4 + r * D
+            lo, hi = r * cap, min(n, (r + 1) * cap)
+            d[o] = hi - lo
+            d[o + self.w_crops:o + self.w_crops + 4 * (hi - lo)] = crops[lo:hi].reshape(-1)
+            d[o + self.w_rwin:o + self.w_rwin + sc.T] = issue['raw_slots']
+            d[o + self.w_fwin:o + self.w_fwin + sc.Tf] = issue['flow_slots']
+            masks = d[o + self.w_mask:o + D].view(np.uint8)
+            here = set()
+            for b in range(lo, hi):
+                for (hh, ww) in blocks[b]:
+                    masks[(hh * self.wb + ww) * cap + (b - lo)] = 1
+                    here.add((hh, ww))
+            used.append([i for i, cell in enumerate(rows) if cell in here])
+        desc = self.desc
+        desc[:words].copy_(st[0], non_blocking=True)
+        st[1] = torch.cuda.Event()
+        st[1].record()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        base = desc.data_ptr()
+        # the flow field of the issued frame, in place in the flow ring: the launches of calc_optical_flow.chunk_flows at one pair
+        _lib.check(lib.vv_flow_pairs_prep(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base, 1, self.flow_h, self.flow_w,
+                                          self.flow_in.data_ptr(), stream), 'vv_flow_pairs_prep')
+        self.flow_graph.replay()
+        _lib.check(lib.vv_flow_resize_back(self.flow_out.data_ptr(), 1, self.flow_h, self.flow_w, base + 8, self.H, self.W,
+                                           self.flow_ring.data_ptr(), sc.Rf, stream), 'vv_flow_resize_back')
+        width = rounds * cap
+        out = torch.full((1 + len(rows) * width,), -float(BIG), dtype=torch.float64, device=self.device)
+        keep = torch.zeros(max(width, 1), dtype=torch.uint8, device=self.device)
+        for r in range(rounds):
+            o = 4 + r * D
+            rnd, k = desc[o:o + D], keep[r * cap:(r + 1) * cap]
+            masks = rnd[self.w_mask:].view(torch.uint8)
+            stream_cut(self.raw_ring, self.flow_ring, rnd[0:1], rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
+                       rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
+            for i in used[r]:
+                hh, ww = rows[i]
+                ent = self.blocks[(hh, ww)]
+                raw = of = stats = None
+                if ent is not None:        # the block's model scores the whole store in its own fixed-size launch
+                    raw, of = ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
+                    raw = raw.to(torch.float32).contiguous()
+                    of = of.to(torch.float32).contiguous() if (of is not None and self.use_flow) else None
+                    stats = ent[1]
+                m0 = (hh * self.wb + ww) * cap
+                stream_scores(raw, of, stats, self.w_raw, self.w_of, k, rnd[0:1], masks[m0:m0 + cap],
+                              out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
+        host = torch.empty(out.shape, dtype=torch.float64, pin_memory=True)
+        host_keep = torch.empty(keep.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        host_keep.copy_(keep, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event)
