@@ -574,7 +574,18 @@ int vv_flow_resize_back(const float* flow, int32_t N, int32_t fh, int32_t fw, co
  *   boxes that belong to the block.  Box b counts iff b < n[0], keep[b] and mask[b]; then box_scores[b] = the score of vv_cube_scores
  *   (the same device function; +big without a model) and frame_score[0] = max(frame_score[0], box_scores[b]); a box below n[0] that
  *   does not count gets -big and its errors are not read, slots >= n[0] are not written: whatever they hold, NaN and Inf included, stays
- *   out of the maximum.  The caller starts frame_score[0] at -big; one workgroup, no atomics. */
+ *   out of the maximum.  The caller starts frame_score[0] at -big; one workgroup, no atomics.
+ * vv_stream_boxes: the tables of vv_stream_cut / vv_stream_scores for motion boxes that exist only on the device (StreamScorer with
+ *   boxes = 'motion').  count int32 [1] and boxes int32 [mcap][4] = (x1, y1, x2, y2) as vv_mask_boxes leaves them for one window
+ *   (count may exceed mcap; rows >= min(count, mcap) are not read); slots 0..n_ap-1 of the tables hold the host's appearance boxes
+ *   and are not touched.  With m = min(count, mcap, cap - n_ap): n[0] = n_ap + m, dropped[0] = count - m, and for j < m in slot
+ *   s = n_ap + j: boxes_out int32 [cap][4] = the box; crops int32 [cap][4] = max(x1,0), max(y1,0), min(x2,W), min(y2,H)
+ *   (extract.boxes_to_crops on integers); masks uint8 [hb*wb][cap]: masks[hi*wb + wi][s] = 1 for every cell (hi, wi) of
+ *   utils.calc_block_idx(x1, x2, y1, y2, h_step, w_step, block_mode) -- float64, int(((p + c) / 2.0) / step) per probe point, each
+ *   operation rounded on its own -- that lies inside the hb x wb grid, provided rows [y1, y2) x columns [x1, x2) touch a pixel of a
+ *   grid_h x grid_w mask under Python's slicing (scoring.box_paints); every other byte of columns n_ap..cap-1 of masks is set to 0.
+ *   Slots >= n[0] of crops and boxes_out are not written.  One workgroup.  0 <= n_ap <= cap, cap >= 1, block_mode >= 1 (1: centre;
+ *   2..8: + edge mid-points; >= 9: + corners), steps > 0, else VV_ERR_BAD_ARG without a launch. */
 int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
                   const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win, int32_t cap, int32_t T,
                   int32_t Tf, int32_t P, double thr, uint8_t* raw_store, float* flow_store, uint8_t* keep, double* energy,
@@ -582,6 +593,9 @@ int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, in
 int vv_stream_scores(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
                      const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cap, double* box_scores, double* frame_score,
                      vv_stream stream);
+int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32_t mcap, int32_t n_ap, int32_t cap, int32_t H, int32_t W,
+                    int32_t grid_h, int32_t grid_w, int32_t hb, int32_t wb, double h_step, double w_step, int32_t block_mode,
+                    int32_t* n, int32_t* dropped, int32_t* crops, uint8_t* masks, int32_t* boxes_out, vv_stream stream);
 
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.

@@ -7,6 +7,12 @@ wrote.  The score of a frame comes back one push later (the flow of a frame need
 back at its end).  Writes ``results/<ds>/stream_scores_<fg>_<method>.npy`` and, when the split has frame labels, the frame-level ROC
 ``results/<ds>/<modality>_<fg>_<method>_stream_results.npz`` (per scene for ShanghaiTech, as ``test.py`` evaluates it) and prints its
 AUROC.  ``main`` returns the score vector.  Nothing under ``optical_flow/`` and no cube file is read or written.
+
+With ``[mi355x] stream_boxes = motion`` no ``bboxes_test_*`` file is loaded or written either: every push hands over the frame and the
+rows of ``bboxes_test_obj_det.npy`` for it (when that file exists; none otherwise), and the scorer finds the motion boxes itself, so
+the boxes are those of ``test_bbox_saved = False`` in mode ``obj_det_with_motion`` (another ``foreground_extraction_mode`` is refused:
+the models and statistics are loaded by that mode).  The number of motion boxes that found no free
+slot is printed when it is not 0.
 """
 import os
 import sys
@@ -31,8 +37,25 @@ def scores_path(c):
     return os.path.join('results', c['dataset_name'], 'stream_scores_{}_{}.npy'.format(c['mode_fg'], c['method']))
 
 
+def _detector_boxes(c, n):
+    """``[mi355x] stream_boxes = motion``: the appearance boxes of every test frame as ``foreground._motion_bboxes`` reads them -- the
+    first four columns of the rows of ``bboxes_test_obj_det.npy`` when that file exists (it must hold ``n`` frames), none otherwise."""
+    path = os.path.join(c['raw_dataset_dir'], c['dataset_name'], 'bboxes_test_obj_det.npy')
+    if not os.path.exists(path):
+        print('no {}: motion boxes only (no appearance boxes)'.format(path))
+        return [np.zeros((0, 4), np.float32) for _ in range(n)]
+    ap_all = np.load(path, allow_pickle=True)
+    if len(ap_all) != n:
+        raise ValueError('{} holds boxes of {} frames, the dataset has {}'.format(path, len(ap_all), n))
+    return [np.asarray(b)[:, :4] if np.asarray(b).ndim == 2 else np.zeros((0, 4), np.float32) for b in ap_all]
+
+
 def main(config_path='config.cfg', flownet2=None):
-    c = read_config(config_path)                      # a bad [mi355x] stream_max_boxes raises here, before any GPU work
+    c = read_config(config_path)                      # a bad [mi355x] stream_max_boxes / stream_boxes raises here, before any GPU work
+    if c['stream_boxes'] == 'motion' and c['mode_fg'] != 'obj_det_with_motion':
+        # the boxes would be obj_det_with_motion's while the models and statistics are loaded by mode_fg
+        raise ValueError("[mi355x] stream_boxes = motion scores the boxes of mode obj_det_with_motion; the configured mode is "
+                         "{!r}".format(c['mode_fg']))
     import foreground as FG
     from test import BIG, load_artifacts
     from vad_datasets import get_inputs
@@ -41,10 +64,17 @@ def main(config_path='config.cfg', flownet2=None):
     shanghai = ds == 'ShanghaiTech'
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
-    st = FG._stage(c, 'test', direct_flow=True)       # boxes and the frame indexer over the raw tree; no flow file is globbed
+    motion = c['stream_boxes'] == 'motion'
+    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+    if motion:                                        # the frame indexer alone: no bboxes_test_* file is loaded or written
+        from types import SimpleNamespace
+        os.makedirs(os.path.join(c['data_root_dir'], c['modality']), exist_ok=True)
+        st = SimpleNamespace(raw_ds=FG._datasets(c, 'test', None, direct_flow=True)[0], base=base)
+        st.boxes = _detector_boxes(c, len(st.raw_ds))
+    else:
+        st = FG._stage(c, 'test', direct_flow=True)   # boxes and the frame indexer over the raw tree; no flow file is globbed
     scene_idx, labels = FG._write_frame_index(st, ds, 'test')
     indexer, n = st.raw_ds, len(st.raw_ds)
-    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
     net_set, st_r, st_o = load_artifacts(base, c['mode_fg'], c['method'], shanghai, lambda: build_network(c), device, c['h_block'],
                                          c['w_block'])
     if flownet2 is None:
@@ -66,8 +96,13 @@ def main(config_path='config.cfg', flownet2=None):
         last = key
     if n:
         results += [(last, r) for r in scorers[last].end_video()]
+    dropped = 0
     for key, r in results:
         scores[pushed[key][r.frame]] = r.wait()[0]
+        dropped += r.dropped
+    if dropped:
+        print('{} motion boxes found no free slot and were dropped: raise [mi355x] stream_max_boxes ({})'.format(
+            dropped, c['stream_max_boxes']))
     os.makedirs(os.path.join('results', ds), exist_ok=True)
     np.save(scores_path(c), scores)
     if labels is None:

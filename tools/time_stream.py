@@ -11,9 +11,19 @@ in one process, ``--reps`` times:
           percentile over the frames after ``--warm``; and the wall time of the whole loop with the constructor over the frames.
 
 With ``--no-flow-branch`` the same is repeated on a tree trained and scored with ``useFlow = False`` (the flow UNets are gone; FlowNet2
-still runs, because the motion test reads its flow).  Prints one JSON line; needs the GPU.
+still runs, because the motion test reads its flow).
+
+With ``--stream-boxes motion`` two stream legs alternate instead, on a test video of ``--boxes`` bright rectangles that move over a
+static background (``moving_frames``):
+
+  given   the scorer is handed, for every frame, the boxes the batch route's motion stage finds for it (computed beforehand);
+  motion  ``StreamScorer(boxes='motion')``: ``push`` gets the frame alone and the scorer finds the same boxes on the device.
+
+Both report the same latency figures, the boxes per frame and the dropped boxes; the largest difference of a frame score is 0 when
+every frame's boxes fit ``stream_max_boxes``.  Prints one JSON line; needs the GPU.
 
     timeout 900 python tools/time_stream.py --frames 200 [--boxes 12] [--reps 2] [--no-flow-branch] [--out stream.json]
+    timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --stream-boxes motion [--out stream_motion.json]
 """
 import argparse
 import contextlib
@@ -45,7 +55,8 @@ def batch_leg(net, n):
     return dict(wall_s=wall, ms_per_frame=1e3 * wall / n), np.load(SCORES)
 
 
-def stream_leg(net, warm):
+def stream_leg(net, warm, frames=None, boxes=None, mode='given'):
+    """``frames`` / ``boxes`` None: the test split of the tree and its box file.  ``mode='motion'``: ``push`` gets the frames alone."""
     import torch
     import foreground as FG
     import test as S
@@ -53,30 +64,101 @@ def stream_leg(net, warm):
     from vad_datasets import get_inputs
     from vec_vad_amd.stream import StreamScorer
     c = T.read_config('config.cfg')
-    with contextlib.redirect_stdout(io.StringIO()):
-        st = FG._stage(c, 'test', direct_flow=True)
-    frames = [get_inputs(a) for a in st.raw_ds.all_frame_addr]
+    if frames is None:
+        with contextlib.redirect_stdout(io.StringIO()):
+            st = FG._stage(c, 'test', direct_flow=True)
+        frames, boxes = [get_inputs(a) for a in st.raw_ds.all_frame_addr], st.boxes
     n = len(frames)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     arts = S.load_artifacts(os.path.join(c['data_root_dir'], c['modality'], 'UCSDped2_'), c['mode_fg'], c['method'], False,
                             lambda: T.build_network(c), torch.device('cuda'))
-    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net)
+    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode)
     torch.cuda.synchronize()
     setup = time.perf_counter() - t0
-    scores, lat = np.zeros(n), []
+    scores, lat, found, dropped = np.zeros(n), [], np.zeros(n, np.int64), 0
+
+    def take(results):
+        nonlocal dropped
+        for r in results:
+            scores[r.frame] = r.wait()[0]
+            found[r.frame], dropped = len(r.boxes), dropped + r.dropped
+
     for i in range(n):
         t = time.perf_counter()
-        for r in sc.push(frames[i], st.boxes[i]):
-            scores[r.frame] = r.wait()[0]
+        take(sc.push(frames[i]) if mode == 'motion' else sc.push(frames[i], boxes[i]))
         lat.append(time.perf_counter() - t)
-    for r in sc.end_video():
-        scores[r.frame] = r.wait()[0]
+    take(sc.end_video())
     wall = time.perf_counter() - t0
     steady = 1e3 * np.array(lat[warm:])
     return dict(setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
                 push_to_wait_ms_p95=float(np.percentile(steady, 95)), push_to_wait_ms_max=float(steady.max()),
-                frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap), scores
+                frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap, boxes_per_frame_mean=float(found.mean()),
+                boxes_per_frame_max=int(found.max()), dropped=int(dropped)), scores
+
+
+def moving_frames(n, rects, seed=5):
+    """``n`` grey 240x360 frames for the motion stage: a static low-contrast background (values 96..103) and ``rects`` bright 10 px wide
+    rectangles, each in a cell of its own, each moving its own width per frame and turning at the cell's ends -- so the places a
+    rectangle has in the three frames of a window touch and the motion stage finds ONE box per rectangle, about ``rects`` per frame."""
+    rng = np.random.default_rng(seed)
+    H, W = 240, 360
+    back = rng.integers(96, 104, (H, W), dtype=np.uint8)
+    cols = int(np.ceil(np.sqrt(rects * 1.5)))
+    rows = -(-rects // cols)
+    ch, cw = H // rows, W // cols
+    K = (cw - 8) // 10                                   # places along a cell
+    wave = list(range(K)) + list(range(K - 2, 0, -1))
+    frames = []
+    for t in range(n):
+        g = back.copy()
+        for r in range(rects):
+            y0, x0 = (r // cols) * ch + 4, (r % cols) * cw + 4 + 10 * wave[(t + 3 * r) % len(wave)]
+            g[y0:y0 + min(24 + 2 * (r % 5), ch - 8), x0:x0 + 10] = 200
+        frames.append(g)
+    return frames
+
+
+def measure_motion(a):
+    """``--stream-boxes motion``: the scorer that finds its own boxes next to the scorer that is given the same boxes, alternating in
+    one process on the same frames.  The tree is trained as for the other legs; then the test video is replaced by ``moving_frames``
+    and its boxes are what the batch route finds for them (``foreground._motion_bboxes``, no detector boxes)."""
+    import torch
+    import foreground as FG
+    import train as T
+    from PIL import Image
+    from FlowNet2_src import FlowNet2
+    work = tempfile.mkdtemp(prefix='stream_tree_')
+    os.chdir(work)
+    try:
+        make_tree({'train': (6, 6), 'test': (a.frames,)}, a.boxes, flow=True)
+        cfg = open(os.path.join(ROOT, 'config.cfg')).read()
+        cfg = cfg.replace('epochs = 10', 'epochs = 1').replace('save_score_masks = True', 'save_score_masks = False')
+        open('config.cfg', 'w').write(cfg)
+        subprocess.run([sys.executable, os.path.join(ROOT, 'train.py')], check=True, env=dict(os.environ, PYTHONPATH=ROOT),
+                       stdout=subprocess.DEVNULL, timeout=600)
+        shutil.rmtree(os.path.join('optical_flow', 'UCSDped2', 'Test'))
+        os.remove(os.path.join('raw_datasets', 'UCSDped2', 'bboxes_test_obj_det_with_motion.npy'))
+        grey = moving_frames(a.frames, a.boxes)
+        for k, g in enumerate(grey):
+            Image.fromarray(g).save(os.path.join('raw_datasets', 'UCSDped2', 'Test', 'Test001', '%04d.tif' % (k + 1)))
+        c = T.read_config('config.cfg')
+        boxes = FG._motion_bboxes(c, 'test', os.path.join('raw_datasets', 'UCSDped2', 'bboxes_test_obj_det.npy'), 'cuda', lambda *m: None)
+        frames = [np.repeat(g[..., None], 3, axis=2) for g in grey]
+        torch.manual_seed(0)
+        net = FlowNet2().cuda().eval()
+        res = {'useFlow': True, 'stream_boxes': 'motion', 'given': [], 'motion': [],
+               'boxes_found_per_frame_mean': float(np.mean([len(b) for b in boxes])), 'boxes_found_per_frame_max': max(len(b) for b in boxes)}
+        for _ in range(a.reps):
+            g, sg = stream_leg(net, a.warm, frames, boxes, 'given')
+            m, sm = stream_leg(net, a.warm, frames, None, 'motion')
+            res['given'].append(g)
+            res['motion'].append(m)
+            res['largest_score_difference'] = float(np.abs(sg - sm).max())
+        return res
+    finally:
+        os.chdir(ROOT)
+        shutil.rmtree(work)
 
 
 def measure(a, use_flow):
@@ -119,13 +201,15 @@ def main():
     ap.add_argument('--reps', type=int, default=2)
     ap.add_argument('--warm', type=int, default=20)
     ap.add_argument('--no-flow-branch', action='store_true')
+    ap.add_argument('--stream-boxes', choices=('given', 'motion'), default='given')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     from vec_vad_amd import build as B
     out_path = os.path.abspath(a.out) if a.out else None
-    res = {'frames': a.frames, 'boxes_per_frame': a.boxes, 'library_hash': B.wanted()[1][:16], 'runs': [measure(a, True)]}
-    if a.no_flow_branch:
+    res = {'frames': a.frames, 'boxes_per_frame': a.boxes, 'library_hash': B.wanted()[1][:16]}
+    res['runs'] = [measure_motion(a) if a.stream_boxes == 'motion' else measure(a, True)]
+    if a.no_flow_branch and a.stream_boxes != 'motion':
         print(json.dumps(res), flush=True)               # the first tree's figures, should the second one fail
         res['runs'].append(measure(a, False))
     line = json.dumps(res)

@@ -133,7 +133,8 @@ def read_config(path='config.cfg'):
              render_boxes=cp.getboolean('mi355x', 'render_boxes', fallback=True),
              render_flow=cp.getboolean('mi355x', 'render_flow', fallback=False),
              render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0),
-             stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip())
+             stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip(),
+             stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower())
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
@@ -177,6 +178,9 @@ def read_config(path='config.cfg'):
         pass
     if not isinstance(c['stream_max_boxes'], int) or c['stream_max_boxes'] < 1:
         raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(c['stream_max_boxes']))
+    # where a streamed frame's boxes come from: the caller, or the motion stage on the device
+    from vec_vad_amd.stream import check_stream_boxes
+    c['stream_boxes'] = check_stream_boxes(c['stream_boxes'])
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -4,7 +4,8 @@
 // score under a validity mask.  Both read the number of boxes, the crops, the window slots and the masks from device memory, so their
 // launch arguments never change from frame to frame (they can sit in a captured graph).  Both are small and latency-bound (5-30 boxes a
 // frame): the point is one launch each.  The arithmetic is that of vv_cube_cut / vv_cube_energy / vv_cube_scores, through the shared
-// headers: the same bits.
+// headers: the same bits.  vv_stream_boxes is the third: for a scorer that finds its own motion boxes (vv_motion_mask + vv_mask_boxes leave
+// them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -85,7 +86,78 @@ __global__ void __launch_bounds__(256) stream_scores_kernel(const float* __restr
   if (threadIdx.x == 0) frame_score[0] = fmax(frame_score[0], part[0]);
 }
 
+// Python's slice(a, b).indices(len)[:2] for step 1: a negative bound counts from the end, then both clip to [0, len].
+__device__ __forceinline__ int slice_bound(int v, const int len) {
+  if (v < 0) v = max(v + len, 0);
+  return min(v, len);
+}
+
+// int(q) of a cell quotient lies in [0, cells): the truncation towards zero of Python's int(), decided on the double so that no
+// out-of-range conversion happens.  Returns the cell or -1.
+__device__ __forceinline__ int cell_of(const double q, const int cells) {
+  return (q > -1.0 && q < (double)cells) ? (int)q : -1;
+}
+
+// One workgroup; thread j takes motion slots n_ap + j, n_ap + j + 256, ... and owns the whole mask column of each, so no two threads
+// write one byte.  For the boxes vv_mask_boxes left on the device this is StreamScorer._prepare: boxes_to_crops, box_paints and
+// calc_block_idx, the last in float64 in the order utils.py writes it (contraction is off in this file: every operation rounds on its
+// own, as in Python).  Slots below n_ap belong to the host's appearance boxes and are not touched.
+__global__ void __launch_bounds__(256) stream_boxes_kernel(const int32_t* __restrict__ count_ptr, const int32_t* __restrict__ boxes,
+                                                           int mcap, int n_ap, int cap, int H, int W, int grid_h, int grid_w, int hb,
+                                                           int wb, double h_step, double w_step, int block_mode,
+                                                           int32_t* __restrict__ n_ptr, int32_t* __restrict__ dropped,
+                                                           int32_t* __restrict__ crops, uint8_t* __restrict__ masks,
+                                                           int32_t* __restrict__ boxes_out) {
+  const int count = max(count_ptr[0], 0);
+  const int m = min(min(count, mcap), cap - n_ap);
+  if (threadIdx.x == 0) {
+    n_ptr[0] = n_ap + m;
+    dropped[0] = count - m;
+  }
+  const int npts = block_mode >= 9 ? 9 : (block_mode > 1 ? 5 : 1);
+  for (int s = n_ap + (int)threadIdx.x; s < cap; s += 256) {
+    const int j = s - n_ap;
+    int hi[9], wi[9];
+    int used = 0;
+    if (j < m) {
+      const int x1 = boxes[4 * j + 0], y1 = boxes[4 * j + 1], x2 = boxes[4 * j + 2], y2 = boxes[4 * j + 3];
+      boxes_out[4 * s + 0] = x1, boxes_out[4 * s + 1] = y1, boxes_out[4 * s + 2] = x2, boxes_out[4 * s + 3] = y2;
+      crops[4 * s + 0] = max(x1, 0), crops[4 * s + 1] = max(y1, 0), crops[4 * s + 2] = min(x2, W), crops[4 * s + 3] = min(y2, H);
+      const bool paints = slice_bound(y2, grid_h) > slice_bound(y1, grid_h) && slice_bound(x2, grid_w) > slice_bound(x1, grid_w);
+      if (paints) {
+        const double x_min = x1, x_max = x2, y_min = y1, y_max = y2;
+        const double cy = (y_min + y_max) / 2.0, cx = (x_min + x_max) / 2.0;
+        // calc_block_idx's probe points: centre | edge mid-points | corners
+        const double py[9] = {cy, y_min, y_max, cy, cy, y_min, y_max, y_max, y_min};
+        const double px[9] = {cx, cx, cx, x_min, x_max, x_min, x_max, x_min, x_max};
+        for (int p = 0; p < npts; ++p) {
+          const int h = cell_of(((py[p] + cy) / 2.0) / h_step, hb), w = cell_of(((px[p] + cx) / 2.0) / w_step, wb);
+          if (h >= 0 && w >= 0) hi[used] = h, wi[used] = w, ++used;      // a cell outside the grid gets no bit
+        }
+      }
+    }
+    for (int r = 0; r < hb * wb; ++r) {
+      uint8_t bit = 0;
+      for (int p = 0; p < used; ++p) bit |= (uint8_t)(hi[p] * wb + wi[p] == r);
+      masks[(int64_t)r * cap + s] = bit;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32_t mcap, int32_t n_ap, int32_t cap, int32_t H, int32_t W,
+                               int32_t grid_h, int32_t grid_w, int32_t hb, int32_t wb, double h_step, double w_step, int32_t block_mode,
+                               int32_t* n, int32_t* dropped, int32_t* crops, uint8_t* masks, int32_t* boxes_out, vv_stream stream) {
+  if (mcap < 0 || cap <= 0 || n_ap < 0 || n_ap > cap || H <= 0 || W <= 0 || grid_h <= 0 || grid_w <= 0 || hb <= 0 || wb <= 0)
+    return VV_ERR_BAD_ARG;
+  if (!(h_step > 0.0) || !(w_step > 0.0) || block_mode < 1 || (int64_t)hb * wb * cap > 0x7fffffff) return VV_ERR_BAD_ARG;
+  if (!count || (mcap > 0 && !boxes) || !n || !dropped || !crops || !masks || !boxes_out) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_boxes_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, count, boxes, mcap, n_ap, cap, H, W, grid_h, grid_w, hb, wb,
+            h_step, w_step, block_mode, n, dropped, crops, masks, boxes_out);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
 
 extern "C" int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
                              const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win, int32_t cap,

@@ -26,8 +26,22 @@ model scores the WHOLE store in its own fixed-size launch (the eval-mode graph o
 no compaction.  The scores go to pinned host memory behind an event; ``StreamResult.wait()`` waits on that event and on nothing else.
 A frame with more boxes than ``max_boxes`` takes ``ceil(n / max_boxes)`` rounds of the same launches, max-accumulated on the device.
 
-What is not here: the detector (boxes are the caller's; ``vec_vad_amd.motion`` has the motion stage), decoding, several cameras per
-scorer, and the pixel-level, smoothing and rendering stages of ``test.py``.
+Boxes found on the device (``boxes='motion'``, ``[mi355x] stream_boxes = motion``).  ``push`` then takes the frame alone, and
+optionally the frame's detector boxes.  The boxes of a frame are those of ``test_bbox_saved = False`` in mode ``obj_det_with_motion``:
+the detector's, followed by the motion boxes of the window ``context_range(t, 'hard', 1)`` = the frame and its two neighbours inside
+the video -- the look-ahead frame the flow pair already waits for, so nothing is added to the latency floor (the raw ring holds
+``max(ring_frames, 3)`` frames).  Behind the flow launches ``vv_motion_mask`` (one window, read from the descriptor, which also carries
+the detector boxes as the table the mask erases) and ``vv_mask_boxes`` (through the C ABI into buffers allocated once; count and boxes
+stay on the device) find the boxes, and ``vv_stream_boxes`` does for them what ``push`` does on the host for given boxes: crops, the
+painted-rectangle test and the per-block masks, written behind the detector boxes' slots.  The host learns the number of boxes only
+with the scores (``StreamResult.boxes`` / ``.dropped`` after ``wait()``), and that has two prices.  A frame is ONE round: motion boxes
+beyond the slots the detector boxes leave free of ``max_boxes`` are dropped, in ``vv_mask_boxes``' emission order, and counted.  And
+EVERY block of the ``h_block x w_block`` grid is scored for every frame -- a scoring launch of ``max_boxes`` cubes per block that has
+a model -- since the host cannot know which blocks the motion boxes fall into.  Frames larger than the dataset's nominal frame are
+refused in this mode: a motion box could then lie outside the block grid, which the host refuses for given boxes and cannot see here.
+
+What is not here: the mmdet detector (detector boxes are the caller's), decoding, several cameras per scorer, and the pixel-level,
+smoothing and rendering stages of ``test.py``.
 """
 import os
 
@@ -43,6 +57,12 @@ def ring_frames(context_frame_num):
     """Frames the raw ring holds: the ``context_frame_num + 1`` frames of the 'predict' window of the frame being issued, plus the
     frame pushed behind it (the second frame of its flow pair)."""
     return int(context_frame_num) + 2
+
+
+def motion_ring_frames(context_frame_num):
+    """Frames the raw ring holds when the scorer finds its own motion boxes: the motion window of the frame being issued is the frame
+    before it, the frame and the look-ahead frame, so never fewer than 3."""
+    return max(ring_frames(context_frame_num), 3)
 
 
 def flow_ring_frames(context_of_num):
@@ -61,6 +81,14 @@ def check_max_boxes(v):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
         raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(v))
     return int(v)
+
+
+def check_stream_boxes(v):
+    """``stream_boxes`` as ``'given'`` or ``'motion'``, else a one-line ``ValueError``; no GPU is touched."""
+    w = v.strip().lower() if isinstance(v, str) else v
+    if w not in ('given', 'motion'):
+        raise ValueError("[mi355x] stream_boxes must be 'given' or 'motion', got {!r}".format(v))
+    return w
 
 
 def _dev(name, t, dtype, numel=None):
@@ -120,6 +148,25 @@ def stream_scores(raw, of, stats, w_raw, w_of, keep, n, mask, box_scores, frame_
                'vv_stream_scores')
 
 
+def stream_boxes(count, boxes, n_ap, H, W, grid_h, grid_w, hb, wb, h_step, w_step, block_mode, n, dropped, crops, masks, boxes_out):
+    """``vv_stream_boxes``: what ``StreamScorer._prepare`` forms on the host, for motion boxes that exist only on the device.  count
+    int32 ``[1]`` and boxes int32 ``[mcap,4]`` as ``vv_mask_boxes`` leaves them for one window; ``n_ap``: slots ``0..n_ap-1`` of the
+    tables hold the host's appearance boxes and are not touched.  Written in place, all on the device: n int32 ``[1]`` = ``n_ap + m``
+    with ``m = min(count, mcap, cap - n_ap)``; dropped int32 ``[1]`` = ``count - m``; crops int32 ``[cap,4]`` (``boxes_to_crops``) and
+    boxes_out int32 ``[cap,4]`` in slots ``n_ap..n-1``; masks uint8 ``[hb*wb,cap]``: columns ``n_ap..cap-1`` get 1 in the cells of
+    ``utils.calc_block_idx`` of a box that paints a pixel of the ``grid_h x grid_w`` mask (``scoring.box_paints``), else 0."""
+    _dev('count', count, torch.int32, 1), _dev('boxes', boxes, torch.int32)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or crops.dim() != 2 or crops.shape[1] != 4:
+        raise ValueError('boxes and crops must be [mcap,4] and [cap,4] tensors')
+    cap = crops.shape[0]
+    _dev('crops', crops, torch.int32), _dev('boxes_out', boxes_out, torch.int32, 4 * cap), _dev('n', n, torch.int32, 1)
+    _dev('dropped', dropped, torch.int32, 1), _dev('masks', masks, torch.uint8, int(hb) * int(wb) * cap)
+    _lib.check(_lib.lib().vv_stream_boxes(count.data_ptr(), boxes.data_ptr(), boxes.shape[0], int(n_ap), cap, int(H), int(W), int(grid_h),
+                                          int(grid_w), int(hb), int(wb), float(h_step), float(w_step), int(block_mode), n.data_ptr(),
+                                          dropped.data_ptr(), crops.data_ptr(), masks.data_ptr(), boxes_out.data_ptr(),
+                                          torch.cuda.current_stream(crops.device).cuda_stream), 'vv_stream_boxes')
+
+
 class RingSchedule:
     """The ring bookkeeping of one camera, pure (no GPU).  ``push()`` -> ``(slot, issue | None)``: the raw ring slot the new frame goes
     into, and the frame that can now be issued (the previous frame of the video).  ``end_video()`` -> the issue of the video's last
@@ -127,21 +174,26 @@ class RingSchedule:
 
     An issue is a dict with video-local frame numbers and ring slots: ``frame``; ``raw_frames`` / ``raw_slots`` (the raw window);
     ``flow_frames`` / ``flow_slots`` (the flow window); ``pair_frames`` / ``pair_slots`` (the two frames FlowNet2 sees for the flow of
-    ``frame``) and ``flow_slot`` (where that flow is written before the window is read).  Frame ``k`` of a video lives in raw slot
-    ``k % R``, its flow in flow slot ``k % Rf``."""
+    ``frame``) and ``flow_slot`` (where that flow is written before the window is read); ``motion_frames`` / ``motion_slots`` (the
+    three-frame window of the motion stage, ``context_range(i, 'hard', 1)``: the frame between its two neighbours, itself in place of
+    a neighbour the video does not have).  Frame ``k`` of a video lives in raw slot ``k % R``, its flow in flow slot ``k % Rf``.
+    ``motion``: the raw ring holds ``motion_ring_frames`` frames, never fewer than the three of the motion window; without it the
+    motion slots mean something only where ``ring_frames`` is 3 or more already."""
 
-    def __init__(self, context_frame_num=4, context_of_num=0):
+    def __init__(self, context_frame_num=4, context_of_num=0, motion=False):
         self.T, self.Tf = int(context_frame_num) + 1, int(context_of_num) + 1
-        self.R, self.Rf = ring_frames(context_frame_num), flow_ring_frames(context_of_num)
+        self.R = motion_ring_frames(context_frame_num) if motion else ring_frames(context_frame_num)
+        self.Rf = flow_ring_frames(context_of_num)
         self.count = 0            # frames of the current video pushed so far
 
     def _issue(self, t, last):
         raw = [max(t - self.T + 1 + i, 0) for i in range(self.T)]            # 'predict': up to and including t, first frame repeated
         flow = [max(t - self.Tf + 1 + i, 0) for i in range(self.Tf)]
         pair = (t - 1, t) if last else ((t, t) if t == 0 else (t, t + 1))     # calc_optical_flow.flow_pairs
+        motion = (max(t - 1, 0), t, t if last else t + 1)                     # 'hard' at one frame of context: clipped to the video
         return dict(frame=t, raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
                     flow_slots=[f % self.Rf for f in flow], pair_frames=pair, pair_slots=(pair[0] % self.R, pair[1] % self.R),
-                    flow_slot=t % self.Rf)
+                    flow_slot=t % self.Rf, motion_frames=motion, motion_slots=tuple(f % self.R for f in motion))
 
     def push(self):
         k = self.count
@@ -161,15 +213,24 @@ class StreamResult:
     """The scores of one frame, on their way to the host.  ``frame``: the running index of the frame (pushes are counted from 0 across
     videos).  ``wait()`` blocks until the frame's copy has landed and returns ``(score, box_scores, kept)``: the frame score (float64;
     ``-BIG`` when no box was kept), the score of every box (float64 ``[n]``: the largest over the blocks the box belongs to, ``+BIG`` in
-    a block without a model, ``-BIG`` for a box that was not kept or paints no pixel) and the motion test's flags (bool ``[n]``)."""
+    a block without a model, ``-BIG`` for a box that was not kept or paints no pixel) and the motion test's flags (bool ``[n]``).
+    After ``wait()``: ``boxes``, float64 ``[n,4]``, the boxes the three refer to, and ``dropped``, an int.  With given boxes these are
+    the pushed boxes and 0 (set from the start).  With ``boxes='motion'`` the host learns ``n`` only here: the appearance boxes of the
+    push first, then the motion boxes that were found, and the number of motion boxes that found no free slot."""
 
-    def __init__(self, frame, n, rows, width, host, host_keep, event):
+    def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None):
         self.frame, self._n, self._rows, self._width = frame, n, rows, width
         self._host, self._host_keep, self._event = host, host_keep, event
+        self._given, self._host_found = np.asarray(boxes, np.float64).reshape(-1, 4), host_found      # host_found: n, dropped, boxes_out
+        self.boxes, self.dropped = (self._given, 0) if host_found is None else (None, None)
 
     def wait(self):
         self._event.synchronize()
         a = self._host.numpy()
+        if self._host_found is not None:
+            f = self._host_found.numpy()
+            self._n, self.dropped = int(f[0]), int(f[1])
+            self.boxes = np.concatenate([self._given, f[2:].reshape(-1, 4)[len(self._given):self._n].astype(np.float64)])
         n = self._n
         box = np.full(n, -float(BIG), np.float64)
         if self._rows and n:
@@ -196,7 +257,7 @@ class _Staging:
 
 
 class StreamScorer:
-    """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda')``.
+    """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None)``.
 
     ``c``: the dict of ``train.read_config``; ``net_set`` / ``stats_raw`` / ``stats_of``: what ``test.load_artifacts`` returns;
     ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3); ``flownet2``: the network (None loads
@@ -206,14 +267,27 @@ class StreamScorer:
     w_block`` grid are honoured as ``test.py`` honours them; like there, the grid cells and the painted-rectangle test are those of the
     dataset's nominal frame size (``vad_datasets.frame_size``).
 
-    ``push(frame_u8 [H,W,C], boxes float [n,>=4])`` -> a list with 0 or 1 ``StreamResult`` (the previous frame of the video);
-    ``end_video()`` -> a list with the video's last frame, and the rings start over.  Neither synchronises the host with the device."""
+    ``boxes``: ``'given'`` (the caller hands every frame's boxes to ``push``) or ``'motion'`` (the scorer finds the motion boxes on the
+    device; the dataset must have ``motion.CONSTANTS`` and the frames must not be larger than its nominal frame, else a one-line
+    ``ValueError``); None reads ``[mi355x] stream_boxes``.
 
-    def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda'):
+    ``push(frame_u8 [H,W,C], boxes float [n,>=4])`` -> a list with 0 or 1 ``StreamResult`` (the previous frame of the video);
+    ``end_video()`` -> a list with the video's last frame, and the rings start over.  Neither synchronises the host with the device.
+    With ``boxes='motion'``: ``push(frame_u8, ap_boxes=None)``, where ``ap_boxes`` float ``[k,>=4]`` are the frame's detector boxes (the
+    rows ``bboxes_<mode>_obj_det.npy`` would hold for it), at most ``max_boxes`` of them.  They take slots ``0..k-1`` and are erased
+    from the motion mask, truncated to integers as ``motion._ap_table`` does; the motion boxes follow.  A frame is one round there: motion
+    boxes that find no free slot are dropped in ``vv_mask_boxes``' emission order and counted in ``StreamResult.dropped``."""
+
+    def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda',
+                 boxes=None):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
+        self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
         from vad_datasets import frame_size
+        from vec_vad_amd.motion import CONSTANTS
         from vec_vad_amd.trainer import FusedTrainer
         cp, ds, method = c['cp'], c['dataset_name'], c['method']
+        if self.motion and ds not in CONSTANTS:
+            raise ValueError("stream_boxes = motion: the motion stage has no constants for dataset {!r}".format(ds))
         if cp.get(method, 'border_mode') != 'predict':
             raise ValueError("a stream scores with border_mode = predict only (a centred window needs frames that have not arrived), got "
                              "{!r}".format(cp.get(method, 'border_mode')))
@@ -221,11 +295,14 @@ class StreamScorer:
         if C not in (1, 3):
             raise ValueError('frames must have 1 or 3 channels, got frame_shape {!r}'.format(tuple(frame_shape)))
         self.H, self.W, self.C = H, W, C
-        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'))
+        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion)
         self.P = cp.getint(ds, 'patch_size')
         self.thr = cp.getfloat(ds, 'motionThr')
         self.hb, self.wb = c['h_block'], c['w_block']
         self.grid_h, self.grid_w = frame_size[ds][0], frame_size[ds][1]
+        if self.motion and (H > self.grid_h or W > self.grid_w):
+            raise ValueError('stream_boxes = motion: {}x{} frames are larger than the nominal {}x{} frame of {}, so a motion box could '
+                             'fall outside the block grid'.format(H, W, self.grid_h, self.grid_w, ds))
         self.h_step, self.w_step = self.grid_h / self.hb, self.grid_w / self.wb
         self.block_mode = cp.getint(ds, 'test_block_mode')
         self.w_raw, self.w_of, self.use_flow = float(c['w_raw']), float(c['w_of']), bool(c['useFlow'])
@@ -269,8 +346,21 @@ class StreamScorer:
         self.w_mask = (self.w_fwin + sc.Tf + 3) // 4 * 4
         self.D = self.w_mask + (self.hb * self.wb * cap + 3) // 4
         self.desc = torch.zeros(4 + self.D, dtype=torch.int32, device=dev)      # header: pair (2), flow row, rounds; grows with the rounds
+        if self.motion:
+            # behind the one round of a frame: motion window [3], 1 unused | appearance table [cap][5] = window 0, x1, y1, x2, y2
+            self.w_mwin = 4 + self.D
+            self.w_ap = self.w_mwin + 4
+            self.words_motion = self.w_ap + 5 * cap
+            self.desc = torch.zeros(self.words_motion, dtype=torch.int32, device=dev)
+            self.mt = CONSTANTS[ds]
+            lib = _lib.lib()
+            self.mt_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
+            self.mt_work = torch.empty((lib.vv_mask_boxes_workspace_bytes(1, H, W),), dtype=torch.uint8, device=dev)
+            self.mt_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self.mt_boxes = torch.zeros((cap, 4), dtype=torch.int32, device=dev)                          # mcap = cap
+            self.found = torch.zeros((2 + 4 * cap,), dtype=torch.int32, device=dev)                       # n, dropped, boxes_out [cap][4]
         self.staging = _Staging()
-        self.held = None          # (boxes, crops, blocks) of the frame that waits for its look-ahead
+        self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
         # warm-up: every engine runs its eager launches and captures its graph here, so that push only replays
         for ent in self.blocks.values():
@@ -307,6 +397,13 @@ class StreamScorer:
             raise ValueError('push takes uint8 frames of shape {}, got {} {}'.format((self.H, self.W, self.C), frame.dtype, tuple(frame.shape)))
         boxes = np.asarray(boxes, np.float64)
         boxes = boxes.reshape(-1, boxes.shape[-1])[:, :4] if boxes.ndim == 2 and boxes.shape[0] else np.zeros((0, 4), np.float64)
+        ap = None
+        if self.motion:                                   # the given boxes are the frame's appearance boxes: one round holds them all
+            from .motion import _ap_table
+            if len(boxes) > self.cap:
+                raise ValueError('{} appearance boxes, stream_max_boxes holds {} (with stream_boxes = motion a frame is one '
+                                 'round)'.format(len(boxes), self.cap))
+            ap = _ap_table([boxes], 1)                    # what vv_motion_mask erases: truncated to int32, x2 < 0 refused
         crops = boxes_to_crops(boxes, self.H, self.W)
         paints = box_paints(boxes, self.grid_h, self.grid_w)
         blocks = []
@@ -315,9 +412,13 @@ class StreamScorer:
             if any(not (0 <= hi < self.hb and 0 <= wi < self.wb) for hi, wi in cells):
                 raise IndexError('box {} falls outside the {}x{} block grid'.format(b, self.hb, self.wb))
             blocks.append(sorted(cells) if paints[b] else [])
-        return frame, (boxes, crops, blocks)
+        return frame, (boxes, crops, blocks, ap)
 
-    def push(self, frame_u8, boxes):
+    def push(self, frame_u8, boxes=None, ap_boxes=None):
+        if self.motion:
+            boxes = ap_boxes if ap_boxes is not None else (boxes if boxes is not None else np.zeros((0, 4), np.float64))
+        elif boxes is None or ap_boxes is not None:
+            raise ValueError('push takes the frame and its boxes; ap_boxes and a push without boxes belong to stream_boxes = motion')
         frame, held = self._prepare(frame_u8, boxes)
         slot, issue = self.sched.push()
         st = self.staging.get('frame', frame.shape, torch.uint8)
@@ -335,9 +436,43 @@ class StreamScorer:
         issue = self.sched.end_video()
         return [self._issue(issue, held)] if issue is not None else []
 
+    def _flow(self, base, stream):
+        """The flow field of the issued frame, in place in the flow ring: the launches of ``calc_optical_flow.chunk_flows`` at one pair."""
+        lib, sc = _lib.lib(), self.sched
+        _lib.check(lib.vv_flow_pairs_prep(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base, 1, self.flow_h, self.flow_w,
+                                          self.flow_in.data_ptr(), stream), 'vv_flow_pairs_prep')
+        self.flow_graph.replay()
+        _lib.check(lib.vv_flow_resize_back(self.flow_out.data_ptr(), 1, self.flow_h, self.flow_w, base + 8, self.H, self.W,
+                                           self.flow_ring.data_ptr(), sc.Rf, stream), 'vv_flow_resize_back')
+
+    def _score_block(self, cell, keep, n, masks, box_scores, frame_score):
+        """One block's share of a round: its model scores the whole store in its own fixed-size launch (no launch for a block without a
+        model), ``vv_stream_scores`` reduces under ``keep`` and the block's mask row."""
+        hh, ww = cell
+        ent = self.blocks[cell]
+        raw = of = stats = None
+        if ent is not None:
+            raw, of = ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
+            raw = raw.to(torch.float32).contiguous()
+            of = of.to(torch.float32).contiguous() if (of is not None and self.use_flow) else None
+            stats = ent[1]
+        m0 = (hh * self.wb + ww) * self.cap
+        stream_scores(raw, of, stats, self.w_raw, self.w_of, keep, n, masks[m0:m0 + self.cap], box_scores, frame_score)
+
+    def _read_back(self, *tensors):
+        """Non-blocking copies to fresh pinned memory and the event behind them."""
+        hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
+        for h, t in zip(hosts, tensors):
+            h.copy_(t, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        return hosts, event
+
     def _issue(self, issue, held):
-        _, crops, blocks = held
-        lib, cap, sc, D = _lib.lib(), self.cap, self.sched, self.D
+        if self.motion:
+            return self._issue_motion(issue, held)
+        boxes, crops, blocks, _ = held
+        cap, sc, D = self.cap, self.sched, self.D
         n = len(crops)
         rounds = (n + cap - 1) // cap
         words = 4 + max(rounds, 1) * D
@@ -354,29 +489,13 @@ class StreamScorer:
         for r in range(rounds):
             o = 4 + r * D
             lo, hi = r * cap, min(n, (r + 1) * cap)
-            d[o] = hi - lo
-            d[o + self.w_crops:o + self.w_crops + 4 * (hi - lo)] = crops[lo:hi].reshape(-1)
-            d[o + self.w_rwin:o + self.w_rwin + sc.T] = issue['raw_slots']
-            d[o + self.w_fwin:o + self.w_fwin + sc.Tf] = issue['flow_slots']
-            masks = d[o + self.w_mask:o + D].view(np.uint8)
-            here = set()
-            for b in range(lo, hi):
-                for (hh, ww) in blocks[b]:
-                    masks[(hh * self.wb + ww) * cap + (b - lo)] = 1
-                    here.add((hh, ww))
+            here = self._fill_round(d[o:o + D], issue, crops[lo:hi], blocks[lo:hi])
             used.append([i for i, cell in enumerate(rows) if cell in here])
         desc = self.desc
         desc[:words].copy_(st[0], non_blocking=True)
         st[1] = torch.cuda.Event()
         st[1].record()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        base = desc.data_ptr()
-        # the flow field of the issued frame, in place in the flow ring: the launches of calc_optical_flow.chunk_flows at one pair
-        _lib.check(lib.vv_flow_pairs_prep(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base, 1, self.flow_h, self.flow_w,
-                                          self.flow_in.data_ptr(), stream), 'vv_flow_pairs_prep')
-        self.flow_graph.replay()
-        _lib.check(lib.vv_flow_resize_back(self.flow_out.data_ptr(), 1, self.flow_h, self.flow_w, base + 8, self.H, self.W,
-                                           self.flow_ring.data_ptr(), sc.Rf, stream), 'vv_flow_resize_back')
+        self._flow(desc.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         width = rounds * cap
         out = torch.full((1 + len(rows) * width,), -float(BIG), dtype=torch.float64, device=self.device)
         keep = torch.zeros(max(width, 1), dtype=torch.uint8, device=self.device)
@@ -387,21 +506,64 @@ class StreamScorer:
             stream_cut(self.raw_ring, self.flow_ring, rnd[0:1], rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
                        rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
             for i in used[r]:
-                hh, ww = rows[i]
-                ent = self.blocks[(hh, ww)]
-                raw = of = stats = None
-                if ent is not None:        # the block's model scores the whole store in its own fixed-size launch
-                    raw, of = ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
-                    raw = raw.to(torch.float32).contiguous()
-                    of = of.to(torch.float32).contiguous() if (of is not None and self.use_flow) else None
-                    stats = ent[1]
-                m0 = (hh * self.wb + ww) * cap
-                stream_scores(raw, of, stats, self.w_raw, self.w_of, k, rnd[0:1], masks[m0:m0 + cap],
-                              out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
-        host = torch.empty(out.shape, dtype=torch.float64, pin_memory=True)
-        host_keep = torch.empty(keep.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(out, non_blocking=True)
-        host_keep.copy_(keep, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event)
+                self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
+        (host, host_keep), event = self._read_back(out, keep)
+        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes)
+
+    def _fill_round(self, d, issue, crops, blocks):
+        """One round of the descriptor on the host: the number of boxes, their crops, the two windows and the mask rows.  Returns the set
+        of blocks with a box of the round."""
+        sc, cap = self.sched, self.cap
+        d[0] = len(crops)
+        d[self.w_crops:self.w_crops + 4 * len(crops)] = crops.reshape(-1)
+        d[self.w_rwin:self.w_rwin + sc.T] = issue['raw_slots']
+        d[self.w_fwin:self.w_fwin + sc.Tf] = issue['flow_slots']
+        masks = d[self.w_mask:self.D].view(np.uint8)
+        here = set()
+        for b, cells in enumerate(blocks):
+            for (hh, ww) in cells:
+                masks[(hh * self.wb + ww) * cap + b] = 1
+                here.add((hh, ww))
+        return here
+
+    def _issue_motion(self, issue, held):
+        """A frame whose motion boxes the device finds: ONE round, the appearance boxes in slots ``0..k-1`` as ``_issue`` files them, the
+        motion boxes behind them by ``vv_stream_boxes``, and every block of the grid scored, since the host does not know where a motion
+        box lands."""
+        boxes, crops, blocks, ap = held
+        lib, cap, sc, D, k = _lib.lib(), self.cap, self.sched, self.D, len(held[1])
+        st = self.staging.get('desc', (self.words_motion,), torch.int32)
+        d = st[0].numpy()
+        d[:] = 0
+        d[0:2] = issue['pair_slots']
+        d[2] = issue['flow_slot']
+        d[3] = 1
+        self._fill_round(d[4:4 + D], issue, crops, blocks)
+        d[self.w_mwin:self.w_mwin + 3] = issue['motion_slots']
+        d[self.w_ap:self.w_ap + 5 * len(ap)] = ap.reshape(-1)
+        desc = self.desc
+        desc.copy_(st[0], non_blocking=True)
+        st[1] = torch.cuda.Event()
+        st[1].record()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        base = desc.data_ptr()
+        self._flow(base, stream)
+        c = self.mt
+        _lib.check(lib.vv_motion_mask(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base + 4 * self.w_mwin, 1, c['ksize'],
+                                      c['binary_thr'], base + 4 * self.w_ap if len(ap) else None, len(ap), c['extend'],
+                                      self.mt_mask.data_ptr(), stream), 'vv_motion_mask')
+        _lib.check(lib.vv_mask_boxes(self.mt_mask.data_ptr(), 1, self.H, self.W, c['area_thr'], c['extend'], cap, self.mt_work.data_ptr(),
+                                     self.mt_work.numel(), self.mt_count.data_ptr(), self.mt_boxes.data_ptr(), stream), 'vv_mask_boxes')
+        rnd, found = desc[4:4 + D], self.found
+        n, masks = found[0:1], rnd[self.w_mask:].view(torch.uint8)
+        stream_boxes(self.mt_count, self.mt_boxes, k, self.H, self.W, self.grid_h, self.grid_w, self.hb, self.wb, self.h_step, self.w_step,
+                     self.block_mode, n, found[1:2], rnd[self.w_crops:self.w_rwin].view(cap, 4), masks, found[2:])
+        keep = torch.zeros(cap, dtype=torch.uint8, device=self.device)
+        stream_cut(self.raw_ring, self.flow_ring, n, rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
+                   rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, keep)
+        cells = [(hh, ww) for hh in range(self.hb) for ww in range(self.wb)]
+        out = torch.full((1 + len(cells) * cap,), -float(BIG), dtype=torch.float64, device=self.device)
+        for i, cell in enumerate(cells):
+            self._score_block(cell, keep, n, masks, out[1 + i * cap:1 + (i + 1) * cap], out[0:1])
+        (host, host_keep, host_found), event = self._read_back(out, keep, found)
+        return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found)
