@@ -597,6 +597,44 @@ int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32_t mcap, in
                     int32_t grid_h, int32_t grid_w, int32_t hb, int32_t wb, double h_step, double w_step, int32_t block_mode,
                     int32_t* n, int32_t* dropped, int32_t* crops, uint8_t* masks, int32_t* boxes_out, vv_stream stream);
 
+/* ---- a streamed frame's score mask, its trailing-window mean and the tables its picture needs (StreamScorer with masks / smooth /
+ * render): what test.py's paint, smooth and render stages compute for a finished split, for ONE issued frame, with the box count and
+ * the motion boxes still on the device.  VV_STREAM_UNPAINTED (-100000.0, = VV_SMOOTH_UNPAINTED = VV_RENDER_UNPAINTED) is the background.
+ * vv_stream_paint: one launch.  scores double [rows][width] = the box-score rows vv_stream_scores left (one row per scored block; rows
+ *   or width may be 0); n int32 [1] on the device, clamped to [0, width] = the boxes of the frame (all rounds together).  For b < n:
+ *   box_max[b] = max(unpainted, scores[0][b], ..., scores[rows-1][b]) and the rectangle of box b is rects[b] = (y0, y1, x0, x1) for
+ *   b < n_host -- resolved by the host as for vv_paint_masks -- and else, from boxes int32 [width][4] = (x1, y1, x2, y2) (the
+ *   boxes_out of vv_stream_boxes), y0, y1 = slice(y1, y2).indices(h)[:2] and x0, x1 = slice(x1, x2).indices(w)[:2] on integers (a
+ *   negative bound counts from the end and clips at 0, a bound past the edge clips to it), which is WRITTEN to rects[b].  boxes == NULL:
+ *   every rectangle is the host's.  mask double [h][w] is written whole: mask[y][x] = the largest box_max[b] over the boxes b < n whose
+ *   rectangle holds y0 <= y < y1 and x0 <= x < x1, unpainted where there is none -- what vv_paint_masks paints with box_max over a
+ *   background of unpainted; its maximum is the frame score of vv_stream_scores.  frame_off int32 [2] = (0, n), the CSR table
+ *   vv_render_overlay wants for this one frame.  Slots >= n of scores, rects and boxes are never read and those of box_max and rects
+ *   never written, whatever they hold.  Any number of boxes, staged through LDS VV_STREAM_PAINT_STAGE at a time; a thread owns two
+ *   consecutive pixels; no atomics, no fill launch.  rects 16-byte aligned and distinct from boxes.  VV_ERR_BAD_ARG: negative sizes,
+ *   h * w > 2^31 - 513, NULL n / frame_off, NULL mask with h * w > 0, NULL rects / box_max with width > 0, NULL scores with rows and
+ *   width > 0, misaligned rects.  NaN scores are outside the domain.
+ * vv_stream_smooth: the filter of vv_smooth_masks with a TRAILING temporal window, over a ring of the last masks.  ring double
+ *   [K][h][w] (vv_stream_paint output per slot); win int32 [1 + kt] on the device = the number of frames of the window (clamped to
+ *   1..kt), then their ring slots in ascending frame order (clamped to [0, K)), the last being the issued frame; entries behind the
+ *   count are not read.  Two launches: (a) the X and Y passes of vv_smooth_masks -- the same V, N, A / a, B / b, ascending offsets from
+ *   +0.0, through the same device function -- for the issued frame's slot ONLY, stored into that slot of Bsum double [K][h][w] and bcnt
+ *   uint16 [K][h][w]; the sums of the window's earlier frames are the ones their own calls left there.  (b) C = sum of B over the
+ *   window's slots in the table's order from +0.0, c likewise, out[y][x] = painted ? C / (double)c : unpainted with `painted` read from
+ *   the issued frame's slot of the ring and one IEEE division, and partial[g] = the maximum of out over pixels [256 g, 256 g + 256):
+ *   vv_stream_smooth_partials(h, w) = ceil(h * w / 256) doubles whose maximum is the smoothed frame score (a maximum does not round;
+ *   no atomics).  The result equals vv_smooth_masks with the window 2 kt - 1 on a buffer that ends at the issued frame, read at its
+ *   last frame, bit for bit.  A slot that no entry of win names is not read, whatever it holds.  1 <= kt <= VV_SMOOTH_MAX (any parity),
+ *   ks odd in 1..VV_SMOOTH_MAX (c <= 33 * 33^2 < 2^16); K >= 1.  h * w == 0: VV_OK, nothing is written.  VV_ERR_BAD_ARG: bad windows,
+ *   K < 1, negative sizes, h * w >= 2^31, a NULL pointer with something to do. */
+#define VV_STREAM_PAINT_STAGE 256
+#define VV_STREAM_UNPAINTED (-100000.0)
+int vv_stream_paint(const double* scores, int32_t rows, int32_t width, const int32_t* n, int32_t n_host, int32_t* rects,
+                    const int32_t* boxes, int32_t h, int32_t w, double* mask, double* box_max, int32_t* frame_off, vv_stream stream);
+int64_t vv_stream_smooth_partials(int32_t h, int32_t w);
+int vv_stream_smooth(const double* ring, int32_t K, int32_t h, int32_t w, const int32_t* win, int32_t kt, int32_t ks, double* Bsum,
+                     uint16_t* bcnt, double* out, double* partial, vv_stream stream);
+
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.
  *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats

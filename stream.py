@@ -13,6 +13,13 @@ rows of ``bboxes_test_obj_det.npy`` for it (when that file exists; none otherwis
 the boxes are those of ``test_bbox_saved = False`` in mode ``obj_det_with_motion`` (another ``foreground_extraction_mode`` is refused:
 the models and statistics are loaded by that mode).  The number of motion boxes that found no free
 slot is printed when it is not 0.
+
+``[mi355x] stream_smooth`` also writes ``results/<ds>/stream_scores_smooth_<fg>_<method>.npy`` -- per frame the maximum of the score mask's
+mean over the last ``smooth_frames`` frames and ``smooth_pixels`` pixels -- and, with frame labels, its ROC
+``..._stream_smooth_results.npz`` and AUROC line.  ``[mi355x] stream_render`` writes ``results/<ds>/stream_render/<frame>.png`` (Pillow,
+lossless), the picture of ``test.py``'s render stage without the ground truth.  With either, or ``stream_masks``, a frame's result is
+taken one push after it was issued instead of at the end, so that its pinned buffers go back to the scorer's pool.
+``stream_scores_*.npy`` is the same file whatever these switches say.
 """
 import os
 import sys
@@ -28,13 +35,31 @@ from train import read_config, build_network  # noqa: E402
 from utils import save_roc_pr_curve_data  # noqa: E402
 
 
-def results_path(c, scene=None):
-    return os.path.join('results', c['dataset_name'], '{}_{}_{}_stream_results{}.npz'.format(
-        c['modality'], c['mode_fg'], c['method'], '' if scene is None else '_scene_{}'.format(scene)))
+def results_path(c, scene=None, smooth=False):
+    return os.path.join('results', c['dataset_name'], '{}_{}_{}_stream{}_results{}.npz'.format(
+        c['modality'], c['mode_fg'], c['method'], '_smooth' if smooth else '', '' if scene is None else '_scene_{}'.format(scene)))
 
 
-def scores_path(c):
-    return os.path.join('results', c['dataset_name'], 'stream_scores_{}_{}.npy'.format(c['mode_fg'], c['method']))
+def scores_path(c, smooth=False):
+    return os.path.join('results', c['dataset_name'], 'stream_scores{}_{}_{}.npy'.format('_smooth' if smooth else '', c['mode_fg'],
+                                                                                       c['method']))
+
+
+def render_dir(c):
+    return os.path.join('results', c['dataset_name'], 'stream_render')
+
+
+def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False):
+    """The frame-level ROC of a score vector of the stream, written and printed as ``test.py`` does for its own."""
+    what = 'smoothed stream' if smooth else 'stream'
+    if shanghai:
+        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si, smooth))
+                             for si in sorted(set(scene_idx))]))
+        print('Average frame-level AUC of the {} is {}'.format(what, auc))
+    else:
+        print('Results written to {}:'.format(results_path(c, smooth=smooth)))
+        auc = save_roc_pr_curve_data(scores, labels, results_path(c, smooth=smooth))
+        print('Frame-level AUC of the {} is {}'.format(what, auc))
 
 
 def _detector_boxes(c, n):
@@ -56,6 +81,10 @@ def main(config_path='config.cfg', flownet2=None):
         # the boxes would be obj_det_with_motion's while the models and statistics are loaded by mode_fg
         raise ValueError("[mi355x] stream_boxes = motion scores the boxes of mode obj_det_with_motion; the configured mode is "
                          "{!r}".format(c['mode_fg']))
+    from vad_datasets import frame_size
+    from vec_vad_amd.stream import check_pixel_settings
+    nominal = frame_size[c['dataset_name']][:2]
+    check_pixel_settings(c, None, None, None, nominal, nominal)      # what the keys alone can get wrong is refused here, before any GPU work
     import foreground as FG
     from test import BIG, load_artifacts
     from vad_datasets import get_inputs
@@ -81,7 +110,27 @@ def main(config_path='config.cfg', flownet2=None):
         from calc_optical_flow import load_flownet2
         flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
     scores = np.full(n, -float(BIG), np.float64)
+    pixels = c['stream_masks'] or c['stream_smooth'] or c['stream_render']
+    smooth_scores = np.full(n, -float(BIG), np.float64) if c['stream_smooth'] else None
+    if c['stream_render']:
+        from PIL import Image
+        os.makedirs(render_dir(c), exist_ok=True)
     scorers, pushed, results = {}, {}, []             # per scene: the scorer, the test frames it was given in push order
+    dropped = 0
+
+    def take(upto):
+        """The results ``results[:upto]``, waited for and filed; they leave the list."""
+        nonlocal dropped
+        for key, r in results[:upto]:
+            f = pushed[key][r.frame]
+            scores[f] = r.wait()[0]
+            dropped += r.dropped
+            if smooth_scores is not None:
+                smooth_scores[f] = r.smooth_score
+            if r.picture is not None:
+                Image.fromarray(r.picture).save(os.path.join(render_dir(c), '{}.png'.format(f)))
+        del results[:upto]
+
     last = None                                       # the scene of the frame before
     for i in range(n):
         frame = get_inputs(indexer.all_frame_addr[i])
@@ -94,29 +143,25 @@ def main(config_path='config.cfg', flownet2=None):
         pushed[key].append(i)
         results += [(key, r) for r in scorers[key].push(frame, st.boxes[i])]
         last = key
+        if pixels:                                    # all but the newest: the device stays one frame ahead of the host
+            take(len(results) - 1)
     if n:
         results += [(last, r) for r in scorers[last].end_video()]
-    dropped = 0
-    for key, r in results:
-        scores[pushed[key][r.frame]] = r.wait()[0]
-        dropped += r.dropped
+    take(len(results))
     if dropped:
         print('{} motion boxes found no free slot and were dropped: raise [mi355x] stream_max_boxes ({})'.format(
             dropped, c['stream_max_boxes']))
     os.makedirs(os.path.join('results', ds), exist_ok=True)
     np.save(scores_path(c), scores)
+    if smooth_scores is not None:
+        np.save(scores_path(c, smooth=True), smooth_scores)
     if labels is None:
         print('no frame labels for {} -> frame-level evaluation of the stream skipped'.format(ds))
         return scores
     print('Evaluating the stream of {} by frame-criterion:'.format(ds))
-    if shanghai:
-        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si))
-                             for si in sorted(set(scene_idx))]))
-        print('Average frame-level AUC of the stream is {}'.format(auc))
-    else:
-        print('Results written to {}:'.format(results_path(c)))
-        auc = save_roc_pr_curve_data(scores, labels, results_path(c))
-        print('Frame-level AUC of the stream is {}'.format(auc))
+    _evaluate(c, scores, labels, scene_idx, shanghai)
+    if smooth_scores is not None:
+        _evaluate(c, smooth_scores, labels, scene_idx, shanghai, smooth=True)
     return scores
 
 

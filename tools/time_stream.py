@@ -20,10 +20,18 @@ static background (``moving_frames``):
   motion  ``StreamScorer(boxes='motion')``: ``push`` gets the frame alone and the scorer finds the same boxes on the device.
 
 Both report the same latency figures, the boxes per frame and the dropped boxes; the largest difference of a frame score is 0 when
-every frame's boxes fit ``stream_max_boxes``.  Prints one JSON line; needs the GPU.
+every frame's boxes fit ``stream_max_boxes``.
+
+With ``--masks``, ``--smooth`` and / or ``--render`` a third leg alternates with the other two: the same stream with those switches of
+the scorer on (``render_range = -5,20``; the picture and the masks are copied out in ``wait()``, inside the timed span), reported as
+``stream_pixels`` next to ``stream`` -- the comparison: same process, same box.  ``pixel_launches_us`` is the device time of the added
+launches alone, each timed with events over a batch of back-to-back launches on the scorer's own buffers (``--boxes`` rectangles).
+
+Prints one JSON line; needs the GPU.
 
     timeout 900 python tools/time_stream.py --frames 200 [--boxes 12] [--reps 2] [--no-flow-branch] [--out stream.json]
     timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --stream-boxes motion [--out stream_motion.json]
+    timeout 900 python tools/time_stream.py --frames 200 --masks --smooth --render [--out stream_masks.json]
 """
 import argparse
 import contextlib
@@ -55,8 +63,47 @@ def batch_leg(net, n):
     return dict(wall_s=wall, ms_per_frame=1e3 * wall / n), np.load(SCORES)
 
 
-def stream_leg(net, warm, frames=None, boxes=None, mode='given'):
-    """``frames`` / ``boxes`` None: the test split of the tree and its box file.  ``mode='motion'``: ``push`` gets the frames alone."""
+def pixel_launches_us(sc, n_boxes, batch=50):
+    """Device time of one launch set of each pixel-level stage of ``sc``, in microseconds: events around ``batch`` back-to-back launches
+    on the scorer's own buffers, with ``n_boxes`` rectangles spread over the frame and one row of scores."""
+    import torch
+    from vec_vad_amd import _lib
+    from vec_vad_amd.stream import stream_paint, stream_smooth
+    dev, gh, gw = sc.device, sc.grid_h, sc.grid_w
+    rng = np.random.default_rng(1)
+    y0, x0 = rng.integers(0, gh - 40, n_boxes), rng.integers(0, gw - 40, n_boxes)
+    rects = torch.from_numpy(np.stack([y0, y0 + 36, x0, x0 + 30], axis=1).astype(np.int32)).to(dev)
+    scores = torch.from_numpy(rng.standard_normal((1, n_boxes)) * 3).to(dev)
+    n = torch.tensor([n_boxes], dtype=torch.int32, device=dev)
+    box_max = torch.zeros(n_boxes, dtype=torch.float64, device=dev)
+    win = torch.tensor([sc.sched.K] + list(range(sc.sched.K)), dtype=torch.int32, device=dev)
+    out = {}
+
+    def timed(name, launch):
+        launch()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(batch):
+            launch()
+        b.record()
+        b.synchronize()
+        out[name] = 1e3 * a.elapsed_time(b) / batch
+
+    timed('vv_stream_paint', lambda: stream_paint(scores, n, n_boxes, rects, None, sc.mask_ring[0], box_max, sc.frame_off))
+    if sc.smooth:
+        timed('vv_stream_smooth', lambda: stream_smooth(sc.mask_ring, win, sc.kt, sc.ks, sc.Bsum, sc.bcnt, sc.S, sc.partial))
+    if sc.render:
+        st = torch.cuda.current_stream(dev).cuda_stream
+        timed('vv_render_overlay', lambda: _lib.check(_lib.lib().vv_render_overlay(
+            sc.raw_ring[0].data_ptr(), sc.C, 1, sc.mask_ring[0].data_ptr(), None, rects.data_ptr(), box_max.data_ptr(),
+            sc.frame_off.data_ptr(), n_boxes, sc.lut.data_ptr(), sc.render_lo, sc.render_hi, sc.render_alpha, 1, sc.H, sc.W,
+            sc.picture.data_ptr(), st), 'vv_render_overlay'))
+    return out
+
+
+def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None):
+    """``frames`` / ``boxes`` None: the test split of the tree and its box file.  ``mode='motion'``: ``push`` gets the frames alone.
+    ``pixels``: the ``masks`` / ``smooth`` / ``render`` switches of the scorer (None: all off)."""
     import torch
     import foreground as FG
     import test as S
@@ -64,6 +111,8 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given'):
     from vad_datasets import get_inputs
     from vec_vad_amd.stream import StreamScorer
     c = T.read_config('config.cfg')
+    if pixels and pixels.get('render'):
+        c['render_range'] = (-5.0, 20.0)
     if frames is None:
         with contextlib.redirect_stdout(io.StringIO()):
             st = FG._stage(c, 'test', direct_flow=True)
@@ -73,7 +122,7 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given'):
     t0 = time.perf_counter()
     arts = S.load_artifacts(os.path.join(c['data_root_dir'], c['modality'], 'UCSDped2_'), c['mode_fg'], c['method'], False,
                             lambda: T.build_network(c), torch.device('cuda'))
-    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode)
+    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode, **(pixels or {}))
     torch.cuda.synchronize()
     setup = time.perf_counter() - t0
     scores, lat, found, dropped = np.zeros(n), [], np.zeros(n, np.int64), 0
@@ -91,7 +140,8 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given'):
     take(sc.end_video())
     wall = time.perf_counter() - t0
     steady = 1e3 * np.array(lat[warm:])
-    return dict(setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
+    extra = dict(pixels, pixel_launches_us=pixel_launches_us(sc, max(1, int(found.max())))) if pixels else {}
+    return dict(extra, setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
                 push_to_wait_ms_p95=float(np.percentile(steady, 95)), push_to_wait_ms_max=float(steady.max()),
                 frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap, boxes_per_frame_mean=float(found.mean()),
                 boxes_per_frame_max=int(found.max()), dropped=int(dropped)), scores
@@ -182,12 +232,19 @@ def measure(a, use_flow):
         torch.manual_seed(0)
         net = FlowNet2().cuda().eval()
         res = {'useFlow': use_flow, 'batch': [], 'stream': []}
+        pixels = dict(masks=a.masks, smooth=a.smooth, render=a.render) if (a.masks or a.smooth or a.render) else None
+        if pixels:
+            res['stream_pixels'] = []
         for _ in range(a.reps):
             b, sb = batch_leg(net, a.frames)
             s, ss = stream_leg(net, a.warm)
             res['batch'].append(b)
             res['stream'].append(s)
             res['largest_score_difference'] = float(np.abs(sb - ss).max())
+            if pixels:
+                p, sp = stream_leg(net, a.warm, pixels=pixels)
+                res['stream_pixels'].append(p)
+                res['pixels_change_a_score'] = bool((sp != ss).any())
         return res
     finally:
         os.chdir(ROOT)
@@ -202,6 +259,9 @@ def main():
     ap.add_argument('--warm', type=int, default=20)
     ap.add_argument('--no-flow-branch', action='store_true')
     ap.add_argument('--stream-boxes', choices=('given', 'motion'), default='given')
+    ap.add_argument('--masks', action='store_true')
+    ap.add_argument('--smooth', action='store_true')
+    ap.add_argument('--render', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)

@@ -134,7 +134,10 @@ def read_config(path='config.cfg'):
              render_flow=cp.getboolean('mi355x', 'render_flow', fallback=False),
              render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0),
              stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip(),
-             stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower())
+             stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower(),
+             stream_masks=cp.getboolean('mi355x', 'stream_masks', fallback=False),
+             stream_smooth=cp.getboolean('mi355x', 'stream_smooth', fallback=False),
+             stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False))
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))

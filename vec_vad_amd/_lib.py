@@ -172,6 +172,9 @@ _SIGS = {
     'vv_stream_scores': (c_i32, [c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     'vv_stream_boxes': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp]),
+    'vv_stream_paint': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vv_stream_smooth_partials': (c_i64, [c_i32, c_i32]),
+    'vv_stream_smooth': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'vv_motion_mask': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     'vv_mask_boxes_workspace_bytes': (C.c_int64, [c_i32, c_i32, c_i32]),
     'vv_mask_boxes': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, C.c_int64, c_vp, c_vp, c_vp]),

@@ -9,6 +9,10 @@
 //   smooth_t_kernel: one pixel per thread: the dt loop over the frames of the buffer that belong to the frame's video, one IEEE
 //     division, the store, and the workgroup's maximum (wave shuffle, then LDS) as one partial per workgroup -- no atomics.
 //   smooth_fmax_kernel: one workgroup per frame takes the maximum of the frame's partials.  A maximum does not round: exact.
+//   stream_smooth_xy_kernel / stream_smooth_t_kernel (vv_stream_smooth): the same filter with a TRAILING window over a ring of the last
+//     kt masks of a stream.  Only the issued frame's X/Y sums are formed (smooth_xy_tile, the device function smooth_xy_kernel calls:
+//     the same bits); those of the window's earlier frames wait in their ring slots, 1/kt of the X/Y work of filtering the window
+//     anew.  The window is a table in device memory, so the launch arguments do not change from frame to frame.
 // The job is memory bound: per output frame the mask is read twice (tile with halo; painted test), B / b are written once and read kt
 // times (the frames of a window are neighbours in time, so those reads mostly hit the L2 / MALL), and the output is written once.
 #include <hip/hip_runtime.h>
@@ -31,21 +35,17 @@ __host__ __device__ constexpr int sm_lds_bytes(int rs) {
   return tw * tw * 8 + tw * SM_T * 8 + tw * SM_T * 2 + tw * tw;
 }
 
-__global__ void __launch_bounds__(VV_WG)
-smooth_xy_kernel(const double* __restrict__ masks, const int h, const int w, const int fa, const int tiles_x, const int tiles,
-                 const int rs, double* __restrict__ Bsum, uint16_t* __restrict__ bcnt) {
-  extern __shared__ double sm_lds[];
+// The X/Y sums of tile `tile` of ONE h x w frame `m`, stored at the frame's Bsum / bcnt.  smooth_xy_kernel (a buffer of frames) and
+// stream_smooth_xy_kernel (the one frame a stream issues) both call it: the same operations in the same order, the same bits.
+__device__ __forceinline__ void smooth_xy_tile(const double* __restrict__ m, const int h, const int w, const int tile, const int tiles_x,
+                                               const int rs, double* __restrict__ Bsum, uint16_t* __restrict__ bcnt, double* sm_lds) {
   const int tw = SM_T + 2 * rs;                // side of the tile with its halo
   double* V = sm_lds;                          // [tw][tw]   value or +0.0
   double* A = V + tw * tw;                     // [tw][32]   X sums
   uint16_t* an = reinterpret_cast<uint16_t*>(A + tw * SM_T);        // [tw][32]   X counts
   uint8_t* P = reinterpret_cast<uint8_t*>(an + tw * SM_T);          // [tw][tw]   painted
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x % tiles;
-  const int f = fa + blockIdx.x / tiles;
   const int y0 = (tile / tiles_x) * SM_T, x0 = (tile % tiles_x) * SM_T;
-  const int64_t hw = (int64_t)h * w;
-  const double* m = masks + (int64_t)f * hw;
   for (int i = tid; i < tw * tw; i += VV_WG) {
     const int ly = i / tw, lx = i - ly * tw;
     const int y = y0 - rs + ly, x = x0 - rs + lx;
@@ -84,9 +84,69 @@ smooth_xy_kernel(const double* __restrict__ masks, const int h, const int w, con
       s += A[(ty + k) * SM_T + tx];
       c += an[(ty + k) * SM_T + tx];
     }
-    const int64_t o = (int64_t)f * hw + (int64_t)y * w + x;
+    const int64_t o = (int64_t)y * w + x;
     Bsum[o] = s;
     bcnt[o] = (uint16_t)c;
+  }
+}
+
+__global__ void __launch_bounds__(VV_WG)
+smooth_xy_kernel(const double* __restrict__ masks, const int h, const int w, const int fa, const int tiles_x, const int tiles,
+                 const int rs, double* __restrict__ Bsum, uint16_t* __restrict__ bcnt) {
+  extern __shared__ double sm_lds[];
+  const int64_t fo = (int64_t)(fa + blockIdx.x / tiles) * h * w;
+  smooth_xy_tile(masks + fo, h, w, blockIdx.x % tiles, tiles_x, rs, Bsum + fo, bcnt + fo, sm_lds);
+}
+
+// ---- the trailing window of a stream (vv_stream_smooth) ------------------------------------------------------------------------------
+// win int32 [1 + kt] in device memory: the number of frames of the window (clamped to 1..kt), then their ring slots in ascending
+// frame order (clamped to the ring), the last one being the issued frame.  Entries behind the count are not read.
+struct StreamWin { int count, cur; };
+__device__ __forceinline__ int sm_slot(const int32_t* __restrict__ win, const int j, const int K) { return min(max(win[j], 0), K - 1); }
+__device__ __forceinline__ StreamWin sm_window(const int32_t* __restrict__ win, const int kt, const int K) {
+  StreamWin s;
+  s.count = min(max(win[0], 1), kt);
+  s.cur = sm_slot(win, s.count, K);
+  return s;
+}
+
+// step (a): the X/Y sums of the issued frame's slot alone; the sums of the window's earlier frames stay in their slots
+__global__ void __launch_bounds__(VV_WG)
+stream_smooth_xy_kernel(const double* __restrict__ ring, const int h, const int w, const int K, const int32_t* __restrict__ win,
+                        const int kt, const int tiles_x, const int rs, double* __restrict__ Bsum, uint16_t* __restrict__ bcnt) {
+  extern __shared__ double sm_lds[];
+  const int64_t fo = (int64_t)sm_window(win, kt, K).cur * h * w;
+  smooth_xy_tile(ring + fo, h, w, blockIdx.x, tiles_x, rs, Bsum + fo, bcnt + fo, sm_lds);
+}
+
+// step (b): one pixel per thread: the T sums over the window's slots in the table's order, one IEEE division, the store, and the
+// workgroup's maximum as one partial -- smooth_t_kernel with the window read from a table
+__global__ void __launch_bounds__(VV_WG)
+stream_smooth_t_kernel(const double* __restrict__ ring, const int64_t hw, const int K, const int32_t* __restrict__ win, const int kt,
+                       const double* __restrict__ Bsum, const uint16_t* __restrict__ bcnt, double* __restrict__ out,
+                       double* __restrict__ partial) {
+  __shared__ double wmax[VV_WG / 64];
+  const int64_t pix = (int64_t)blockIdx.x * VV_WG + threadIdx.x;
+  double best = SM_BG;
+  if (pix < hw) {
+    const StreamWin sw = sm_window(win, kt, K);
+    double s = 0.0;
+    int c = 0;
+    for (int j = 1; j <= sw.count; ++j) {      // ascending frame order; the slot is wave-uniform
+      const int64_t o = (int64_t)sm_slot(win, j, K) * hw + pix;
+      s += Bsum[o];
+      c += bcnt[o];
+    }
+    const bool p = ring[(int64_t)sw.cur * hw + pix] != SM_BG;      // a painted pixel counts itself: c >= 1
+    best = p ? s / (double)c : SM_BG;
+    out[pix] = best;
+  }
+  for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_down(best, o));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < VV_WG / 64; ++k) best = fmax(best, wmax[k]);
+    partial[blockIdx.x] = best;
   }
 }
 
@@ -187,5 +247,29 @@ extern "C" int vv_smooth_masks(const double* masks, const int32_t* vid, int32_t 
     VV_LAUNCH(smooth_fmax_kernel, dim3((unsigned)nf), dim3(VV_WG), 0, (hipStream_t)stream, (const double*)partial, nblk, fmax_out);
     VV_CHECK_LAUNCH();
   }
+  return VV_OK;
+}
+
+extern "C" int64_t vv_stream_smooth_partials(int32_t h, int32_t w) {
+  if (h < 0 || w < 0 || (int64_t)h * w > INT32_MAX) return -1;
+  return ((int64_t)h * w + VV_WG - 1) / VV_WG;
+}
+
+extern "C" int vv_stream_smooth(const double* ring, int32_t K, int32_t h, int32_t w, const int32_t* win, int32_t kt, int32_t ks,
+                                double* Bsum, uint16_t* bcnt, double* out, double* partial, vv_stream stream) {
+  if (K < 1 || h < 0 || w < 0 || (int64_t)h * w > INT32_MAX || (int64_t)K * h * w > INT64_MAX / 8) return VV_ERR_BAD_ARG;
+  if (kt < 1 || kt > VV_SMOOTH_MAX || ks < 1 || ks > VV_SMOOTH_MAX || ks % 2 == 0) return VV_ERR_BAD_ARG;
+  const int64_t hw = (int64_t)h * w;
+  if (hw == 0) return VV_OK;                   // frames of no pixels: no partial either, the caller's maximum is the background
+  if (!ring || !win || !Bsum || !bcnt || !out || !partial) return VV_ERR_BAD_ARG;
+  const int rs = ks / 2;
+  const int tiles_x = (w + SM_T - 1) / SM_T, tiles = tiles_x * ((h + SM_T - 1) / SM_T);
+  const int nblk = (int)((hw + VV_WG - 1) / VV_WG);
+  VV_LAUNCH(stream_smooth_xy_kernel, dim3((unsigned)tiles), dim3(VV_WG), (size_t)sm_lds_bytes(rs), (hipStream_t)stream, ring, (int)h,
+            (int)w, (int)K, win, (int)kt, tiles_x, rs, Bsum, bcnt);
+  VV_CHECK_LAUNCH();
+  VV_LAUNCH(stream_smooth_t_kernel, dim3((unsigned)nblk), dim3(VV_WG), 0, (hipStream_t)stream, ring, hw, (int)K, win, (int)kt,
+            (const double*)Bsum, (const uint16_t*)bcnt, out, partial);
+  VV_CHECK_LAUNCH();
   return VV_OK;
 }

@@ -5,7 +5,8 @@
 // launch arguments never change from frame to frame (they can sit in a captured graph).  Both are small and latency-bound (5-30 boxes a
 // frame): the point is one launch each.  The arithmetic is that of vv_cube_cut / vv_cube_energy / vv_cube_scores, through the shared
 // headers: the same bits.  vv_stream_boxes is the third: for a scorer that finds its own motion boxes (vv_motion_mask + vv_mask_boxes leave
-// them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.
+// them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.  vv_stream_paint is
+// the fourth: the frame's box-score rows painted into its score mask, with the box count and the motion boxes still on the device.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -144,7 +145,87 @@ __global__ void __launch_bounds__(256) stream_boxes_kernel(const int32_t* __rest
   }
 }
 
+// ---- the issued frame's score mask (vv_stream_paint) -----------------------------------------------------------------------------------
+constexpr int SP_STAGE = VV_STREAM_PAINT_STAGE;      // boxes per LDS pass = threads of the workgroup
+constexpr int SP_PIX = 2;                            // consecutive pixels per thread: one 16-byte store
+constexpr int SP_TILE = SP_PIX * 256;                // pixels per workgroup
+constexpr double SP_BG = VV_STREAM_UNPAINTED;
+
+// vv_paint_masks' layout for ONE frame whose box count lives on the device: a thread owns two consecutive pixels of the flat h*w mask
+// and walks the boxes, staged in LDS SP_STAGE at a time (every lane reads the same box: broadcast).  Staging box b, a thread takes the
+// maximum of its column of the [rows][width] score rows and its rectangle -- the host's for b < n_host, else Python's slicing of the
+// device's box on integers -- so every workgroup forms the same table; workgroup 0 also leaves it in box_max / rects for the overlay.
+// Rows >= n_host of rects are read by nobody (their rectangles come from `boxes`), so that write races with no read.  The mask is
+// written whole, background included: no fill launch, no atomics.
+__global__ void __launch_bounds__(256) stream_paint_kernel(const double* __restrict__ scores, int rows, int width,
+                                                           const int32_t* __restrict__ n_ptr, int n_host, int4* rects,
+                                                           const int32_t* __restrict__ boxes, int h, int w, double* __restrict__ mask,
+                                                           double* __restrict__ box_max, int32_t* __restrict__ frame_off) {
+  __shared__ int4 srect[SP_STAGE];
+  __shared__ double ssc[SP_STAGE];
+  const int n = min(max(n_ptr[0], 0), width);
+  const int nh = boxes ? min(max(n_host, 0), n) : n;     // without a box table every rectangle is the host's
+  const int hw = h * w;
+  const int p0 = (blockIdx.x * 256 + (int)threadIdx.x) * SP_PIX;
+  const bool in0 = p0 < hw, in1 = p0 + 1 < hw;
+  const int ya = in0 ? p0 / w : -1, xa = in0 ? p0 - ya * w : -1;      // a pixel past the frame lies in no box
+  const int yb = in1 ? (p0 + 1) / w : -1, xb = in1 ? p0 + 1 - yb * w : -1;
+  double v0 = SP_BG, v1 = SP_BG;
+  for (int base = 0; base < n; base += SP_STAGE) {
+    const int cnt = min(SP_STAGE, n - base);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const int b = base + (int)threadIdx.x;
+      int4 r;
+      if (b < nh) {
+        r = rects[b];
+      } else {
+        const int x1 = boxes[4 * b + 0], y1 = boxes[4 * b + 1], x2 = boxes[4 * b + 2], y2 = boxes[4 * b + 3];
+        r = make_int4(slice_bound(y1, h), slice_bound(y2, h), slice_bound(x1, w), slice_bound(x2, w));
+      }
+      double s = SP_BG;
+      for (int i = 0; i < rows; ++i) s = fmax(s, scores[(int64_t)i * width + b]);
+      srect[threadIdx.x] = r;
+      ssc[threadIdx.x] = s;
+      if (blockIdx.x == 0) {
+        box_max[b] = s;
+        if (b >= nh) rects[b] = r;
+      }
+    }
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const int4 r = srect[k];                // y0, y1, x0, x1
+      const double s = ssc[k];
+      if (ya >= r.x && ya < r.y && xa >= r.z && xa < r.w) v0 = fmax(v0, s);
+      if (yb >= r.x && yb < r.y && xb >= r.z && xb < r.w) v1 = fmax(v1, s);
+    }
+  }
+  if (in1 && (reinterpret_cast<uintptr_t>(mask + p0) & 15) == 0) {
+    *reinterpret_cast<double2*>(mask + p0) = make_double2(v0, v1);
+  } else {
+    if (in0) mask[p0] = v0;
+    if (in1) mask[p0 + 1] = v1;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    frame_off[0] = 0;
+    frame_off[1] = n;
+  }
+}
+
 }  // namespace
+
+extern "C" int vv_stream_paint(const double* scores, int32_t rows, int32_t width, const int32_t* n, int32_t n_host, int32_t* rects,
+                               const int32_t* boxes, int32_t h, int32_t w, double* mask, double* box_max, int32_t* frame_off,
+                               vv_stream stream) {
+  if (rows < 0 || width < 0 || n_host < 0 || h < 0 || w < 0 || (int64_t)h * w > INT32_MAX - SP_TILE) return VV_ERR_BAD_ARG;
+  if (!n || !frame_off || ((int64_t)h * w > 0 && !mask) || ((uintptr_t)rects & 15)) return VV_ERR_BAD_ARG;
+  if (width > 0 && (!rects || !box_max || (rows > 0 && !scores))) return VV_ERR_BAD_ARG;
+  const int tiles = max(1, (h * w + SP_TILE - 1) / SP_TILE);      // a frame of no pixels still leaves box_max, rects and frame_off
+  VV_LAUNCH(stream_paint_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, scores, (int)rows, (int)width, n, (int)n_host,
+            reinterpret_cast<int4*>(rects), boxes, (int)h, (int)w, mask, box_max, frame_off);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
 
 extern "C" int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32_t mcap, int32_t n_ap, int32_t cap, int32_t H, int32_t W,
                                int32_t grid_h, int32_t grid_w, int32_t hb, int32_t wb, double h_step, double w_step, int32_t block_mode,

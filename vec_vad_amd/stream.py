@@ -40,8 +40,21 @@ EVERY block of the ``h_block x w_block`` grid is scored for every frame -- a sco
 a model -- since the host cannot know which blocks the motion boxes fall into.  Frames larger than the dataset's nominal frame are
 refused in this mode: a motion box could then lie outside the block grid, which the host refuses for given boxes and cannot see here.
 
-What is not here: the mmdet detector (detector boxes are the caller's), decoding, several cameras per scorer, and the pixel-level,
-smoothing and rendering stages of ``test.py``.
+Where in the frame (``masks`` / ``smooth`` / ``render``; ``[mi355x] stream_masks`` / ``stream_smooth`` / ``stream_render``, all off by
+default -- then nothing more is allocated, launched or copied).  Behind the frame's last ``vv_stream_scores`` the tables that are on
+the device anyway -- the box-score rows, the box count, the boxes -- become pixels, with no word to the host in between.
+``vv_stream_paint`` (one launch) paints the frame's score mask over the dataset's nominal frame, the mask ``test.paint_frame`` paints
+from the box scores and boxes ``wait()`` returns: rectangles of given boxes ride in the descriptor as ``scoring.box_rects`` resolves
+them, those of motion boxes are resolved by the kernel.  ``vv_stream_smooth`` is the filter of ``[mi355x] smooth_masks`` made causal:
+the stream counts ``smooth_frames`` BACKWARDS from the frame (the frames ``max(0, t - smooth_frames + 1) .. t`` of the video), where
+``test.py`` centres its window, so the values are those of the centred filter of ``2 smooth_frames - 1`` frames on a split that ends
+at the frame, not those of ``score_mask_smooth``.  The masks live in a ring of ``smooth_frames`` slots next to their X/Y sums, so a
+frame costs one frame's spatial passes.  ``vv_render_overlay`` then draws the picture of ``[mi355x] render`` from the frame as it lies
+in the raw ring (no ground truth; ``render_range`` must be two numbers, since ``auto`` needs the whole run).  Masks and picture reach
+the host in pooled pinned buffers behind the event ``wait()`` already waits on, which copies them out.
+
+What is not here: the mmdet detector (detector boxes are the caller's), decoding, several cameras per scorer, a centred (delayed)
+smoothing window, per-pixel error maps, and the pixel and region criteria of ``test.py``.
 """
 import os
 
@@ -167,6 +180,80 @@ def stream_boxes(count, boxes, n_ap, H, W, grid_h, grid_w, hb, wb, h_step, w_ste
                                           torch.cuda.current_stream(crops.device).cuda_stream), 'vv_stream_boxes')
 
 
+PAINT_STAGE = 256      # boxes ``vv_stream_paint`` stages in LDS per pass (VV_STREAM_PAINT_STAGE)
+SMOOTH_MAX = 33        # VV_SMOOTH_MAX: the widest window of ``vv_stream_smooth``, in frames and in pixels
+
+
+def stream_paint(scores, n, n_host, rects, boxes, mask, box_max, frame_off):
+    """``vv_stream_paint``: the score mask of one issued frame.  scores float64 ``[rows,width]`` (the box-score rows of
+    ``vv_stream_scores``), n int32 ``[1]``, rects int32 ``[width,4]`` rows ``(y0, y1, x0, x1)`` (16-byte aligned; rows below
+    ``n_host`` resolved by the host with ``scoring.box_rects``), boxes int32 ``[width,4]`` rows ``(x1, y1, x2, y2)`` or None, all on
+    the device.  Written in place: mask float64 ``[h,w]`` whole (``-BIG`` where no box reaches), box_max float64 ``[width]`` below
+    ``n[0]``, rows ``n_host..n[0]-1`` of rects (Python's slicing of the device's boxes) and frame_off int32 ``[2] = (0, n)``.  Slots
+    at or above ``n[0]`` are neither read nor written."""
+    _dev('scores', scores, torch.float64), _dev('mask', mask, torch.float64), _dev('n', n, torch.int32, 1)
+    if scores.dim() != 2 or mask.dim() != 2:
+        raise ValueError('scores must be a [rows,width] and mask an [h,w] tensor')
+    rows, width = scores.shape
+    _dev('rects', rects, torch.int32, 4 * width), _dev('box_max', box_max, torch.float64, width), _dev('frame_off', frame_off, torch.int32, 2)
+    if boxes is not None:
+        _dev('boxes', boxes, torch.int32, 4 * width)
+    _lib.check(_lib.lib().vv_stream_paint(scores.data_ptr(), rows, width, n.data_ptr(), int(n_host), rects.data_ptr(),
+                                          boxes.data_ptr() if boxes is not None else None, mask.shape[0], mask.shape[1], mask.data_ptr(),
+                                          box_max.data_ptr(), frame_off.data_ptr(), torch.cuda.current_stream(mask.device).cuda_stream),
+               'vv_stream_paint')
+
+
+def stream_smooth(ring, win, kt, ks, Bsum, bcnt, out, partial):
+    """``vv_stream_smooth``: the trailing-window mean of the issued frame's mask.  ring float64 ``[K,h,w]`` (a ``stream_paint`` mask
+    per slot), win int32 ``[1+kt]`` on the device (the number of frames of the window, then their ring slots in ascending frame order,
+    the issued frame last), Bsum float64 ``[K,h,w]`` and bcnt int16 ``[K,h,w]`` (16-bit counts; the X/Y sums of every slot, kept from
+    frame to frame: only the issued frame's are formed), out float64 ``[h,w]`` and partial float64 ``[ceil(h*w/256)]``, written in
+    place: the smoothed mask and one maximum per 256 pixels, whose maximum is the smoothed frame score."""
+    _dev('ring', ring, torch.float64), _dev('win', win, torch.int32, 1 + int(kt))
+    if ring.dim() != 3:
+        raise ValueError('ring must be a [K,h,w] tensor')
+    K, h, w = ring.shape
+    _dev('Bsum', Bsum, torch.float64, K * h * w), _dev('bcnt', bcnt, torch.int16, K * h * w), _dev('out', out, torch.float64, h * w)
+    _dev('partial', partial, torch.float64, (h * w + 255) // 256)
+    _lib.check(_lib.lib().vv_stream_smooth(ring.data_ptr(), K, h, w, win.data_ptr(), int(kt), int(ks), Bsum.data_ptr(), bcnt.data_ptr(),
+                                           out.data_ptr(), partial.data_ptr(), torch.cuda.current_stream(ring.device).cuda_stream),
+               'vv_stream_smooth')
+
+
+def check_pixel_settings(c, masks, smooth, render, frame_hw, grid_hw):
+    """The switches of the pixel-level stages of a stream and what they need, checked on the host: ``(masks, smooth, render, kt, ks,
+    source, boxes, lo, hi, alpha)``.  ``smooth`` and ``render`` imply the mask.  One-line ``ValueError``: windows outside 1..33 (an
+    even ``smooth_pixels``), ``render_source = smooth`` without the smoothing, ``render_range = auto`` (it needs the whole run) and
+    frames that are not of the dataset's nominal size (the mask's)."""
+    smooth = bool(c.get('stream_smooth', False) if smooth is None else smooth)
+    render = bool(c.get('stream_render', False) if render is None else render)
+    masks = bool(c.get('stream_masks', False) if masks is None else masks) or smooth or render
+    kt, ks = c.get('smooth_frames', 5), c.get('smooth_pixels', 9)
+    if smooth:
+        if isinstance(kt, bool) or int(kt) != kt or not 1 <= kt <= SMOOTH_MAX:
+            raise ValueError('[mi355x] smooth_frames must be an integer in 1..{} for a stream, got {!r}'.format(SMOOTH_MAX, kt))
+        if isinstance(ks, bool) or int(ks) != ks or not 1 <= ks <= SMOOTH_MAX or ks % 2 == 0:
+            raise ValueError('[mi355x] smooth_pixels must be an odd integer in 1..{}, got {!r}'.format(SMOOTH_MAX, ks))
+    source, lo, hi, alpha = c.get('render_source', 'score'), 0.0, 1.0, 0
+    if render:
+        if source not in ('score', 'smooth'):
+            raise ValueError("[mi355x] render_source must be 'score' or 'smooth', got {!r}".format(source))
+        if source == 'smooth' and not smooth:
+            raise ValueError('[mi355x] render_source = smooth needs stream_smooth = True: only that stage forms the smoothed mask of a stream')
+        rng = c.get('render_range', 'auto')
+        if isinstance(rng, str):
+            raise ValueError('[mi355x] render_range = {} needs the scores of the whole run; a stream takes two numbers lo,hi'.format(rng))
+        lo, hi = float(rng[0]), float(rng[1])
+        if not lo < hi:
+            raise ValueError('[mi355x] render_range must have lo < hi, got {!r}'.format(rng))
+        if tuple(frame_hw) != tuple(grid_hw):
+            raise ValueError('stream_render draws the {}x{} score mask over the frame: {}x{} frames are refused'.format(
+                grid_hw[0], grid_hw[1], frame_hw[0], frame_hw[1]))
+        alpha = (256 * int(c.get('render_alpha', 50)) + 50) // 100          # as test.py's render stage reads the percent
+    return masks, smooth, render, int(kt), int(ks), source, bool(c.get('render_boxes', True)), lo, hi, alpha
+
+
 class RingSchedule:
     """The ring bookkeeping of one camera, pure (no GPU).  ``push()`` -> ``(slot, issue | None)``: the raw ring slot the new frame goes
     into, and the frame that can now be issued (the previous frame of the video).  ``end_video()`` -> the issue of the video's last
@@ -178,10 +265,12 @@ class RingSchedule:
     three-frame window of the motion stage, ``context_range(i, 'hard', 1)``: the frame between its two neighbours, itself in place of
     a neighbour the video does not have).  Frame ``k`` of a video lives in raw slot ``k % R``, its flow in flow slot ``k % Rf``.
     ``motion``: the raw ring holds ``motion_ring_frames`` frames, never fewer than the three of the motion window; without it the
-    motion slots mean something only where ``ring_frames`` is 3 or more already."""
+    motion slots mean something only where ``ring_frames`` is 3 or more already.  ``mask_frames`` = K, the slots of the score-mask ring
+    (the trailing smoothing window in frames; 1 without smoothing): ``mask_slot`` = ``frame % K`` is where the issued frame's mask
+    goes, ``mask_frames`` / ``mask_slots`` the frames ``max(0, frame - K + 1) .. frame`` of the video and their slots, ascending."""
 
-    def __init__(self, context_frame_num=4, context_of_num=0, motion=False):
-        self.T, self.Tf = int(context_frame_num) + 1, int(context_of_num) + 1
+    def __init__(self, context_frame_num=4, context_of_num=0, motion=False, mask_frames=1):
+        self.T, self.Tf, self.K = int(context_frame_num) + 1, int(context_of_num) + 1, int(mask_frames)
         self.R = motion_ring_frames(context_frame_num) if motion else ring_frames(context_frame_num)
         self.Rf = flow_ring_frames(context_of_num)
         self.count = 0            # frames of the current video pushed so far
@@ -191,7 +280,8 @@ class RingSchedule:
         flow = [max(t - self.Tf + 1 + i, 0) for i in range(self.Tf)]
         pair = (t - 1, t) if last else ((t, t) if t == 0 else (t, t + 1))     # calc_optical_flow.flow_pairs
         motion = (max(t - 1, 0), t, t if last else t + 1)                     # 'hard' at one frame of context: clipped to the video
-        return dict(frame=t, raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
+        trail = list(range(max(0, t - self.K + 1), t + 1))                    # the trailing window of the mask smoothing
+        return dict(frame=t, mask_slot=t % self.K, mask_frames=trail, mask_slots=[f % self.K for f in trail], raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
                     flow_slots=[f % self.Rf for f in flow], pair_frames=pair, pair_slots=(pair[0] % self.R, pair[1] % self.R),
                     flow_slot=t % self.Rf, motion_frames=motion, motion_slots=tuple(f % self.R for f in motion))
 
@@ -216,16 +306,38 @@ class StreamResult:
     a block without a model, ``-BIG`` for a box that was not kept or paints no pixel) and the motion test's flags (bool ``[n]``).
     After ``wait()``: ``boxes``, float64 ``[n,4]``, the boxes the three refer to, and ``dropped``, an int.  With given boxes these are
     the pushed boxes and 0 (set from the start).  With ``boxes='motion'`` the host learns ``n`` only here: the appearance boxes of the
-    push first, then the motion boxes that were found, and the number of motion boxes that found no free slot."""
+    push first, then the motion boxes that were found, and the number of motion boxes that found no free slot.
 
-    def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None):
+    With the scorer's pixel-level switches, also after ``wait()`` (None for a switch that is off): ``mask``, float64 ``[gh,gw]``, the
+    frame's score mask as ``test.paint_frame`` paints it from ``box_scores`` and ``boxes`` (its maximum is the frame score);
+    ``smooth_mask`` and ``smooth_score``, its trailing-window mean and that mean's maximum; ``picture``, uint8 ``[H,W,3]`` RGB."""
+
+    def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None, pixels=None):
         self.frame, self._n, self._rows, self._width = frame, n, rows, width
         self._host, self._host_keep, self._event = host, host_keep, event
         self._given, self._host_found = np.asarray(boxes, np.float64).reshape(-1, 4), host_found      # host_found: n, dropped, boxes_out
         self.boxes, self.dropped = (self._given, 0) if host_found is None else (None, None)
+        self._pixels = pixels or {}          # name -> pooled pinned buffer, held until wait() has copied it out
+        self.mask = self.smooth_mask = self.smooth_score = self.picture = None
+
+    def _copy_out(self):
+        """The pixel-level results out of their pooled pinned buffers, which go back to the pool."""
+        px, self._pixels = self._pixels, {}
+        for name, it in px.items():
+            a = it[0].numpy()
+            if name == 'partial':             # one maximum per workgroup; a maximum does not round
+                self.smooth_score = float(a.max()) if a.size else -float(BIG)
+            else:
+                setattr(self, name, a.copy())
+            it[1] = None
+
+    def __del__(self):                        # a result that was never waited for gives its buffers back once its copies have landed
+        for it in self._pixels.values():
+            it[1] = self._event
 
     def wait(self):
         self._event.synchronize()
+        self._copy_out()
         a = self._host.numpy()
         if self._host_found is not None:
             f = self._host_found.numpy()
@@ -255,9 +367,27 @@ class _Staging:
         pool.append(it)
         return it
 
+    def hold(self, key, shape, dtype):
+        """A buffer for a read-back: it stays out of the pool until its reader (``StreamResult``) hands it back."""
+        it = self.get(key, shape, dtype)
+        it[1] = _HELD
+        return it
+
+
+class _Held:
+    """In place of an event on a pooled buffer that a ``StreamResult`` still has to read: never 'completed'."""
+
+    @staticmethod
+    def query():
+        return False
+
+
+_HELD = _Held()
+
 
 class StreamScorer:
-    """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None)``.
+    """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None,
+    masks=None, smooth=None, render=None)``.
 
     ``c``: the dict of ``train.read_config``; ``net_set`` / ``stats_raw`` / ``stats_of``: what ``test.load_artifacts`` returns;
     ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3); ``flownet2``: the network (None loads
@@ -276,10 +406,18 @@ class StreamScorer:
     With ``boxes='motion'``: ``push(frame_u8, ap_boxes=None)``, where ``ap_boxes`` float ``[k,>=4]`` are the frame's detector boxes (the
     rows ``bboxes_<mode>_obj_det.npy`` would hold for it), at most ``max_boxes`` of them.  They take slots ``0..k-1`` and are erased
     from the motion mask, truncated to integers as ``motion._ap_table`` does; the motion boxes follow.  A frame is one round there: motion
-    boxes that find no free slot are dropped in ``vv_mask_boxes``' emission order and counted in ``StreamResult.dropped``."""
+    boxes that find no free slot are dropped in ``vv_mask_boxes``' emission order and counted in ``StreamResult.dropped``.
+
+    ``masks`` / ``smooth`` / ``render`` (None reads ``[mi355x] stream_masks`` / ``stream_smooth`` / ``stream_render``; all off by
+    default, and then nothing below is allocated or launched): the frame's score mask, its trailing-window mean over the last
+    ``smooth_frames`` frames of the video and ``smooth_pixels`` pixels, and its picture (``render_source``, ``render_range`` -- two
+    numbers; ``auto`` is refused --, ``render_alpha``, ``render_boxes``), formed behind the frame's last ``vv_stream_scores`` and
+    delivered with the scores (``StreamResult.mask`` / ``.smooth_mask`` / ``.smooth_score`` / ``.picture``).  ``smooth`` and ``render``
+    imply the mask; a picture needs frames of the dataset's nominal size.  Every refusal is a one-line ``ValueError`` before any GPU
+    work."""
 
     def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda',
-                 boxes=None):
+                 boxes=None, masks=None, smooth=None, render=None):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
         self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
         from vad_datasets import frame_size
@@ -295,7 +433,10 @@ class StreamScorer:
         if C not in (1, 3):
             raise ValueError('frames must have 1 or 3 channels, got frame_shape {!r}'.format(tuple(frame_shape)))
         self.H, self.W, self.C = H, W, C
-        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion)
+        (self.masks, self.smooth, self.render, self.kt, self.ks, self.render_source, self.render_boxes, self.render_lo, self.render_hi,
+         self.render_alpha) = check_pixel_settings(c, masks, smooth, render, (H, W), frame_size[ds][:2])      # before any GPU work
+        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion,
+                                  mask_frames=self.kt if self.smooth else 1)
         self.P = cp.getint(ds, 'patch_size')
         self.thr = cp.getfloat(ds, 'motionThr')
         self.hb, self.wb = c['h_block'], c['w_block']
@@ -359,6 +500,8 @@ class StreamScorer:
             self.mt_count = torch.zeros((1,), dtype=torch.int32, device=dev)
             self.mt_boxes = torch.zeros((cap, 4), dtype=torch.int32, device=dev)                          # mcap = cap
             self.found = torch.zeros((2 + 4 * cap,), dtype=torch.int32, device=dev)                       # n, dropped, boxes_out [cap][4]
+        if self.masks:
+            self._init_pixels()
         self.staging = _Staging()
         self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
@@ -368,6 +511,71 @@ class StreamScorer:
                 for _ in range(3):
                     ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
         torch.cuda.synchronize(dev)
+
+    def _init_pixels(self):
+        """The device state of the pixel-level stages, allocated once: the mask ring (``smooth_frames`` slots, 1 without smoothing),
+        the X/Y sums and counts of every slot, the smoothed mask and its partial maxima, the picture, the colour table, the table of
+        box maxima (it grows with the rounds of a frame) and, behind the descriptor, the tail ``n, 3 unused | window [1 + K], padded
+        to 4 words | rects [width][4]``."""
+        from .render import colormap
+        dev, gh, gw, K = self.device, self.grid_h, self.grid_w, self.sched.K
+        self.mask_ring = torch.full((K, gh, gw), -float(BIG), dtype=torch.float64, device=dev)
+        self.box_max = torch.zeros(self.cap, dtype=torch.float64, device=dev)
+        self.frame_off = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.t_win = 4
+        self.t_rects = self.t_win + (1 + K + 3) // 4 * 4
+        if self.smooth:
+            self.Bsum = torch.zeros((K, gh, gw), dtype=torch.float64, device=dev)
+            self.bcnt = torch.zeros((K, gh, gw), dtype=torch.int16, device=dev)
+            self.S = torch.empty((gh, gw), dtype=torch.float64, device=dev)
+            self.partial = torch.empty(int(_lib.lib().vv_stream_smooth_partials(gh, gw)), dtype=torch.float64, device=dev)
+        if self.render:
+            self.picture = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=dev)
+            self.lut = torch.from_numpy(colormap()).to(dev)
+        if self.motion:                       # one round: the tail has its place behind the descriptor for good
+            self.t_base = (self.words_motion + 3) // 4 * 4
+            self.desc = torch.zeros(self.t_base + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+        else:                                 # room for one round and its tail from the start; more rounds grow it as before
+            self.desc = torch.zeros((4 + self.D + 3) // 4 * 4 + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+
+    def _fill_tail(self, d, issue, n, boxes):
+        """The tail of the descriptor on the host: the total number of boxes, the trailing window and the host's rectangles."""
+        from .scoring import box_rects
+        d[0] = n
+        d[self.t_win] = len(issue['mask_slots'])
+        d[self.t_win + 1:self.t_win + 1 + len(issue['mask_slots'])] = issue['mask_slots']
+        d[self.t_rects:self.t_rects + 4 * len(boxes)] = box_rects(boxes, self.grid_h, self.grid_w).reshape(-1)
+
+    def _pixels(self, issue, tail, scores, n_dev, n_host, boxes_dev):
+        """The launches of the pixel-level stages behind a frame's last ``vv_stream_scores`` and their copies to pooled pinned buffers,
+        all on the current stream: the caller's event behind them covers them.  tail: the descriptor's tail on the device; scores:
+        the ``[rows,width]`` box-score rows; n_dev: the frame's box count on the device; ``n_host`` rectangles are the host's, the
+        others the kernel resolves from ``boxes_dev``."""
+        width = scores.shape[1]
+        if self.box_max.numel() < width:
+            self.box_max = torch.zeros(width, dtype=torch.float64, device=self.device)
+        rects = tail[self.t_rects:self.t_rects + 4 * max(width, 1)]
+        mask = self.mask_ring[issue['mask_slot']]
+        stream_paint(scores, n_dev, n_host, rects, boxes_dev, mask, self.box_max, self.frame_off)
+        out = {'mask': mask}
+        if self.smooth:
+            stream_smooth(self.mask_ring, tail[self.t_win:self.t_win + 1 + self.sched.K], self.kt, self.ks, self.Bsum, self.bcnt, self.S,
+                          self.partial)
+            out['smooth_mask'], out['partial'] = self.S, self.partial
+        if self.render:
+            shown = self.S if self.render_source == 'smooth' else mask
+            draw = self.render_boxes and width > 0
+            _lib.check(_lib.lib().vv_render_overlay(
+                self.raw_ring[issue['raw_slots'][-1]].data_ptr(), self.C, 1, shown.data_ptr(), None, rects.data_ptr() if draw else None,
+                self.box_max.data_ptr() if draw else None, self.frame_off.data_ptr() if draw else None, width if draw else 0,
+                self.lut.data_ptr(), self.render_lo, self.render_hi, self.render_alpha, 1, self.H, self.W, self.picture.data_ptr(),
+                torch.cuda.current_stream(self.device).cuda_stream), 'vv_render_overlay')
+            out['picture'] = self.picture
+        held = {}
+        for name, t in out.items():
+            held[name] = self.staging.hold(name, t.shape, t.dtype)
+            held[name][0].copy_(t, non_blocking=True)
+        return held
 
     @classmethod
     def from_config(cls, config_path='config.cfg', frame_shape=None, flownet2=None, scene=None):
@@ -476,6 +684,9 @@ class StreamScorer:
         n = len(crops)
         rounds = (n + cap - 1) // cap
         words = 4 + max(rounds, 1) * D
+        t_base = (words + 3) // 4 * 4                                          # the tail of the pixel-level stages, 16-byte aligned
+        if self.masks:
+            words = t_base + self.t_rects + 4 * max(rounds * cap, 1)
         if self.desc.numel() < words:
             self.desc = torch.zeros(words, dtype=torch.int32, device=self.device)
         st = self.staging.get('desc', (words,), torch.int32)
@@ -491,6 +702,8 @@ class StreamScorer:
             lo, hi = r * cap, min(n, (r + 1) * cap)
             here = self._fill_round(d[o:o + D], issue, crops[lo:hi], blocks[lo:hi])
             used.append([i for i, cell in enumerate(rows) if cell in here])
+        if self.masks:
+            self._fill_tail(d[t_base:], issue, n, boxes)
         desc = self.desc
         desc[:words].copy_(st[0], non_blocking=True)
         st[1] = torch.cuda.Event()
@@ -507,8 +720,12 @@ class StreamScorer:
                        rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
             for i in used[r]:
                 self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
+        pixels = None
+        if self.masks:
+            tail = desc[t_base:words]
+            pixels = self._pixels(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)
         (host, host_keep), event = self._read_back(out, keep)
-        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes)
+        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes, pixels=pixels)
 
     def _fill_round(self, d, issue, crops, blocks):
         """One round of the descriptor on the host: the number of boxes, their crops, the two windows and the mask rows.  Returns the set
@@ -532,7 +749,7 @@ class StreamScorer:
         box lands."""
         boxes, crops, blocks, ap = held
         lib, cap, sc, D, k = _lib.lib(), self.cap, self.sched, self.D, len(held[1])
-        st = self.staging.get('desc', (self.words_motion,), torch.int32)
+        st = self.staging.get('desc', (self.desc.numel(),), torch.int32)
         d = st[0].numpy()
         d[:] = 0
         d[0:2] = issue['pair_slots']
@@ -541,6 +758,8 @@ class StreamScorer:
         self._fill_round(d[4:4 + D], issue, crops, blocks)
         d[self.w_mwin:self.w_mwin + 3] = issue['motion_slots']
         d[self.w_ap:self.w_ap + 5 * len(ap)] = ap.reshape(-1)
+        if self.masks:                        # the count is the device's (found[0]); the appearance boxes' rectangles are the host's
+            self._fill_tail(d[self.t_base:], issue, k, boxes)
         desc = self.desc
         desc.copy_(st[0], non_blocking=True)
         st[1] = torch.cuda.Event()
@@ -565,5 +784,8 @@ class StreamScorer:
         out = torch.full((1 + len(cells) * cap,), -float(BIG), dtype=torch.float64, device=self.device)
         for i, cell in enumerate(cells):
             self._score_block(cell, keep, n, masks, out[1 + i * cap:1 + (i + 1) * cap], out[0:1])
+        pixels = None
+        if self.masks:
+            pixels = self._pixels(issue, desc[self.t_base:], out[1:].view(len(cells), cap), n, k, found[2:])
         (host, host_keep, host_found), event = self._read_back(out, keep, found)
-        return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found)
+        return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found, pixels=pixels)
