@@ -394,7 +394,10 @@ int vv_nchw_to_out4(int32_t B, int32_t HW, int32_t oc, const float* src, int32_t
 /* ---- FlowNet2 native ops (forward only; FlowNet2 is inference-only in VEC_VAD, calc_optical_flow.py:56-57) ----
  * Same argument meaning as the reference's cffi functions, NCHW fp32 contiguous, stream = current stream.
  * Correlation_forward_cuda  (ops/correlation/src/correlation_cuda.c:11-93, correlation_cuda_kernel.cu:10-106):
- *   no rInput scratch is needed (bounds are predicated instead of materialising zero-padded NHWC copies). */
+ *   no rInput scratch is needed (bounds are predicated instead of materialising zero-padded NHWC copies).
+ *   Served: kernel_size 1 with at most 24 displacements per axis and C * 128 + 256 * span bytes <= 160 KiB of LDS
+ *   (span = 31 * stride1 + 2 * (max_displacement / stride2) * stride2 + 1, made odd), and any odd kernel_size > 1 by a plain
+ *   kernel; the rest, an even kernel_size and corr_type_multiply != 1 return VV_ERR_UNSUPPORTED. */
 int vv_correlation_fwd(const float* in1, const float* in2, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
                        int32_t pad_size, int32_t kernel_size, int32_t max_displacement, int32_t stride1,
                        int32_t stride2, int32_t corr_type_multiply, vv_stream stream);
@@ -403,9 +406,10 @@ int vv_correlation_out_shape(int32_t C, int32_t H, int32_t W, int32_t pad_size, 
                              int32_t* oW);
 /* The same op specialised to how FlowNetC uses it (FlowNetC.py:41-47,92-93,120: pad 20, kernel 1, max_displacement 20,
  * stride1 1, stride2 2, then LeakyReLU(0.1), then torch.cat with conv_redir): NHWC maps in (pixel stride `cstride` floats,
- * C % 32 == 0, 16-byte aligned), result * 1/C through y = v > 0 ? v : slope*v written to channels
- * [out_coff, out_coff+441) of an NHWC buffer with pixel stride out_cstride.  W in {64, 128} (512- and 1024-wide
- * inputs); other widths return VV_ERR_UNSUPPORTED -> use vv_correlation_fwd. */
+ * cstride >= C, cstride % 4 == 0, C % 16 == 0, 16-byte aligned; a pointer into the middle of a wider pixel is a slice), result * 1/C
+ * through y = v > 0 ? v : slope*v written to channels [out_coff, out_coff+441) of an NHWC buffer with pixel stride out_cstride
+ * (element stores: out_cstride and out_coff need no alignment).  W in {64, 128} (512- and 1024-wide inputs); other widths, C % 16 != 0
+ * or a cstride that breaks the rules above return VV_ERR_UNSUPPORTED -> use vv_correlation_fwd. */
 int vv_correlation_nhwc(const float* f1, const float* f2, int32_t cstride, int32_t B, int32_t C, int32_t H, int32_t W,
                         float* out, int32_t out_cstride, int32_t out_coff, float slope, vv_stream stream);
 /* Resample2d_cuda_forward (ops/resample2d/src/Resample2d_cuda.c:8-11, Resample2d_kernel.cu:20-66) */
@@ -490,7 +494,8 @@ int vv_fold_bn(const vv_fold_entry* table_dev, int32_t nentries, int32_t G, cons
  * vv_flownet_prep: inputs [B,3,2,H,W] fp32 (0..rgb_max) -> rgb_mean over (frame, H, W) per image and colour (:66-67),
  *   x = (inputs - rgb_mean) / rgb_max (:69), x6 [B,H,W,8] = cat(x1, x2) + 2 zero channels (:70-72), img0 / img1 [B,H,W,4] =
  *   the two frames + 1 zero channel (FlowNetC's siamese stem).  workspace: vv_flownet_prep_workspace_bytes(B) bytes, 16-byte
- *   aligned like every tensor here.
+ *   aligned like every tensor here.  H * W must be even (the mean is summed with 16-byte loads per colour); an odd H * W returns
+ *   VV_ERR_UNSUPPORTED.
  * vv_warp_pack12: flow = Upsample x4 (mode as vv_upsample4's `bilinear`) of flow2 [B,H/4,W/4,flow_cstride] (channels 0,1)
  *   times `scale` (:76,90); out12 [B,H,W,12] = cat(x6[0:6], Resample2d(img1, flow), flow / div_flow, ChannelNorm(x1 - warped))
  *   (:79-86, 93-100).

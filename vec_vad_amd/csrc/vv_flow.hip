@@ -358,8 +358,10 @@ extern "C" int vv_correlation_fwd(const float* in1, const float* in2, float* out
   const size_t lds = ((size_t)C * CORR_XT + (size_t)CORR_CC * (span | 1)) * sizeof(float);
   if (lds > 160 * 1024) return VV_ERR_UNSUPPORTED;
   const int xtiles = (oW + CORR_XT - 1) / CORR_XT;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)correlation_k1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)correlation_k1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return VV_HIP_STATUS(e);
+  }
   VV_LAUNCH(correlation_k1_kernel, dim3(xtiles * oH, B), dim3(VV_WG), lds, (hipStream_t)stream, in1, in2, out, C,
                      H, W, oC, oH, oW, pad_size, max_displacement, stride1, stride2, dr, xtiles);
   VV_CHECK_LAUNCH();

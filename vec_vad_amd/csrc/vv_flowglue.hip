@@ -232,6 +232,7 @@ extern "C" int64_t vv_flownet_prep_workspace_bytes(int32_t B) { return (int64_t)
 extern "C" int vv_flownet_prep(const float* inputs, int32_t B, int32_t H, int32_t W, float rgb_max, void* workspace,
                                int64_t workspace_bytes, float* x6, float* img0, float* img1, vv_stream stream) {
   if (!inputs || !workspace || !x6 || !img0 || !img1 || B <= 0 || H <= 0 || W <= 0) return VV_ERR_BAD_ARG;
+  if (((int64_t)H * W) & 1) return VV_ERR_UNSUPPORTED;      // prep_sum_kernel's float4 loads: every colour plane pair 16-byte aligned
   if (workspace_bytes < vv_flownet_prep_workspace_bytes(B)) return VV_ERR_BAD_ARG;
   if (((uintptr_t)inputs | (uintptr_t)x6 | (uintptr_t)img0 | (uintptr_t)img1) & 15) return VV_ERR_BAD_ARG;
   const int nblk = 64;
@@ -272,6 +273,7 @@ extern "C" int vv_fusion_pack11(const float* x6, const float* img1, const float*
 extern "C" int vv_flownet_prep_f16(const float* inputs, int32_t B, int32_t H, int32_t W, float rgb_max, void* workspace,
                                    int64_t workspace_bytes, uint16_t* x6, uint16_t* img0, uint16_t* img1, vv_stream stream) {
   if (!inputs || !workspace || !x6 || !img0 || !img1 || B <= 0 || H <= 0 || W <= 0) return VV_ERR_BAD_ARG;
+  if (((int64_t)H * W) & 1) return VV_ERR_UNSUPPORTED;
   if (workspace_bytes < vv_flownet_prep_workspace_bytes(B)) return VV_ERR_BAD_ARG;
   if (((uintptr_t)inputs | (uintptr_t)x6 | (uintptr_t)img0 | (uintptr_t)img1) & 15) return VV_ERR_BAD_ARG;
   const int nblk = 64;
