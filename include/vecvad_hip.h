@@ -640,6 +640,45 @@ int64_t vv_stream_smooth_partials(int32_t h, int32_t w);
 int vv_stream_smooth(const double* ring, int32_t K, int32_t h, int32_t w, const int32_t* win, int32_t kt, int32_t ks, double* Bsum,
                      uint16_t* bcnt, double* out, double* partial, vv_stream stream);
 
+/* ---- a streamed frame's boxes linked into tracks (StreamScorer with tracks): one launch behind the frame's last vv_stream_scores,
+ * over the tables vv_stream_paint reads.  All geometry is in integers and every sum is taken in one stated order, so the result is
+ * exact.  The state belongs to the caller (one camera): t_meta int32 [max_tracks][8] = (id, age, hits, y0, y1, x0, x1, 0), t_hist
+ * double [max_tracks][window] and next_id int32 [1] (started at 1 by the caller; it never goes back).  A live slot has id > 0, age =
+ * the issued frames since its last match, hits = its matched frames, its last matched rectangle and, at position (k - 1) % window of
+ * its row of t_hist, the score of its k-th match; a free slot is all zeros, history included.
+ * vv_stream_tracks, in this order:
+ *   0. reset != 0 (the first frame of a video): every slot is freed, whatever it holds.
+ *   1. n int32 [1] on the device, clamped to [0, width].  Box b < n has the score s_b = max(-big, scores[0][b], ..,
+ *      scores[rows-1][b]) (vv_stream_paint's box_max) and vv_stream_paint's rectangle: rects[b] = (y0, y1, x0, x1) for b < n_host, else
+ *      Python's slicing of boxes[b] = (x1, y1, x2, y2) in an h x w mask; boxes == NULL: every rectangle is the host's.  rects is only
+ *      read here, and a host rectangle is clipped to the mask.  Box b is a detection iff its rectangle is not empty and s_b > -big.
+ *   2. every live track: age += 1.
+ *   3. track t and detection d are a candidate pair iff inter > 0 and 100 * inter >= iou_pct * (area_t + area_d - inter), in int64.
+ *      Pairs are ordered by IoU descending (inter_a * union_b against inter_b * union_a in int64), then lower slot, then lower box;
+ *      the matching is the greedy one under that order, computed as iterated mutual-best choice (at most min(live tracks, detections)
+ *      rounds, each of which ends by construction).  A matched track takes the detection's rectangle, age = 0, hits += 1 and s_d at
+ *      position (hits - 1) % window of its history.
+ *   4. an unmatched track with age > max_age is freed.
+ *   5. unmatched detections in ascending box index take the free slots in ascending slot order: id = next_id++, age 0, hits 1, their
+ *      rectangle and score.  A detection that finds no free slot has no track and is counted in dropped.
+ *   6. for b < n: box_track[b] = (id, hits) of the box's track, (0, 0) for a box that is no detection or was dropped;
+ *      box_track_score[b] = the mean of the track's last min(hits, window) scores, summed from +0.0 from the oldest to the newest and
+ *      divided once, -big for id 0.  frame_track_score[0] = the largest box_track_score[b] over the boxes whose track has hits >=
+ *      min_hits, -big if there is none.  counts int32 [3] = (live slots, dropped, next_id).
+ *   Slots >= n of scores, rects and boxes are never read and those of box_track and box_track_score never written.  One workgroup;
+ *   rectangles and scores are staged through LDS VV_STREAM_TRACK_STAGE at a time, so any n <= width goes; ordinary stores only, nothing
+ *   waits for another workgroup.  VV_ERR_BAD_ARG without a launch: max_tracks outside 1..VV_STREAM_MAX_TRACKS, window outside
+ *   1..VV_STREAM_TRACK_WINDOW, iou_pct outside 1..100, max_age < 0, min_hits < 1, negative sizes, h * w > INT32_MAX, NULL t_meta /
+ *   t_hist / next_id / n / frame_track_score / counts, NULL rects / box_track / box_track_score with width > 0, NULL scores with rows
+ *   and width > 0.  NaN scores are outside the domain. */
+#define VV_STREAM_TRACK_STAGE 256
+#define VV_STREAM_MAX_TRACKS 1024
+#define VV_STREAM_TRACK_WINDOW 32
+int vv_stream_tracks(int32_t* t_meta, double* t_hist, int32_t* next_id, int32_t max_tracks, const double* scores, int32_t rows,
+                     int32_t width, const int32_t* n, int32_t n_host, const int32_t* rects, const int32_t* boxes, int32_t h, int32_t w,
+                     int32_t reset, int32_t iou_pct, int32_t max_age, int32_t window, int32_t min_hits, double big, int32_t* box_track,
+                     double* box_track_score, double* frame_track_score, int32_t* counts, vv_stream stream);
+
 /* ---- motion-based foreground boxes (fore_det/obj_det_with_motion.py:144-223 get_mt_bboxes), integer arithmetic throughout ----
  * vv_motion_mask: one launch for N windows of three frames.
  *   frames uint8 [F][H][W][C], C = 1 | 3, 4-byte aligned; win int32 [N][3] = frame indices of each window (a 'hard' border repeats

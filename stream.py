@@ -20,6 +20,10 @@ mean over the last ``smooth_frames`` frames and ``smooth_pixels`` pixels -- and,
 lossless), the picture of ``test.py``'s render stage without the ground truth.  With either, or ``stream_masks``, a frame's result is
 taken one push after it was issued instead of at the end, so that its pinned buffers go back to the scorer's pool.
 ``stream_scores_*.npy`` is the same file whatever these switches say.
+
+``[mi355x] stream_tracks`` also writes ``results/<ds>/stream_scores_track_<fg>_<method>.npy`` -- per frame the largest mean score of a
+track seen ``track_min_hits`` times or more (``StreamResult.track_score``) -- and, with frame labels, its ROC
+``..._stream_track_results.npz`` and AUROC line; every other file is the one written without the key.
 """
 import os
 import sys
@@ -35,30 +39,31 @@ from train import read_config, build_network  # noqa: E402
 from utils import save_roc_pr_curve_data  # noqa: E402
 
 
-def results_path(c, scene=None, smooth=False):
+def results_path(c, scene=None, smooth=False, track=False):
     return os.path.join('results', c['dataset_name'], '{}_{}_{}_stream{}_results{}.npz'.format(
-        c['modality'], c['mode_fg'], c['method'], '_smooth' if smooth else '', '' if scene is None else '_scene_{}'.format(scene)))
+        c['modality'], c['mode_fg'], c['method'], '_smooth' if smooth else ('_track' if track else ''),
+        '' if scene is None else '_scene_{}'.format(scene)))
 
 
-def scores_path(c, smooth=False):
-    return os.path.join('results', c['dataset_name'], 'stream_scores{}_{}_{}.npy'.format('_smooth' if smooth else '', c['mode_fg'],
-                                                                                       c['method']))
+def scores_path(c, smooth=False, track=False):
+    return os.path.join('results', c['dataset_name'], 'stream_scores{}_{}_{}.npy'.format(
+        '_smooth' if smooth else ('_track' if track else ''), c['mode_fg'], c['method']))
 
 
 def render_dir(c):
     return os.path.join('results', c['dataset_name'], 'stream_render')
 
 
-def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False):
+def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False, track=False):
     """The frame-level ROC of a score vector of the stream, written and printed as ``test.py`` does for its own."""
-    what = 'smoothed stream' if smooth else 'stream'
+    what = 'smoothed stream' if smooth else ("stream's tracks" if track else 'stream')
     if shanghai:
-        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si, smooth))
+        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si, smooth, track))
                              for si in sorted(set(scene_idx))]))
         print('Average frame-level AUC of the {} is {}'.format(what, auc))
     else:
-        print('Results written to {}:'.format(results_path(c, smooth=smooth)))
-        auc = save_roc_pr_curve_data(scores, labels, results_path(c, smooth=smooth))
+        print('Results written to {}:'.format(results_path(c, smooth=smooth, track=track)))
+        auc = save_roc_pr_curve_data(scores, labels, results_path(c, smooth=smooth, track=track))
         print('Frame-level AUC of the {} is {}'.format(what, auc))
 
 
@@ -112,6 +117,7 @@ def main(config_path='config.cfg', flownet2=None):
     scores = np.full(n, -float(BIG), np.float64)
     pixels = c['stream_masks'] or c['stream_smooth'] or c['stream_render']
     smooth_scores = np.full(n, -float(BIG), np.float64) if c['stream_smooth'] else None
+    track_scores = np.full(n, -float(BIG), np.float64) if c['stream_tracks'] else None
     if c['stream_render']:
         from PIL import Image
         os.makedirs(render_dir(c), exist_ok=True)
@@ -127,6 +133,8 @@ def main(config_path='config.cfg', flownet2=None):
             dropped += r.dropped
             if smooth_scores is not None:
                 smooth_scores[f] = r.smooth_score
+            if track_scores is not None:
+                track_scores[f] = r.track_score
             if r.picture is not None:
                 Image.fromarray(r.picture).save(os.path.join(render_dir(c), '{}.png'.format(f)))
         del results[:upto]
@@ -155,6 +163,8 @@ def main(config_path='config.cfg', flownet2=None):
     np.save(scores_path(c), scores)
     if smooth_scores is not None:
         np.save(scores_path(c, smooth=True), smooth_scores)
+    if track_scores is not None:
+        np.save(scores_path(c, track=True), track_scores)
     if labels is None:
         print('no frame labels for {} -> frame-level evaluation of the stream skipped'.format(ds))
         return scores
@@ -162,6 +172,8 @@ def main(config_path='config.cfg', flownet2=None):
     _evaluate(c, scores, labels, scene_idx, shanghai)
     if smooth_scores is not None:
         _evaluate(c, smooth_scores, labels, scene_idx, shanghai, smooth=True)
+    if track_scores is not None:
+        _evaluate(c, track_scores, labels, scene_idx, shanghai, track=True)
     return scores
 
 

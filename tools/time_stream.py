@@ -27,11 +27,17 @@ the scorer on (``render_range = -5,20``; the picture and the masks are copied ou
 ``stream_pixels`` next to ``stream`` -- the comparison: same process, same box.  ``pixel_launches_us`` is the device time of the added
 launches alone, each timed with events over a batch of back-to-back launches on the scorer's own buffers (``--boxes`` rectangles).
 
+With ``--tracks`` a further leg alternates with the others: the same stream through ``StreamScorer(tracks=True)`` with the stock
+``track_*`` keys, reported as ``stream_tracks`` next to ``stream``.  ``track_launch_us`` is the device time of ``vv_stream_tracks`` alone,
+timed like the pixel launches: ``--boxes`` rectangles that every launch finds where the launch before left them, so a launch is one
+matching round in a table of ``stream_max_tracks`` slots.
+
 Prints one JSON line; needs the GPU.
 
     timeout 900 python tools/time_stream.py --frames 200 [--boxes 12] [--reps 2] [--no-flow-branch] [--out stream.json]
     timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --stream-boxes motion [--out stream_motion.json]
     timeout 900 python tools/time_stream.py --frames 200 --masks --smooth --render [--out stream_masks.json]
+    timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --tracks [--out stream_tracks.json]
 """
 import argparse
 import contextlib
@@ -101,9 +107,41 @@ def pixel_launches_us(sc, n_boxes, batch=50):
     return out
 
 
-def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None):
+def track_launch_us(sc, n_boxes, batch=50):
+    """Device time of one ``vv_stream_tracks`` launch with the settings of ``sc``, in microseconds: events around ``batch`` back-to-back
+    launches over a table of its own, ``n_boxes`` rectangles spread over the frame and one row of scores."""
+    import torch
+    from vec_vad_amd.stream import stream_tracks
+    dev, gh, gw = sc.device, sc.grid_h, sc.grid_w
+    rng = np.random.default_rng(1)
+    y0, x0 = rng.integers(0, gh - 40, n_boxes), rng.integers(0, gw - 40, n_boxes)
+    rects = torch.from_numpy(np.stack([y0, y0 + 36, x0, x0 + 30], axis=1).astype(np.int32)).to(dev)
+    scores = torch.from_numpy(rng.standard_normal((1, n_boxes)) * 3).to(dev)
+    n = torch.tensor([n_boxes], dtype=torch.int32, device=dev)
+    t_meta = torch.zeros((sc.trk_max, 8), dtype=torch.int32, device=dev)
+    t_hist = torch.zeros((sc.trk_max, sc.trk_window), dtype=torch.float64, device=dev)
+    next_id = torch.ones(1, dtype=torch.int32, device=dev)
+    box_track = torch.zeros((n_boxes, 2), dtype=torch.int32, device=dev)
+    box_score, frame_score = torch.zeros(n_boxes, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+    counts = torch.zeros(3, dtype=torch.int32, device=dev)
+
+    def launch():
+        stream_tracks(t_meta, t_hist, next_id, scores, n, n_boxes, rects, None, gh, gw, False, sc.trk_iou, sc.trk_age, sc.trk_hits, box_track,
+                      box_score, frame_score, counts)
+
+    launch()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(batch):
+        launch()
+    b.record()
+    b.synchronize()
+    return dict(vv_stream_tracks=1e3 * a.elapsed_time(b) / batch, live=int(counts[0]), next_id=int(counts[2]))
+
+
+def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tracks=False):
     """``frames`` / ``boxes`` None: the test split of the tree and its box file.  ``mode='motion'``: ``push`` gets the frames alone.
-    ``pixels``: the ``masks`` / ``smooth`` / ``render`` switches of the scorer (None: all off)."""
+    ``pixels``: the ``masks`` / ``smooth`` / ``render`` switches of the scorer (None: all off).  ``tracks``: its ``tracks`` switch."""
     import torch
     import foreground as FG
     import test as S
@@ -122,16 +160,21 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None):
     t0 = time.perf_counter()
     arts = S.load_artifacts(os.path.join(c['data_root_dir'], c['modality'], 'UCSDped2_'), c['mode_fg'], c['method'], False,
                             lambda: T.build_network(c), torch.device('cuda'))
-    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode, **(pixels or {}))
+    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode, tracks=tracks, **(pixels or {}))
     torch.cuda.synchronize()
     setup = time.perf_counter() - t0
     scores, lat, found, dropped = np.zeros(n), [], np.zeros(n, np.int64), 0
+    trk = dict(live_max=0, next_id=1, dropped=0, frames_with_a_track_score=0)
 
     def take(results):
         nonlocal dropped
         for r in results:
             scores[r.frame] = r.wait()[0]
             found[r.frame], dropped = len(r.boxes), dropped + r.dropped
+            if tracks:
+                trk['live_max'], trk['dropped'] = max(trk['live_max'], len(r.tracks)), trk['dropped'] + r.tracks_dropped
+                trk['next_id'] = max([trk['next_id']] + [int(i) + 1 for i in r.track_ids])
+                trk['frames_with_a_track_score'] += r.track_score > -1e5
 
     for i in range(n):
         t = time.perf_counter()
@@ -141,6 +184,8 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None):
     wall = time.perf_counter() - t0
     steady = 1e3 * np.array(lat[warm:])
     extra = dict(pixels, pixel_launches_us=pixel_launches_us(sc, max(1, int(found.max())))) if pixels else {}
+    if tracks:
+        extra.update(tracks=trk, track_launch_us=track_launch_us(sc, max(1, int(found.max()))))
     return dict(extra, setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
                 push_to_wait_ms_p95=float(np.percentile(steady, 95)), push_to_wait_ms_max=float(steady.max()),
                 frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap, boxes_per_frame_mean=float(found.mean()),
@@ -235,6 +280,8 @@ def measure(a, use_flow):
         pixels = dict(masks=a.masks, smooth=a.smooth, render=a.render) if (a.masks or a.smooth or a.render) else None
         if pixels:
             res['stream_pixels'] = []
+        if a.tracks:
+            res['stream_tracks'] = []
         for _ in range(a.reps):
             b, sb = batch_leg(net, a.frames)
             s, ss = stream_leg(net, a.warm)
@@ -245,6 +292,10 @@ def measure(a, use_flow):
                 p, sp = stream_leg(net, a.warm, pixels=pixels)
                 res['stream_pixels'].append(p)
                 res['pixels_change_a_score'] = bool((sp != ss).any())
+            if a.tracks:
+                t, st = stream_leg(net, a.warm, tracks=True)
+                res['stream_tracks'].append(t)
+                res['tracks_change_a_score'] = bool((st != ss).any())
         return res
     finally:
         os.chdir(ROOT)
@@ -262,6 +313,7 @@ def main():
     ap.add_argument('--masks', action='store_true')
     ap.add_argument('--smooth', action='store_true')
     ap.add_argument('--render', action='store_true')
+    ap.add_argument('--tracks', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)

@@ -137,7 +137,13 @@ def read_config(path='config.cfg'):
              stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower(),
              stream_masks=cp.getboolean('mi355x', 'stream_masks', fallback=False),
              stream_smooth=cp.getboolean('mi355x', 'stream_smooth', fallback=False),
-             stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False))
+             stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False),
+             stream_tracks=cp.getboolean('mi355x', 'stream_tracks', fallback=False),
+             track_iou_percent=cp.getint('mi355x', 'track_iou_percent', fallback=30),
+             track_max_age=cp.getint('mi355x', 'track_max_age', fallback=5),
+             track_window=cp.getint('mi355x', 'track_window', fallback=8),
+             track_min_hits=cp.getint('mi355x', 'track_min_hits', fallback=3),
+             stream_max_tracks=cp.getint('mi355x', 'stream_max_tracks', fallback=128))
     for key in ('pixel_overlap_percent', 'region_iou_percent', 'track_percent'):
         if not 1 <= c[key] <= 100:
             raise ValueError('[mi355x] {} must be an integer in 1..100, got {}'.format(key, c[key]))
@@ -182,8 +188,9 @@ def read_config(path='config.cfg'):
     if not isinstance(c['stream_max_boxes'], int) or c['stream_max_boxes'] < 1:
         raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(c['stream_max_boxes']))
     # where a streamed frame's boxes come from: the caller, or the motion stage on the device
-    from vec_vad_amd.stream import check_stream_boxes
+    from vec_vad_amd.stream import check_stream_boxes, check_track_settings
     c['stream_boxes'] = check_stream_boxes(c['stream_boxes'])
+    check_track_settings(c, None)                      # the settings of a stream's tracks, checked whatever the switch says
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

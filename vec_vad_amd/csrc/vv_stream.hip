@@ -7,6 +7,7 @@
 // headers: the same bits.  vv_stream_boxes is the third: for a scorer that finds its own motion boxes (vv_motion_mask + vv_mask_boxes leave
 // them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.  vv_stream_paint is
 // the fourth: the frame's box-score rows painted into its score mask, with the box count and the motion boxes still on the device.
+// vv_stream_tracks is the fifth: over the same tables, the frame's boxes linked to the tracks of the frames before, in one workgroup.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -212,7 +213,282 @@ __global__ void __launch_bounds__(256) stream_paint_kernel(const double* __restr
   }
 }
 
+// ---- the issued frame's boxes linked into tracks (vv_stream_tracks) ---------------------------------------------------------------------
+constexpr int ST_STAGE = VV_STREAM_TRACK_STAGE;      // detections per LDS pass = threads of the workgroup
+constexpr int ST_MAX = VV_STREAM_MAX_TRACKS;
+constexpr int ST_PER = ST_MAX / 256;                 // consecutive slots a thread takes in the scan over free slots
+static_assert(ST_STAGE == 256 && ST_MAX % 256 == 0, "one detection of a stage per thread, whole slots per thread");
+
+// Rectangles are int4 (y0, y1, x0, x1), clipped to the h x w mask: an intersection is then at most h * w <= INT32_MAX.
+__device__ __forceinline__ int4 st_clip(const int y0, const int y1, const int x0, const int x1, const int h, const int w) {
+  return make_int4(min(max(y0, 0), h), min(max(y1, 0), h), min(max(x0, 0), w), min(max(x1, 0), w));
+}
+
+// The rectangle of box b as vv_stream_paint resolves it.
+__device__ __forceinline__ int4 st_box_rect(const int b, const int nh, const int32_t* __restrict__ rects,
+                                            const int32_t* __restrict__ boxes, const int h, const int w) {
+  if (b < nh) return st_clip(rects[4 * b + 0], rects[4 * b + 1], rects[4 * b + 2], rects[4 * b + 3], h, w);
+  const int x1 = boxes[4 * b + 0], y1 = boxes[4 * b + 1], x2 = boxes[4 * b + 2], y2 = boxes[4 * b + 3];
+  return make_int4(slice_bound(y1, h), slice_bound(y2, h), slice_bound(x1, w), slice_bound(x2, w));
+}
+
+__device__ __forceinline__ int64_t st_area(const int4 r) { return (int64_t)(r.y - r.x) * (r.w - r.z); }
+
+__device__ __forceinline__ int st_inter(const int4 a, const int4 b) {
+  const int iy = min(a.y, b.y) - max(a.x, b.x), ix = min(a.w, b.w) - max(a.z, b.z);
+  return (iy > 0 && ix > 0) ? iy * ix : 0;
+}
+
+// Exclusive scan of one int per thread over the workgroup, through LDS; *total = the sum.  Every thread calls it.
+__device__ __forceinline__ int st_scan(const int v, int* buf, int* total) {
+  const int tid = (int)threadIdx.x;
+  buf[tid] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int add = tid >= off ? buf[tid - off] : 0;
+    __syncthreads();
+    buf[tid] += add;
+    __syncthreads();
+  }
+  const int incl = buf[tid];
+  *total = buf[255];
+  __syncthreads();
+  return incl - v;
+}
+
+__device__ __forceinline__ void st_free(int32_t* meta, double* hist, const int window) {
+  for (int k = 0; k < 8; ++k) meta[k] = 0;
+  for (int k = 0; k < window; ++k) hist[k] = 0.0;
+}
+
+// One workgroup.  Slot t is owned by thread t % 256: only its owner touches its row of t_meta and t_hist until the matching is over,
+// and the rectangles and flags (0 free, 1 live and unmatched, 2 matched) of all slots lie in LDS.  Box b's detection state lives in
+// box_track[b][0] (-1 no detection, 0 unmatched, slot + 1 matched) and its score in box_track_score[b] until the last pass puts the
+// outputs there; thread b % 256 alone reads and writes them.  A round of the matching: every unmatched track finds its best unmatched
+// detection over all stages (ties: the lower box), then every unmatched detection its best unmatched track (ties: the lower slot); a
+// pair that chose each other is matched.  The best pair of the whole order always is one, and a mutual-best pair is in the greedy
+// matching, since every pair ahead of it in the order holds neither of its two.  Flags and rectangles change only between rounds.
+__global__ void __launch_bounds__(256) stream_tracks_kernel(int32_t* t_meta, double* t_hist, int32_t* __restrict__ next_id,
+                                                            int max_tracks,
+                                                            const double* __restrict__ scores, int rows, int width,
+                                                            const int32_t* __restrict__ n_ptr, int n_host,
+                                                            const int32_t* __restrict__ rects, const int32_t* __restrict__ boxes, int h,
+                                                            int w, int reset, int iou_pct, int max_age, int window, int min_hits,
+                                                            double big, int32_t* box_track, double* box_track_score,
+                                                            double* __restrict__ frame_track_score, int32_t* __restrict__ counts) {
+  __shared__ int4 trect[ST_MAX];
+  __shared__ int tflag[ST_MAX];
+  __shared__ int tbi[ST_MAX];            // a track's best candidate of the round: intersection, union, box (-1: none)
+  __shared__ unsigned tbu[ST_MAX];
+  __shared__ int tbd[ST_MAX];            // ... and, once the matching is over, the free slots in ascending order
+  __shared__ int tnew[ST_MAX];           // the box a track was matched with in this round, or -1
+  __shared__ int4 srect[ST_STAGE];
+  __shared__ int sstate[ST_STAGE];
+  __shared__ int scan[256];
+  __shared__ double part[256];
+  __shared__ int s_live, s_det, s_match;          // s_match: the pairs matched so far in this launch
+  const int tid = (int)threadIdx.x;
+  const int n = min(max(n_ptr[0], 0), width);
+  const int nh = boxes ? min(max(n_host, 0), n) : n;
+  const int next0 = next_id[0];
+  if (tid == 0) s_live = 0, s_det = 0, s_match = 0;
+  __syncthreads();
+  // steps 0 and 2: reset, ageing; the live tracks' rectangles into LDS
+  for (int t = tid; t < ST_MAX; t += 256) {
+    int flag = 0;
+    if (t < max_tracks) {
+      int32_t* m = t_meta + 8 * t;
+      if (reset) {
+        st_free(m, t_hist + (int64_t)t * window, window);
+      } else if (m[0] > 0) {
+        m[1] += 1;
+        flag = 1;
+        trect[t] = st_clip(m[3], m[4], m[5], m[6], h, w);
+        atomicAdd(&s_live, 1);
+      }
+    }
+    tflag[t] = flag;
+  }
+  // step 1: detections
+  for (int b = tid; b < n; b += 256) {
+    double s = -big;
+    for (int i = 0; i < rows; ++i) s = fmax(s, scores[(int64_t)i * width + b]);
+    const int4 r = st_box_rect(b, nh, rects, boxes, h, w);
+    const bool det = r.y > r.x && r.w > r.z && s > -big;
+    box_track_score[b] = s;
+    box_track[2 * b + 0] = det ? 0 : -1;
+    box_track[2 * b + 1] = 0;
+    if (det) atomicAdd(&s_det, 1);
+  }
+  __syncthreads();
+  // step 3: matching
+  const int max_rounds = min(s_live, s_det);
+  __syncthreads();                     // s_live is counted anew below
+  for (int round = 0, matched = 0; round < max_rounds; ++round) {
+    for (int t = tid; t < ST_MAX; t += 256) tbi[t] = 0, tbu[t] = 1u, tbd[t] = -1, tnew[t] = -1;
+    for (int pass = 0; pass < 2; ++pass) {
+      for (int base = 0; base < n; base += ST_STAGE) {
+        const int cnt = min(ST_STAGE, n - base);
+        __syncthreads();
+        if (tid < cnt) {
+          const int b = base + tid;
+          srect[tid] = st_box_rect(b, nh, rects, boxes, h, w);
+          sstate[tid] = box_track[2 * b];
+        }
+        __syncthreads();
+        if (pass == 0) {               // a thread's tracks against the stage's detections
+          for (int t = tid; t < max_tracks; t += 256) {
+            if (tflag[t] != 1) continue;
+            const int4 rt = trect[t];
+            const int64_t at = st_area(rt);
+            int bi = tbi[t], bd = tbd[t];
+            int64_t bu = tbu[t];
+            for (int k = 0; k < cnt; ++k) {
+              if (sstate[k] != 0) continue;
+              const int4 rd = srect[k];
+              const int inter = st_inter(rt, rd);
+              if (inter <= 0) continue;
+              const int64_t uni = at + st_area(rd) - inter;
+              if ((int64_t)100 * inter >= (int64_t)iou_pct * uni && (int64_t)inter * bu > (int64_t)bi * uni) bi = inter, bu = uni, bd = base + k;
+            }
+            tbi[t] = bi, tbu[t] = (unsigned)bu, tbd[t] = bd;
+          }
+        } else if (tid < cnt && sstate[tid] == 0) {      // a thread's detection against all tracks
+          const int b = base + tid;
+          const int4 rd = srect[tid];
+          const int64_t ad = st_area(rd);
+          int bi = 0, bt = -1;
+          int64_t bu = 1;
+          for (int t = 0; t < max_tracks; ++t) {
+            if (tflag[t] != 1) continue;
+            const int4 rt = trect[t];
+            const int inter = st_inter(rt, rd);
+            if (inter <= 0) continue;
+            const int64_t uni = st_area(rt) + ad - inter;
+            if ((int64_t)100 * inter >= (int64_t)iou_pct * uni && (int64_t)inter * bu > (int64_t)bi * uni) bi = inter, bu = uni, bt = t;
+          }
+          if (bt >= 0 && tbd[bt] == b) {
+            tnew[bt] = b;
+            box_track[2 * b] = bt + 1;
+            atomicAdd(&s_match, 1);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    for (int t = tid; t < max_tracks; t += 256) {
+      const int d = tnew[t];
+      if (tflag[t] != 1 || d < 0) continue;
+      const int4 r = st_box_rect(d, nh, rects, boxes, h, w);
+      int32_t* m = t_meta + 8 * t;
+      const int hits = max(m[2], 0) + 1;
+      m[1] = 0, m[2] = hits, m[3] = r.x, m[4] = r.y, m[5] = r.z, m[6] = r.w;
+      t_hist[(int64_t)t * window + (hits - 1) % window] = box_track_score[d];
+      tflag[t] = 2;
+    }
+    const int before = matched;
+    matched = s_match;                  // counted before the barrier above, counted on behind the one below
+    __syncthreads();
+    if (matched == before || matched >= max_rounds) break;      // no candidate pair is left, or no track or no detection
+  }
+  // step 4: deaths
+  if (tid == 0) s_live = 0;
+  __syncthreads();
+  for (int t = tid; t < max_tracks; t += 256) {
+    if (tflag[t] == 0) continue;
+    int32_t* m = t_meta + 8 * t;
+    if (tflag[t] == 1 && m[1] > max_age) {
+      st_free(m, t_hist + (int64_t)t * window, window);
+      tflag[t] = 0;
+    } else {
+      atomicAdd(&s_live, 1);
+    }
+  }
+  __syncthreads();
+  // the free slots in ascending order
+  int nfree = 0;
+  {
+    int c = 0;
+    for (int k = 0; k < ST_PER; ++k) {
+      const int t = ST_PER * tid + k;
+      c += (t < max_tracks && tflag[t] == 0);
+    }
+    int at = st_scan(c, scan, &nfree);
+    for (int k = 0; k < ST_PER; ++k) {
+      const int t = ST_PER * tid + k;
+      if (t < max_tracks && tflag[t] == 0) tbd[at++] = t;
+    }
+  }
+  __syncthreads();
+  // steps 5 and 6: births in ascending box index, and every box's outputs
+  int unmatched = 0;
+  double best = -INFINITY;
+  for (int base = 0; base < n; base += ST_STAGE) {
+    const int b = base + tid;
+    const int state = b < n ? box_track[2 * b] : -1;
+    int total;
+    const int k = unmatched + st_scan(state == 0, scan, &total);
+    unmatched += total;
+    if (b >= n) continue;
+    int id = 0, hits = 0;
+    double ts = -big;
+    if (state > 0) {
+      const int t = state - 1;
+      id = t_meta[8 * t + 0], hits = t_meta[8 * t + 2];
+      const int m = min(hits, window);
+      double acc = 0.0;
+      for (int j = 0; j < m; ++j) acc += t_hist[(int64_t)t * window + (hits - m + j) % window];
+      ts = acc / (double)m;
+    } else if (state == 0 && k < nfree) {
+      const int t = tbd[k];
+      const int4 r = st_box_rect(b, nh, rects, boxes, h, w);
+      const double s = box_track_score[b];
+      int32_t* m = t_meta + 8 * t;
+      id = next0 + k, hits = 1;
+      m[0] = id, m[1] = 0, m[2] = 1, m[3] = r.x, m[4] = r.y, m[5] = r.z, m[6] = r.w, m[7] = 0;
+      double* hist = t_hist + (int64_t)t * window;
+      hist[0] = s;
+      for (int j = 1; j < window; ++j) hist[j] = 0.0;
+      ts = (0.0 + s) / 1.0;
+    }
+    box_track[2 * b + 0] = id;
+    box_track[2 * b + 1] = hits;
+    box_track_score[b] = ts;
+    if (id > 0 && hits >= min_hits) best = fmax(best, ts);
+  }
+  part[tid] = best;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) part[tid] = fmax(part[tid], part[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int births = min(unmatched, nfree);
+    frame_track_score[0] = part[0] == -INFINITY ? -big : part[0];
+    counts[0] = s_live + births;
+    counts[1] = unmatched - births;
+    counts[2] = next0 + births;
+    next_id[0] = next0 + births;
+  }
+}
+
 }  // namespace
+
+extern "C" int vv_stream_tracks(int32_t* t_meta, double* t_hist, int32_t* next_id, int32_t max_tracks, const double* scores, int32_t rows,
+                                int32_t width, const int32_t* n, int32_t n_host, const int32_t* rects, const int32_t* boxes, int32_t h,
+                                int32_t w, int32_t reset, int32_t iou_pct, int32_t max_age, int32_t window, int32_t min_hits, double big,
+                                int32_t* box_track, double* box_track_score, double* frame_track_score, int32_t* counts,
+                                vv_stream stream) {
+  if (max_tracks < 1 || max_tracks > ST_MAX || window < 1 || window > VV_STREAM_TRACK_WINDOW || iou_pct < 1 || iou_pct > 100) return VV_ERR_BAD_ARG;
+  if (max_age < 0 || min_hits < 1 || rows < 0 || width < 0 || n_host < 0 || h < 0 || w < 0 || (int64_t)h * w > INT32_MAX) return VV_ERR_BAD_ARG;
+  if (!t_meta || !t_hist || !next_id || !n || !frame_track_score || !counts) return VV_ERR_BAD_ARG;
+  if (width > 0 && (!rects || !box_track || !box_track_score || (rows > 0 && !scores))) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_tracks_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, t_meta, t_hist, next_id, (int)max_tracks, scores, (int)rows,
+            (int)width, n, (int)n_host, rects, boxes, (int)h, (int)w, (int)reset, (int)iou_pct, (int)max_age, (int)window, (int)min_hits,
+            big, box_track, box_track_score, frame_track_score, counts);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
 
 extern "C" int vv_stream_paint(const double* scores, int32_t rows, int32_t width, const int32_t* n, int32_t n_host, int32_t* rects,
                                const int32_t* boxes, int32_t h, int32_t w, double* mask, double* box_max, int32_t* frame_off,

@@ -53,8 +53,19 @@ frame costs one frame's spatial passes.  ``vv_render_overlay`` then draws the pi
 in the raw ring (no ground truth; ``render_range`` must be two numbers, since ``auto`` needs the whole run).  Masks and picture reach
 the host in pooled pinned buffers behind the event ``wait()`` already waits on, which copies them out.
 
+Which object, and for how long (``tracks``; ``[mi355x] stream_tracks``, off by default -- then nothing more is allocated, launched or
+copied).  One more launch over the same tables, ``vv_stream_tracks``, links the frame's boxes to the tracks of the video's earlier
+frames: greedy matching by IoU in integers, best pair first, in a table of ``stream_max_tracks`` slots that stays on the device and is
+emptied at the first frame of a video (``RingSchedule`` says which that is).  A track keeps the scores of its last ``track_window``
+matches; a box's track score is their mean, the frame's the largest over tracks matched ``track_min_hits`` times or more, so that one
+badly reconstructed cube of an object seen once cannot raise the alarm, and a track that finds no box coasts ``track_max_age`` frames.
+It needs the descriptor's tail (the count and the host's rectangles) but no mask; its outputs and the table ride to pinned memory in
+one copy behind the same event (``StreamResult.track_ids`` / ``.track_hits`` / ``.track_scores`` / ``.track_score`` /
+``.tracks_dropped`` / ``.tracks``).  The defaults of its keys are untuned picks; no accuracy is claimed for them.
+
 What is not here: the mmdet detector (detector boxes are the caller's), decoding, several cameras per scorer, a centred (delayed)
-smoothing window, per-pixel error maps, and the pixel and region criteria of ``test.py``.
+smoothing window, per-pixel error maps, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment
+by the Hungarian method, re-identification and ids drawn into the picture.
 """
 import os
 
@@ -221,6 +232,54 @@ def stream_smooth(ring, win, kt, ks, Bsum, bcnt, out, partial):
                'vv_stream_smooth')
 
 
+TRACK_STAGE = 256      # detections ``vv_stream_tracks`` stages in LDS per pass (VV_STREAM_TRACK_STAGE)
+MAX_TRACKS = 1024      # VV_STREAM_MAX_TRACKS: the largest table of ``vv_stream_tracks``
+TRACK_WINDOW = 32      # VV_STREAM_TRACK_WINDOW: the longest score history of a track
+
+
+def stream_tracks(t_meta, t_hist, next_id, scores, n, n_host, rects, boxes, h, w, reset, iou_pct, max_age, min_hits, box_track,
+                  box_track_score, frame_track_score, counts):
+    """``vv_stream_tracks``: the boxes of one issued frame linked to the tracks of the frames before (include/vecvad_hip.h states the
+    steps).  The state is the caller's, on the device, and is updated in place: t_meta int32 ``[max_tracks,8]`` rows ``(id, age, hits,
+    y0, y1, x0, x1, 0)``, t_hist float64 ``[max_tracks,window]``, next_id int32 ``[1]`` (started at 1).  scores, n, n_host, rects and
+    boxes as for ``stream_paint`` (rects is only read); ``h x w``: the mask the rectangles lie in; ``reset``: the first frame of a
+    video.  Written in place below ``n[0]``: box_track int32 ``[width,2]`` rows ``(id, hits)`` and box_track_score float64 ``[width]``
+    (the mean of the track's last ``min(hits, window)`` scores; ``-BIG`` for id 0); frame_track_score float64 ``[1]``, the largest of
+    them over tracks with ``hits >= min_hits``; counts int32 ``[3] = (live, dropped, next_id)``."""
+    _dev('t_meta', t_meta, torch.int32), _dev('t_hist', t_hist, torch.float64), _dev('scores', scores, torch.float64)
+    if t_meta.dim() != 2 or t_meta.shape[1] != 8 or t_hist.dim() != 2 or t_hist.shape[0] != t_meta.shape[0] or scores.dim() != 2:
+        raise ValueError('t_meta must be a [max_tracks,8], t_hist a [max_tracks,window] and scores a [rows,width] tensor')
+    rows, width = scores.shape
+    _dev('next_id', next_id, torch.int32, 1), _dev('n', n, torch.int32, 1), _dev('rects', rects, torch.int32, 4 * width)
+    _dev('box_track', box_track, torch.int32, 2 * width), _dev('box_track_score', box_track_score, torch.float64, width)
+    _dev('frame_track_score', frame_track_score, torch.float64, 1), _dev('counts', counts, torch.int32, 3)
+    if boxes is not None:
+        _dev('boxes', boxes, torch.int32, 4 * width)
+    _lib.check(_lib.lib().vv_stream_tracks(t_meta.data_ptr(), t_hist.data_ptr(), next_id.data_ptr(), t_meta.shape[0], scores.data_ptr(), rows,
+                                           width, n.data_ptr(), int(n_host), rects.data_ptr(),
+                                           boxes.data_ptr() if boxes is not None else None, int(h), int(w), int(bool(reset)), int(iou_pct),
+                                           int(max_age), t_hist.shape[1], int(min_hits), float(BIG), box_track.data_ptr(),
+                                           box_track_score.data_ptr(), frame_track_score.data_ptr(), counts.data_ptr(),
+                                           torch.cuda.current_stream(t_meta.device).cuda_stream), 'vv_stream_tracks')
+
+
+TRACK_KEYS = (('track_iou_percent', 30, 1, 100), ('track_max_age', 5, 0, 2 ** 31 - 2), ('track_window', 8, 1, TRACK_WINDOW),
+              ('track_min_hits', 3, 1, 2 ** 31 - 1), ('stream_max_tracks', 128, 1, MAX_TRACKS))      # key, default, smallest, largest
+
+
+def check_track_settings(c, tracks):
+    """The switch of the tracks of a stream and their settings, checked on the host whatever the switch says: ``(tracks, iou_percent,
+    max_age, window, min_hits, max_tracks)``.  ``tracks`` None reads ``stream_tracks``.  One-line ``ValueError`` for a setting that
+    is no integer of its range."""
+    out = [bool(c.get('stream_tracks', False) if tracks is None else tracks)]
+    for key, default, lo, hi in TRACK_KEYS:
+        v = c.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError('[mi355x] {} must be an integer in {}..{}, got {!r}'.format(key, lo, hi, v))
+        out.append(int(v))
+    return tuple(out)
+
+
 def check_pixel_settings(c, masks, smooth, render, frame_hw, grid_hw):
     """The switches of the pixel-level stages of a stream and what they need, checked on the host: ``(masks, smooth, render, kt, ks,
     source, boxes, lo, hi, alpha)``.  ``smooth`` and ``render`` imply the mask.  One-line ``ValueError``: windows outside 1..33 (an
@@ -267,7 +326,8 @@ class RingSchedule:
     ``motion``: the raw ring holds ``motion_ring_frames`` frames, never fewer than the three of the motion window; without it the
     motion slots mean something only where ``ring_frames`` is 3 or more already.  ``mask_frames`` = K, the slots of the score-mask ring
     (the trailing smoothing window in frames; 1 without smoothing): ``mask_slot`` = ``frame % K`` is where the issued frame's mask
-    goes, ``mask_frames`` / ``mask_slots`` the frames ``max(0, frame - K + 1) .. frame`` of the video and their slots, ascending."""
+    goes, ``mask_frames`` / ``mask_slots`` the frames ``max(0, frame - K + 1) .. frame`` of the video and their slots, ascending.
+    ``reset``: the issue is the first of its video (what a tracker frees its table for)."""
 
     def __init__(self, context_frame_num=4, context_of_num=0, motion=False, mask_frames=1):
         self.T, self.Tf, self.K = int(context_frame_num) + 1, int(context_of_num) + 1, int(mask_frames)
@@ -281,7 +341,7 @@ class RingSchedule:
         pair = (t - 1, t) if last else ((t, t) if t == 0 else (t, t + 1))     # calc_optical_flow.flow_pairs
         motion = (max(t - 1, 0), t, t if last else t + 1)                     # 'hard' at one frame of context: clipped to the video
         trail = list(range(max(0, t - self.K + 1), t + 1))                    # the trailing window of the mask smoothing
-        return dict(frame=t, mask_slot=t % self.K, mask_frames=trail, mask_slots=[f % self.K for f in trail], raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
+        return dict(frame=t, reset=t == 0, mask_slot=t % self.K, mask_frames=trail, mask_slots=[f % self.K for f in trail], raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
                     flow_slots=[f % self.Rf for f in flow], pair_frames=pair, pair_slots=(pair[0] % self.R, pair[1] % self.R),
                     flow_slot=t % self.Rf, motion_frames=motion, motion_slots=tuple(f % self.R for f in motion))
 
@@ -310,15 +370,36 @@ class StreamResult:
 
     With the scorer's pixel-level switches, also after ``wait()`` (None for a switch that is off): ``mask``, float64 ``[gh,gw]``, the
     frame's score mask as ``test.paint_frame`` paints it from ``box_scores`` and ``boxes`` (its maximum is the frame score);
-    ``smooth_mask`` and ``smooth_score``, its trailing-window mean and that mean's maximum; ``picture``, uint8 ``[H,W,3]`` RGB."""
+    ``smooth_mask`` and ``smooth_score``, its trailing-window mean and that mean's maximum; ``picture``, uint8 ``[H,W,3]`` RGB.
 
-    def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None, pixels=None):
+    With the scorer's ``tracks``, also after ``wait()`` (all None with the switch off): ``track_ids`` and ``track_hits``, int32 ``[n]``,
+    the identity of every box's track (0: the box is no detection -- it scored ``-BIG`` or paints no pixel -- or found no free slot)
+    and the frames that track was matched in; ``track_scores``, float64 ``[n]``, the mean of the track's last ``track_window`` scores
+    (``-BIG`` for id 0); ``track_score``, their maximum over tracks with ``track_min_hits`` matches or more (``-BIG`` without one);
+    ``tracks_dropped``, the detections that found no free slot; ``tracks``, int32 ``[L,7]``, the live slots of the table in slot
+    order as ``(id, age, hits, y0, y1, x0, x1)``."""
+
+    def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None, pixels=None, tracks=None):
         self.frame, self._n, self._rows, self._width = frame, n, rows, width
         self._host, self._host_keep, self._event = host, host_keep, event
         self._given, self._host_found = np.asarray(boxes, np.float64).reshape(-1, 4), host_found      # host_found: n, dropped, boxes_out
         self.boxes, self.dropped = (self._given, 0) if host_found is None else (None, None)
         self._pixels = pixels or {}          # name -> pooled pinned buffer, held until wait() has copied it out
         self.mask = self.smooth_mask = self.smooth_score = self.picture = None
+        self._tracks = tracks                # (pinned copy of the scorer's track buffer, max_tracks, width) | None
+        self.track_ids = self.track_hits = self.track_scores = self.track_score = self.tracks_dropped = self.tracks = None
+
+    def _copy_tracks(self, n):
+        """The track outputs out of the frame's copy of the track buffer (``StreamScorer._init_tracks`` has the layout)."""
+        host, mt, width = self._tracks
+        a, o = host.numpy(), 8 * mt
+        meta = a[:o].reshape(mt, 8)
+        self.tracks = meta[meta[:, 0] > 0][:, :7].copy()
+        self.tracks_dropped = int(a[o + 1])
+        self.track_score = float(a[o + 4:o + 6].view(np.float64)[0])
+        self.track_scores = a[o + 6:o + 6 + 2 * width].view(np.float64)[:n].copy()
+        pairs = a[o + 6 + 2 * width:o + 6 + 4 * width].reshape(width, 2)[:n]
+        self.track_ids, self.track_hits = pairs[:, 0].copy(), pairs[:, 1].copy()
 
     def _copy_out(self):
         """The pixel-level results out of their pooled pinned buffers, which go back to the pool."""
@@ -344,6 +425,8 @@ class StreamResult:
             self._n, self.dropped = int(f[0]), int(f[1])
             self.boxes = np.concatenate([self._given, f[2:].reshape(-1, 4)[len(self._given):self._n].astype(np.float64)])
         n = self._n
+        if self._tracks is not None:
+            self._copy_tracks(n)
         box = np.full(n, -float(BIG), np.float64)
         if self._rows and n:
             box = a[1:].reshape(self._rows, self._width)[:, :n].max(axis=0)
@@ -387,7 +470,7 @@ _HELD = _Held()
 
 class StreamScorer:
     """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None,
-    masks=None, smooth=None, render=None)``.
+    masks=None, smooth=None, render=None, tracks=None)``.
 
     ``c``: the dict of ``train.read_config``; ``net_set`` / ``stats_raw`` / ``stats_of``: what ``test.load_artifacts`` returns;
     ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3); ``flownet2``: the network (None loads
@@ -414,10 +497,19 @@ class StreamScorer:
     numbers; ``auto`` is refused --, ``render_alpha``, ``render_boxes``), formed behind the frame's last ``vv_stream_scores`` and
     delivered with the scores (``StreamResult.mask`` / ``.smooth_mask`` / ``.smooth_score`` / ``.picture``).  ``smooth`` and ``render``
     imply the mask; a picture needs frames of the dataset's nominal size.  Every refusal is a one-line ``ValueError`` before any GPU
-    work."""
+    work.
+
+    ``tracks`` (None reads ``[mi355x] stream_tracks``; off by default, and then nothing of it is allocated, launched or copied): one
+    more launch behind the frame's last ``vv_stream_scores``, ``vv_stream_tracks``, links the frame's boxes to the tracks of the
+    video's earlier frames by IoU (``track_iou_percent``; greedy, best pair first), in a table of ``stream_max_tracks`` slots that
+    lives on the device and is emptied at the first frame of a video.  A track that finds no box coasts for ``track_max_age`` frames;
+    its score is the mean of its last ``track_window`` box scores, and the frame's track score the largest over tracks seen
+    ``track_min_hits`` times or more (``StreamResult.track_ids`` / ``.track_hits`` / ``.track_scores`` / ``.track_score`` /
+    ``.tracks_dropped`` / ``.tracks``).  The box scores are those of the frame's score mask: a box that paints no pixel of the
+    nominal frame or scored ``-BIG`` has no track.  Needs no mask: with ``masks`` off nothing of the mask ring exists."""
 
     def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda',
-                 boxes=None, masks=None, smooth=None, render=None):
+                 boxes=None, masks=None, smooth=None, render=None, tracks=None):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
         self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
         from vad_datasets import frame_size
@@ -435,6 +527,8 @@ class StreamScorer:
         self.H, self.W, self.C = H, W, C
         (self.masks, self.smooth, self.render, self.kt, self.ks, self.render_source, self.render_boxes, self.render_lo, self.render_hi,
          self.render_alpha) = check_pixel_settings(c, masks, smooth, render, (H, W), frame_size[ds][:2])      # before any GPU work
+        self.tracks, self.trk_iou, self.trk_age, self.trk_window, self.trk_hits, self.trk_max = check_track_settings(c, tracks)
+        self.tail = self.masks or self.tracks          # the stages that read the descriptor's tail
         self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion,
                                   mask_frames=self.kt if self.smooth else 1)
         self.P = cp.getint(ds, 'patch_size')
@@ -500,8 +594,12 @@ class StreamScorer:
             self.mt_count = torch.zeros((1,), dtype=torch.int32, device=dev)
             self.mt_boxes = torch.zeros((cap, 4), dtype=torch.int32, device=dev)                          # mcap = cap
             self.found = torch.zeros((2 + 4 * cap,), dtype=torch.int32, device=dev)                       # n, dropped, boxes_out [cap][4]
+        if self.tail:
+            self._init_tail()
         if self.masks:
             self._init_pixels()
+        if self.tracks:
+            self._init_tracks()
         self.staging = _Staging()
         self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
@@ -512,18 +610,27 @@ class StreamScorer:
                     ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
         torch.cuda.synchronize(dev)
 
+    def _init_tail(self):
+        """Behind the descriptor, for the stages behind a frame's last ``vv_stream_scores`` (pixels, tracks): the tail ``n, 3 unused |
+        window [1 + K], padded to 4 words | rects [width][4]``."""
+        dev, K = self.device, self.sched.K
+        self.t_win = 4
+        self.t_rects = self.t_win + (1 + K + 3) // 4 * 4
+        if self.motion:                       # one round: the tail has its place behind the descriptor for good
+            self.t_base = (self.words_motion + 3) // 4 * 4
+            self.desc = torch.zeros(self.t_base + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+        else:                                 # room for one round and its tail from the start; more rounds grow it as before
+            self.desc = torch.zeros((4 + self.D + 3) // 4 * 4 + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+
     def _init_pixels(self):
         """The device state of the pixel-level stages, allocated once: the mask ring (``smooth_frames`` slots, 1 without smoothing),
-        the X/Y sums and counts of every slot, the smoothed mask and its partial maxima, the picture, the colour table, the table of
-        box maxima (it grows with the rounds of a frame) and, behind the descriptor, the tail ``n, 3 unused | window [1 + K], padded
-        to 4 words | rects [width][4]``."""
+        the X/Y sums and counts of every slot, the smoothed mask and its partial maxima, the picture, the colour table and the table of
+        box maxima (it grows with the rounds of a frame)."""
         from .render import colormap
         dev, gh, gw, K = self.device, self.grid_h, self.grid_w, self.sched.K
         self.mask_ring = torch.full((K, gh, gw), -float(BIG), dtype=torch.float64, device=dev)
         self.box_max = torch.zeros(self.cap, dtype=torch.float64, device=dev)
         self.frame_off = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.t_win = 4
-        self.t_rects = self.t_win + (1 + K + 3) // 4 * 4
         if self.smooth:
             self.Bsum = torch.zeros((K, gh, gw), dtype=torch.float64, device=dev)
             self.bcnt = torch.zeros((K, gh, gw), dtype=torch.int16, device=dev)
@@ -532,11 +639,31 @@ class StreamScorer:
         if self.render:
             self.picture = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=dev)
             self.lut = torch.from_numpy(colormap()).to(dev)
-        if self.motion:                       # one round: the tail has its place behind the descriptor for good
-            self.t_base = (self.words_motion + 3) // 4 * 4
-            self.desc = torch.zeros(self.t_base + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
-        else:                                 # room for one round and its tail from the start; more rounds grow it as before
-            self.desc = torch.zeros((4 + self.D + 3) // 4 * 4 + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+
+    def _init_tracks(self):
+        """The track table of the camera, on the device for good: the history, the id counter and ONE int32 buffer that holds what a
+        frame's read-back wants, so that it is one copy: ``t_meta [max_tracks][8] | counts [3], 1 unused | frame track score (float64)
+        | box track scores (float64) [width] | box (id, hits) [width][2]``.  It grows with the rounds of a frame."""
+        dev, mt = self.device, self.trk_max
+        self.t_hist = torch.zeros((mt, self.trk_window), dtype=torch.float64, device=dev)
+        self.next_id = torch.ones(1, dtype=torch.int32, device=dev)
+        self.trk = torch.zeros(8 * mt + 6 + 4 * self.cap, dtype=torch.int32, device=dev)
+
+    def _tracks(self, issue, tail, scores, n_dev, n_host, boxes_dev):
+        """``vv_stream_tracks`` behind a frame's last ``vv_stream_scores``, on the current stream; the arguments of ``_pixels``.
+        Returns the part of the track buffer the frame's read-back copies."""
+        width, o = scores.shape[1], 8 * self.trk_max
+        used = o + 6 + 4 * width
+        if self.trk.numel() < used:
+            grown = torch.zeros(used, dtype=torch.int32, device=self.device)
+            grown[:o].copy_(self.trk[:o])
+            self.trk = grown
+        t = self.trk
+        stream_tracks(t[:o].view(self.trk_max, 8), self.t_hist, self.next_id, scores, n_dev, n_host,
+                      tail[self.t_rects:self.t_rects + 4 * max(width, 1)], boxes_dev, self.grid_h, self.grid_w, issue['reset'], self.trk_iou,
+                      self.trk_age, self.trk_hits, t[o + 6 + 2 * width:used].view(width, 2), t[o + 6:o + 6 + 2 * width].view(torch.float64),
+                      t[o + 4:o + 6].view(torch.float64), t[o:o + 4])
+        return t[:used]
 
     def _fill_tail(self, d, issue, n, boxes):
         """The tail of the descriptor on the host: the total number of boxes, the trailing window and the host's rectangles."""
@@ -685,7 +812,7 @@ class StreamScorer:
         rounds = (n + cap - 1) // cap
         words = 4 + max(rounds, 1) * D
         t_base = (words + 3) // 4 * 4                                          # the tail of the pixel-level stages, 16-byte aligned
-        if self.masks:
+        if self.tail:
             words = t_base + self.t_rects + 4 * max(rounds * cap, 1)
         if self.desc.numel() < words:
             self.desc = torch.zeros(words, dtype=torch.int32, device=self.device)
@@ -702,7 +829,7 @@ class StreamScorer:
             lo, hi = r * cap, min(n, (r + 1) * cap)
             here = self._fill_round(d[o:o + D], issue, crops[lo:hi], blocks[lo:hi])
             used.append([i for i, cell in enumerate(rows) if cell in here])
-        if self.masks:
+        if self.tail:
             self._fill_tail(d[t_base:], issue, n, boxes)
         desc = self.desc
         desc[:words].copy_(st[0], non_blocking=True)
@@ -720,12 +847,16 @@ class StreamScorer:
                        rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
             for i in used[r]:
                 self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
-        pixels = None
-        if self.masks:
+        pixels, trk = None, []
+        if self.tail:
             tail = desc[t_base:words]
-            pixels = self._pixels(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)
-        (host, host_keep), event = self._read_back(out, keep)
-        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes, pixels=pixels)
+            if self.tracks:
+                trk = [self._tracks(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)]
+            if self.masks:
+                pixels = self._pixels(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)
+        (host, host_keep, *host_trk), event = self._read_back(out, keep, *trk)
+        return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes, pixels=pixels,
+                            tracks=(host_trk[0], self.trk_max, width) if host_trk else None)
 
     def _fill_round(self, d, issue, crops, blocks):
         """One round of the descriptor on the host: the number of boxes, their crops, the two windows and the mask rows.  Returns the set
@@ -758,7 +889,7 @@ class StreamScorer:
         self._fill_round(d[4:4 + D], issue, crops, blocks)
         d[self.w_mwin:self.w_mwin + 3] = issue['motion_slots']
         d[self.w_ap:self.w_ap + 5 * len(ap)] = ap.reshape(-1)
-        if self.masks:                        # the count is the device's (found[0]); the appearance boxes' rectangles are the host's
+        if self.tail:                         # the count is the device's (found[0]); the appearance boxes' rectangles are the host's
             self._fill_tail(d[self.t_base:], issue, k, boxes)
         desc = self.desc
         desc.copy_(st[0], non_blocking=True)
@@ -784,8 +915,11 @@ class StreamScorer:
         out = torch.full((1 + len(cells) * cap,), -float(BIG), dtype=torch.float64, device=self.device)
         for i, cell in enumerate(cells):
             self._score_block(cell, keep, n, masks, out[1 + i * cap:1 + (i + 1) * cap], out[0:1])
-        pixels = None
+        pixels, trk = None, []
+        if self.tracks:
+            trk = [self._tracks(issue, desc[self.t_base:], out[1:].view(len(cells), cap), n, k, found[2:])]
         if self.masks:
             pixels = self._pixels(issue, desc[self.t_base:], out[1:].view(len(cells), cap), n, k, found[2:])
-        (host, host_keep, host_found), event = self._read_back(out, keep, found)
-        return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found, pixels=pixels)
+        (host, host_keep, host_found, *host_trk), event = self._read_back(out, keep, found, *trk)
+        return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found, pixels=pixels,
+                            tracks=(host_trk[0], self.trk_max, cap) if host_trk else None)
