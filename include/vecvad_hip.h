@@ -76,7 +76,9 @@ typedef struct vv_view {
 #define VV_CONV_SRC_BF16 2
 /* with VV_CONV_BF16, VV_CONV3 / VV_CONVT_DGRAD: `out` is stored as bf16 (nearest even; same element indexing, gstride in
  * floats) and `stats` sums the stored values -- activation gradients in bf16, torch.autocast's dtype for them; read back by
- * vv_bn_bwd_* (VV_BNBWD_DA_BF16), by the transposed conv's data / weight gradient (VV_CONV_SRC_BF16 / VV_WGRAD_DY_BF16) */
+ * vv_bn_bwd_* (VV_BNBWD_DA_BF16), by the transposed conv's data / weight gradient (VV_CONV_SRC_BF16 / VV_WGRAD_DY_BF16).
+ * The tile is stored as 16-byte items of 8 channels: out.coff and out.cstride (and out1.coff) must be multiples of 8 elements and
+ * the tensor base 16-byte aligned, else VV_ERR_BAD_ARG.  (VV_CONVT_FWD with VV_CONV_ALLSRC_BF16 stores single elements: no such rule.) */
 #define VV_CONV_OUT_BF16 8
 /* with VV_CONV_BF16 (any kind; modes PLAIN / ACT / CAT): EVERY source tensor of the launch holds bf16 elements -- pre-BN conv
  * outputs written with VV_CONV_OUT_BF16 (then also allowed on forward and VV_CONVT_FWD launches: torch.autocast's output dtype),

@@ -575,6 +575,8 @@ extern "C" int vv_conv_mfma(const vv_conv_params* p, vv_stream stream) {
   if (bf && p->CinP % 16) return VV_ERR_BAD_ARG;
   if ((p->pad0 & VV_CONV_SRC_BF16) && !(bf && p->in_mode == VV_IN_PLAIN && p->kind != VV_CONVT_FWD && p->src0.coff % 2 == 0)) return VV_ERR_BAD_ARG;
   if ((p->pad0 & VV_CONV_OUT_BF16) && !bf) return VV_ERR_BAD_ARG;
+  // bf16 tiles of VV_CONV3 / VV_CONVT_DGRAD leave as 16-byte items of 8 channels (every bf16-output kernel): see the header
+  if ((p->pad0 & VV_CONV_OUT_BF16) && p->kind != VV_CONVT_FWD && (p->out.coff % 8 || p->out.cstride % 8)) return VV_ERR_BAD_ARG;
   if ((p->pad0 & VV_CONV_ALLSRC_BF16) && (!bf || p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE)) return VV_ERR_BAD_ARG;
   if (p->CinP % 8) return VV_ERR_BAD_ARG;
   if (p->kind == VV_CONVT_FWD && p->stats) return VV_ERR_UNSUPPORTED;   // the four-phase store keeps no column sums: refuse, do not store zeros
