@@ -96,6 +96,15 @@ typedef struct vv_view {
 /* A/B switch: vv_conv_wino runs the 32x32-level launches with at most 32 input channels on the persistent LDS-DMA ring kernel of
  * round 5 (bit-identical results); with this flag they stay on the per-tile kernel. */
 #define VV_CONV_NO_RING 128
+/* A/B switches of vv_conv_mfma's fp32 VV_CONVT_FWD / VV_CONVT_DGRAD launches on the 128-pixel tiles (forward: 8x8 / 4x4 input; data
+ * gradient: 16x16 / 8x8 / 4x4 output).  With Cout % 64 == 0 such a launch runs 64-wide N tiles (each staged input tile serves 64 output
+ * channels) when it still has a workgroup for every slot of the chip, else 32-wide ones; results, `stats` and bn_partial rows are
+ * bit-identical either way.  VV_CONV_CONVT_NARROW forces the 32-wide tiles, VV_CONV_CONVT_WIDE the 64-wide ones wherever they exist
+ * (Cout % 64 != 0, VV_IN_POOL / VV_IN_CUBE sources, other levels and the bf16 kernels ignore it); NARROW wins over WIDE.  Environment,
+ * read once, for launches without these bits: VV_CONVT_WIDE=0 keeps every launch 32-wide, VV_CONVT_WIDE=2 runs every launch that has a
+ * wide form 64-wide whatever its workgroup count. */
+#define VV_CONV_CONVT_NARROW 256
+#define VV_CONV_CONVT_WIDE 512
 typedef struct vv_conv_params {
   int32_t kind;      /* vv_conv_kind */
   int32_t in_mode;   /* vv_in_mode */

@@ -29,6 +29,8 @@ CONV_ALLSRC_BF16 = 16   # VV_CONV_ALLSRC_BF16
 CONV_RELU = 32          # VV_CONV_RELU: eval mode, BatchNorm folded into the filter, ReLU in the epilogue
 CONV_NO_GEMM16 = 64     # VV_CONV_NO_GEMM16: keep an all-bf16 3x3 launch on the round-3 kernel (A/B switch)
 CONV_NO_RING = 128      # VV_CONV_NO_RING: keep the 32x32-level Winograd launches on the per-tile kernel (A/B switch)
+CONV_CONVT_NARROW = 256  # VV_CONV_CONVT_NARROW: fp32 transposed-conv launches on 128-pixel tiles stay on 32-wide N tiles (A/B switch)
+CONV_CONVT_WIDE = 512    # VV_CONV_CONVT_WIDE: ... run 64-wide N tiles wherever that form exists (Cout % 64 == 0)
 BNBWD_Y_BF16 = 8
 BNBWD_PARTIALS_PER_TILE = 16   # partial sums left by the data-gradient launch (ConvParams.bn_partial)
 BNBWD_PARTIALS_PER_CTILE = 32  # ... of vv_conv_mfma (all-bf16 tensors): rows per vv_conv_ntiles

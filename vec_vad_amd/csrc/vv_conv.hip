@@ -14,11 +14,28 @@
 // forward (model/unet.py:54) and its data gradient; cuDNN calls in the reference.  By default the 3x3 / stride-1 layers run
 // through the Winograd kernel in vv_wino.hip (VV_WINOGRAD=0 brings them back here); the transposed convolution always
 // runs here -- forward with all four output-parity phases in one workgroup, data gradient as a stride-2 gather.
+//
+// fp32 transposed conv on the 128-pixel tiles, 32-wide (NR = 1) and 64-wide (NR = 2) N tiles; -Rpass-analysis=kernel-resource-usage,
+// <TH, TW, NI, NR>: registers / LDS bytes / waves per SIMD, no scratch in any of them (__launch_bounds__: 2 workgroups per CU for
+// the forward, 3 for the stride-2 gather, narrow and wide):
+//   forward  <8,8,2,1> 198 / 31392 / 2   <8,8,2,2> 254 / 49824 / 2   <4,4,8,1> 164 / 18816 / 3   <4,4,8,2> 226 / 28032 / 2
+//   gather   <8,16,1,1> 135 / 36144 / 3  <8,16,1,2> 118 / 45360 / 3  <8,8,2,1> 129 / 36960 / 3   <8,8,2,2> 118 / 46176 / 3
+//            <4,4,8,1> 143 / 40320 / 3   <4,4,8,2> 128 / 49536 / 3
+//   gather with bn_partial (S16 == 4)    <8,16,1,1> 163 / 36144 / 3  <8,16,1,2> 156 / 45360 / 3  <8,8,2,1> 153 / 36960 / 3
+//            <8,8,2,2> 158 / 46176 / 3   <4,4,8,1> 163 / 40320 / 3   <4,4,8,2> 160 / 49536 / 3
+//   (the wide gather measured at 2 workgroups per CU was SLOWER than the narrow one at 3: 200 / 170 / 155 us became 221 / 177 / 190 at
+//    B = 256; at 3, with the source mode a constant and z read through a buffer descriptor -- what it took to fit 168 registers
+//    without scratch -- 164 / 138 / 128.  profiles/README.md)
 #include "vv_common.h"
 // steps of distance between an LDS fragment read and its MFMAs in the bf16 kernels (measured on BASELINE config 4: 1 -> 41.1 k
 // cubes/s, 2 -> 40.5 k, 3 -> 38.6 k: the ring costs registers, and the kernels are bound by LDS bandwidth, not by its latency)
 #ifndef VV_PD_BF
 #define VV_PD_BF 1
+#endif
+
+// workgroups per CU (__launch_bounds__) of the 64-wide fp32 stride-2 gather on the 128-pixel tiles
+#ifndef VV_CONVT_WIDE_WGS
+#define VV_CONVT_WIDE_WGS 3
 #endif
 
 namespace {
@@ -38,7 +55,7 @@ struct Geo {
 // MR: 32-pixel row blocks per wave (2 = 256-pixel tiles; 1 = 128-pixel tiles, four workgroups per CU: the bf16 kernels on the 8x8 / 4x4
 // levels, where a launch has few, long workgroups and is bound by the chunk round trips)
 template <int TH, int TW, int NI, int NR, int KIND, int CK, bool BF, int S16, int MR>      // S16: 0 fp32 sources, 1 plain bf16 src0, 2 ALL sources bf16, 3 = 2 + bn_partial, 4 = fp32 stride-2 gather + bn_partial
-__global__ void __launch_bounds__(VV_WG, (MR == 1 && BF) ? 4 : ((BF && KIND == VV_CONVT_DGRAD) ? 1 : ((NR == 1 && KIND != VV_CONVT_FWD && !(BF && NI >= 4)) ? 3 : 2)))
+__global__ void __launch_bounds__(VV_WG, (MR == 1 && BF) ? 4 : ((BF && KIND == VV_CONVT_DGRAD) ? 1 : ((!BF && KIND == VV_CONVT_DGRAD && MR == 1 && NR == 2) ? VV_CONVT_WIDE_WGS : ((NR == 1 && KIND != VV_CONVT_FWD && !(BF && NI >= 4)) ? 3 : 2))))
 conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int total, const int nper) {
   using G_ = Geo<KIND, TH, TW>;
   constexpr int HH = G_::HH, HW = G_::HW, SP = G_::SP;
@@ -83,7 +100,15 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   const int oy0 = KIND == VV_CONV3 ? ty0 - 1 : (KIND == VV_CONVT_FWD ? ty0 : 2 * ty0 - 1);
   const int ox0 = KIND == VV_CONV3 ? tx0 - 1 : (KIND == VV_CONVT_FWD ? tx0 : 2 * tx0 - 1);
 
-  const VVSrc s = vv_make_src(p, g, SH, SW);
+  VVSrc s_ = vv_make_src(p, g, SH, SW);
+  // the 64-wide stride-2 gather is routed to with VV_IN_PLAIN sources only (convt_wide; what a data gradient reads): as a constant the
+  // mode takes the stager's other paths, their scale / shift registers and per-item addresses out of this form, which needs every
+  // register to stay at three workgroups per CU without scratch
+  if constexpr (!BF && KIND == VV_CONVT_DGRAD && NR == 2 && MR == 1) s_.mode = VV_IN_PLAIN;
+  const VVSrc s = s_;
+  // the 64-wide forward is routed to with PLAIN / ACT / CAT sources only (convt_wide): told so, the compiler stops holding the per-item
+  // 64-bit addresses of the stager's immediate path for pooled / gathered inputs, which spilled (36 bytes of scratch at 256 registers)
+  if constexpr (!BF && KIND == VV_CONVT_FWD && NR == 2) __builtin_assume(s.mode != VV_IN_POOL && s.mode != VV_IN_CUBE);
   const int Cout = p.Cout, CinP = p.CinP, KQ = CinP >> 3;
   const int co0 = nn * TN;
   const float* __restrict__ wg = p.w + (int64_t)g * p.w_gstride;
@@ -98,8 +123,9 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
 
   // transposed conv: one accumulator set per output parity phase (py, px) -- all 9 taps of a chunk run in ONE workgroup,
   // each tap feeding the phase it belongs to, so the staged tile + weight panel serve 9 taps like in the 3x3 conv
-  constexpr int NACC = KIND == VV_CONVT_FWD ? 4 : NR;
-  static_assert(KIND != VV_CONVT_FWD || NR == 1, "transposed conv forward: 32-wide N tiles");
+  // (phase ph, N block n) -> acc[m][ph * NR + n]; 64-wide N tiles (NR == 2) on the fp32 128-pixel tiles only: 128 accumulator registers
+  constexpr int NACC = KIND == VV_CONVT_FWD ? 4 * NR : NR;
+  static_assert(KIND != VV_CONVT_FWD || NR == 1 || (NR == 2 && MR == 1 && !BF), "transposed conv forward: 32-wide N tiles, 64-wide on the fp32 128-pixel tiles");
   v16f acc[MR][NACC];
 #pragma unroll
   for (int m = 0; m < MR; ++m)
@@ -120,18 +146,33 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   // Winograd data gradients (vv_wino.hip): lane = channel, the lane's 16 z values (its 16 output pixels) requested ahead of the K loop.
   // (The all-bf16 form of the same launch -- z as 16-byte items, sums in the LDS store loop like S16 == 3 -- was built and measured on
   // config 4: 138 / 113 / 98 us per launch became 264 / 189 / 146 for 116 us of reduce passes saved; not kept, profiles/README.md.)
-  constexpr bool BNT = !BF && KIND == VV_CONVT_DGRAD && NR == 1 && MR == 1 && S16 == 4;
-  static_assert(S16 != 4 || BNT, "S16 == 4: the fp32 stride-2 gather (128-pixel tiles, 32-wide N tiles) with BatchNorm-backward sums");
-  float zt[BNT ? 16 : 1];
-  if constexpr (BNT) {
-    const float* zb = p.bn_z + (int64_t)g * p.bn_z_gstride + co0 + l31;
+  // 64-wide N tiles (NR == 2): the 16 z values of each N block, 32 registers held through the K loop
+  constexpr bool BNT = !BF && KIND == VV_CONVT_DGRAD && NR <= 2 && MR == 1 && S16 == 4;
+  static_assert(S16 != 4 || BNT, "S16 == 4: the fp32 stride-2 gather (128-pixel tiles, 32- or 64-wide N tiles) with BatchNorm-backward sums");
+  float zt[BNT ? NR : 1][BNT ? 16 : 1];
+  auto request_z = [&](const int n) {
+    if constexpr (!BNT) return;
+    const float* zb = p.bn_z + (int64_t)g * p.bn_z_gstride + co0 + n * 32 + l31;
+    // NR == 2: buffer loads -- one 32-bit offset per pixel serves both N blocks (the second 128 bytes on) where 64-bit addresses per
+    // pixel and block, held by the compiler through the K loop, cost the third workgroup per CU; a pixel of an image past B gets an
+    // offset past the descriptor's range and reads 0 (vv_conv_mfma routes here only while a group's z stays below 2 GB)
+    const __amdgpu_buffer_rsrc_t rsZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bn_z + (int64_t)g * p.bn_z_gstride), 0, 0x7FFFFFFF, 0x00020000);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
       const int pp = wave * 32 + row;
       const int im = pp / (TH * TW), r = (pp / TW) % TH, c = pp % TW;
-      zt[i] = img0 + im < p.B ? zb[((int64_t)((img0 + im) * H + ty0 + r) * W + tx0 + c) * Cout] : 0.f;
+      if constexpr (NR > 1) {
+        const unsigned off = img0 + im < p.B ? (unsigned)((((img0 + im) * H + ty0 + r) * W + tx0 + c) * Cout + co0 + l31) * 4u : 0x80000000u;
+        zt[n][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsZ, off + (unsigned)n * 128u, 0, 0));
+      } else {
+        zt[n][i] = img0 + im < p.B ? zb[((int64_t)((img0 + im) * H + ty0 + r) * W + tx0 + c) * Cout] : 0.f;
+      }
     }
+  };
+  if constexpr (BNT) {
+#pragma unroll
+    for (int n = 0; n < NR; ++n) request_z(n);
   }
   constexpr int BN_QN = NR * 4, BN_NOUT = 128 * MR * BN_QN / VV_WG;
   const bool bnf = BNF && p.bn_partial != nullptr;
@@ -158,6 +199,10 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   // K groups per tap in the whole panel: fp32 panel [tap][CinP/8][2][Cout][4], bf16 panel [tap][CinP/16][2][Cout][8] -- in both
   // one (tap, group, half) row is Cout x 16 B and IS the LDS row, so the panel chunk is copied as it is
   const int KGT = BF ? (CinP >> 4) : KQ;
+  // 64-wide forward with 16-channel chunks: one pass of the workgroup's threads over the panel chunk is exactly one tap, so item k
+  // of a thread is its item 0 one tap further -- a scalar offset instead of 9 offset registers (this form sits at the 256-register
+  // limit of two workgroups per CU)
+  constexpr bool BLIN = !BF && KIND == VV_CONVT_FWD && NR == 2 && VV_WG == 2 * KGC * TN;
 #pragma unroll
   for (int k = 0; k < NBT; ++k) {
     const int it = tid + k * VV_WG;
@@ -174,7 +219,8 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
     const int so = (BF ? (c0 >> 4) : (c0 >> 3)) * 2 * Cout * 16;
 #pragma unroll
     for (int k = 0; k < NBT; ++k) {
-      const v4f v = __builtin_amdgcn_raw_buffer_load_b128(rsW, boff[k], so, 0);
+      const v4f v = BLIN ? __builtin_amdgcn_raw_buffer_load_b128(rsW, boff[0], so + k * KGT * 2 * Cout * 16, 0)
+                         : __builtin_amdgcn_raw_buffer_load_b128(rsW, boff[k], so, 0);
       rb[k] = make_float4(v.x, v.y, v.z, v.w);
     }
   };
@@ -236,7 +282,7 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
         for (int m = 0; m < MR; ++m)
 #pragma unroll
           for (int n = 0; n < NR; ++n) {
-            const int an = KIND == VV_CONVT_FWD ? phc : n;
+            const int an = KIND == VV_CONVT_FWD ? phc * NR + n : n;
             if constexpr (BF) {
               acc[m][an] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, fa[cur][m]),
                                                                    __builtin_bit_cast(v8bf, fb[cur][n]), acc[m][an], 0, 0, 0);
@@ -278,7 +324,9 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   // VV_CONV_RELU: clamp at 0, else at -inf = a no-op that leaves every value bit-identical (the flag test hoisted out of the
   // store loops: tested per element it cost the 64-wide bf16 data gradient at 32x32 85 us of 270)
   const float relu_lo = (p.pad0 & VV_CONV_RELU) ? 0.f : -__builtin_inff();
-  float bta = 0.f, btb = 0.f, bt1 = 0.f, bt2 = 0.f;      // BNT: scale / shift of the lane's channel, its two sums
+  float bta[NR], btb[NR], bt1[NR], bt2[NR];      // BNT: scale / shift of the lane's channel (per N block), its two sums
+#pragma unroll
+  for (int n = 0; n < NR; ++n) { bta[n] = 0.f; btb[n] = 0.f; bt1[n] = 0.f; bt2[n] = 0.f; }
   bool tile_out = false;
   if constexpr (BF && KIND != VV_CONVT_FWD) tile_out = o16;
   if (tile_out) {
@@ -381,7 +429,8 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   } else {
   if constexpr (BNT) {
     const int64_t o = (int64_t)g * p.bn_gstride + co0 + l31;
-    bta = p.bn_a[o]; btb = p.bn_b[o];
+#pragma unroll
+    for (int n = 0; n < NR; ++n) { bta[n] = p.bn_a[o + n * 32]; btb[n] = p.bn_b[o + n * 32]; }
   }
 #pragma unroll
   for (int m = 0; m < MR; ++m)
@@ -393,19 +442,24 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
       const int img = img0 + im;
       if constexpr (BNT) {
         // dz = dA [a z + b > 0]; sum dz and sum dz * z per channel (xhat's shift and scale once per workgroup, below)
-        const float d = (img < p.B && fmaf(bta, zt[i], btb) > 0.f) ? acc[m][0][i] + bias[0] : 0.f;
-        bt1 += d;
-        bt2 = fmaf(d, zt[i], bt2);
+#pragma unroll
+        for (int n = 0; n < NR; ++n) {
+          const float d = (img < p.B && fmaf(bta[n], zt[n][i], btb[n]) > 0.f) ? acc[m][n][i] + bias[n] : 0.f;
+          bt1[n] += d;
+          bt2[n] = fmaf(d, zt[n][i], bt2[n]);
+        }
       }
       if (img < p.B) {
         if constexpr (KIND == VV_CONVT_FWD) {
           const int64_t e = ((int64_t)(img * OH + 2 * (ty0 + r)) * OW + 2 * (tx0 + c)) * ocs + co0 + l31;
 #pragma unroll
-          for (int ph = 0; ph < 4; ++ph) {
-            const float v = acc[m][ph][i] + bias[0];
-            if (o16) outh[e + ((ph >> 1) * OW + (ph & 1)) * ocs] = (__bf16)v;
-            else outg[e + ((ph >> 1) * OW + (ph & 1)) * ocs] = v;
-          }
+          for (int n = 0; n < NR; ++n)
+#pragma unroll
+            for (int ph = 0; ph < 4; ++ph) {
+              const float v = acc[m][ph * NR + n][i] + bias[n];
+              if (o16) outh[e + ((ph >> 1) * OW + (ph & 1)) * ocs + n * 32] = (__bf16)v;
+              else outg[e + ((ph >> 1) * OW + (ph & 1)) * ocs + n * 32] = v;
+            }
         } else {
           const int64_t e = ((int64_t)(img * OH + ty0 + r) * OW + tx0 + c) * ocs + co0 + l31;
 #pragma unroll
@@ -429,14 +483,18 @@ conv_mfma_kernel(const vv_conv_params p, const int NT, const int NN, const int t
   if constexpr (BNT) {
     // the lane pair of a channel, then the four waves through LDS in wave order: one row [sum dz | sum dz xhat] per pixel tile
     // (vv_bn_bwd_apply reads it with VV_BNBWD_PARTIALS_PER_TTILE: rows = this launch's tiles)
-    bt1 += __shfl_xor(bt1, 32);
-    bt2 += __shfl_xor(bt2, 32);
+    // (LDS rows: [wave][sum dz | sum dz z][TN], channel tid of the workgroup's TN)
     __syncthreads();                      // every wave is done with the staging buffers
-    if (half == 0) { lds[wave * 64 + l31] = bt1; lds[wave * 64 + 32 + l31] = bt2; }
+#pragma unroll
+    for (int n = 0; n < NR; ++n) {
+      bt1[n] += __shfl_xor(bt1[n], 32);
+      bt2[n] += __shfl_xor(bt2[n], 32);
+      if (half == 0) { lds[wave * 2 * TN + n * 32 + l31] = bt1[n]; lds[wave * 2 * TN + TN + n * 32 + l31] = bt2[n]; }
+    }
     __syncthreads();
-    if (tid < 32) {
-      const float t1 = (lds[tid] + lds[64 + tid]) + (lds[128 + tid] + lds[192 + tid]);
-      const float t2 = (lds[32 + tid] + lds[96 + tid]) + (lds[160 + tid] + lds[224 + tid]);
+    if (tid < TN) {
+      const float t1 = (lds[tid] + lds[2 * TN + tid]) + (lds[4 * TN + tid] + lds[6 * TN + tid]);
+      const float t2 = (lds[TN + tid] + lds[3 * TN + tid]) + (lds[5 * TN + tid] + lds[7 * TN + tid]);
       const int64_t o = (int64_t)g * p.bn_gstride + co0 + tid;
       float* bp = p.bn_partial + ((int64_t)(g * NT + pt) * 2) * Cout + co0 + tid;
       bp[0] = t1;
@@ -492,6 +550,27 @@ int launch(const vv_conv_params* p, hipStream_t st) {
   return VV_OK;
 }
 
+// fp32 transposed conv (forward and stride-2 gather) on the 128-pixel tiles: 64-wide N tiles stage each halo tile once per 64 output
+// channels instead of once per 32 -- same tiles, same rows of stats / bn_partial, bit-identical results (every accumulator sees the
+// same chunk -> tap -> k-pair order).  Wide when Cout % 64 == 0 and the wide launch still has one workgroup for every slot of the
+// chip (CUs x workgroups per CU of the instantiation); in the environment, read once, VV_CONVT_WIDE=0 keeps
+// every launch 32-wide and VV_CONVT_WIDE=2 runs every launch that has a wide form 64-wide (A/B measurements).  The pad0 bits
+// VV_CONV_CONVT_NARROW / VV_CONV_CONVT_WIDE (tests) override both; Cout % 64 != 0, pooled / gathered sources and a stride-2 gather
+// whose source is not VV_IN_PLAIN are always narrow.
+inline bool convt_wide(const vv_conv_params* p, int nt, int wgs_per_cu) {
+  if ((p->Cout % 64) || (p->pad0 & VV_CONV_CONVT_NARROW) || p->in_mode == VV_IN_POOL || p->in_mode == VV_IN_CUBE) return false;
+  if (p->kind == VV_CONVT_DGRAD && p->in_mode != VV_IN_PLAIN) return false;      // the wide gather is built for plain sources only
+  if (p->pad0 & VV_CONV_CONVT_WIDE) return true;
+  static const int mode = [] { const char* e = getenv("VV_CONVT_WIDE"); return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }();
+  // the forward's wide forms hold 128 accumulator registers: two workgroups per CU like the narrow ones, so a launch of few rounds
+  // only trades them for half as many rounds of longer workgroups and a longer last one (B = 256: 8x8 level 768 workgroups on 512
+  // slots 137 -> 138 - 150 us, 4x4 level 384 workgroups 130 -> 157 us).  A full wide round measured ~0.75 of the two narrow rounds
+  // it replaces, a partial last round can cost a whole one: from four rounds on the wide form cannot lose (scoring batches of 2048
+  // cubes: 12 and 6 rounds, 1034 -> 971 us and 969 -> 914 us); the step's forward launches stay 32-wide.
+  const int64_t rounds = p->kind == VV_CONVT_FWD ? 4 : 1;
+  return mode == 2 || (mode == 1 && (int64_t)p->G * nt * (p->Cout / 64) >= rounds * vv_num_cus() * wgs_per_cu);
+}
+
 template <int KIND, int CK, bool BF, int S16 = 0>
 int dispatch(const vv_conv_params* p, hipStream_t st) {
   TileGeo t;
@@ -517,9 +596,13 @@ int dispatch(const vv_conv_params* p, hipStream_t st) {
     // B = 256 against the 256-pixel tiles -- forward 170 -> 131 us (4x4 level) and 155 -> 137 (8x8), 147 -> 158 at 16x16 (kept at 256
     // there); stride-2 gather 178 -> 146 / 191 -> 155 / 188 -> 176 on the three levels.  At the per-rank batches of the reference's
     // DataParallel split (train.py:375) they also double the workgroup count of launches that had a few dozen (B = 32: 99 -> 59 us).
-    if (p->H == 16 && KIND == VV_CONVT_DGRAD) return launch<8, 16, 1, 1, KIND, CKD, BF, S16, 1>(p, st);
-    if (p->H == 8) return launch<8, 8, 2, 1, KIND, CKD, BF, S16, 1>(p, st);
-    if (p->H == 4) return launch<4, 4, 8, 1, KIND, CK4, BF, S16, 1>(p, st);
+    // 64-wide N tiles on these tiles (convt_wide): one staged halo tile and one 64-column panel chunk feed two N blocks
+    const bool w128 = (p->H == 16 || p->H == 8 || p->H == 4) &&
+                      convt_wide(p, vv_convt_dgrad_ntiles(p->B, p->H, p->W, 0), KIND == VV_CONVT_FWD ? 2 : VV_CONVT_WIDE_WGS);
+    if constexpr (KIND == VV_CONVT_DGRAD)
+      if (p->H == 16) return w128 ? launch<8, 16, 1, 2, KIND, CKD, BF, S16, 1>(p, st) : launch<8, 16, 1, 1, KIND, CKD, BF, S16, 1>(p, st);
+    if (p->H == 8) return w128 ? launch<8, 8, 2, 2, KIND, CKD, BF, S16, 1>(p, st) : launch<8, 8, 2, 1, KIND, CKD, BF, S16, 1>(p, st);
+    if (p->H == 4) return w128 ? launch<4, 4, 8, 2, KIND, CK4, BF, S16, 1>(p, st) : launch<4, 4, 8, 1, KIND, CK4, BF, S16, 1>(p, st);
   }
   if constexpr (KIND == VV_CONVT_FWD) {        // four phase accumulators: 32-wide N tiles only
     switch (p->H) {
@@ -619,9 +702,11 @@ extern "C" int vv_conv_mfma(const vv_conv_params* p, vv_stream stream) {
     case VV_CONVT_DGRAD:
       if (bf && p->CinP % 16) return VV_ERR_BAD_ARG;
       if (!bf && p->bn_partial) {          // (validated above) the tiles of dispatch<VV_CONVT_DGRAD, 8, false>, with the sums
-        if (p->H == 16) return launch<8, 16, 1, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
-        if (p->H == 8) return launch<8, 8, 2, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
-        return launch<4, 4, 8, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
+        // (the wide form reads z through 32-bit byte offsets)
+        const bool w128 = convt_wide(p, vv_convt_dgrad_ntiles(p->B, p->H, p->W, 0), VV_CONVT_WIDE_WGS) && (int64_t)p->B * p->H * p->W * p->Cout * 4 < 0x7FFFFFFF;
+        if (p->H == 16) return w128 ? launch<8, 16, 1, 2, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st) : launch<8, 16, 1, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
+        if (p->H == 8) return w128 ? launch<8, 8, 2, 2, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st) : launch<8, 8, 2, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
+        return w128 ? launch<4, 4, 8, 2, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st) : launch<4, 4, 8, 1, VV_CONVT_DGRAD, 8, false, 4, 1>(p, st);
       }
       if (sm == 2) return dispatch<VV_CONVT_DGRAD, 8, true, 2>(p, st);
       if (sm == 1) return dispatch<VV_CONVT_DGRAD, 8, true, 1>(p, st);
