@@ -943,6 +943,8 @@ int vv_abi_sizeof(int32_t which);
  *                         NP % 32 == 0; zero padding).
  *  vv_conv3x3_n2_f16 / vv_deconv4x4_c2_f16 / vv_correlation_nhwc_f16 / vv_flownet_prep_f16 / vv_warp_pack12_f16 /
  *  vv_fusion_pack11_f16 : the fp32 entry points above on fp16 maps (images and flows of 8-half pixels, packed outputs of 16).
+ *                         vv_conv3x3_n2_f16 refuses a src_cstride that is no multiple of 8 halves (VV_ERR_BAD_ARG).  Pad channels
+ *                         [Cin, ceil8(Cin)) of a conv source must be finite (they meet zero weights), not zero.
  *  vv_out8_to_nchw_f16  : vv_out4_to_nchw from an 8-half pixel map to NCHW fp16 (dst_f16 = 1) or fp32 (dst_f16 = 0). */
 int vv_conv2d_f16(const vv_conv2d_params* p, vv_stream stream);
 int vv_pack_conv2d_f16(const float* w, uint16_t* packed, int32_t taps, int32_t K, int32_t KP, int32_t N, int32_t NP,

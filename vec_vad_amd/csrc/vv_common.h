@@ -187,7 +187,13 @@ __device__ __forceinline__ T vv_act_out(const float v, const float slope) {
     return v > 0.f ? v : v * slope;
   } else {
     const float r = (float)(vv_h)v;
-    return (vv_h)(r > 0.f ? r : r * slope);
+    // The product is an fp32 value (rounded to 24 bits) before it is rounded to fp16, as LeakyReLU on a half tensor computes it.
+    // Left to itself the compiler fuses the multiply and the conversion into v_fma_mixlo_f16(slope, r, +0): one rounding (off by
+    // an fp16 step where the fp32 product lands on an fp16 tie, e.g. -5 * 2^-24 * 0.1f) and +0 for r = -0.  The empty asm keeps
+    // the product in a register of its own.
+    float m = r * slope;
+    asm volatile("" : "+v"(m));
+    return (vv_h)(r > 0.f ? r : m);
   }
 }
 template <typename T>

@@ -794,7 +794,8 @@ namespace {
 template <typename T>
 int launch_n2(const T* src, int32_t src_cstride, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* wq, int32_t C4P,
               const float* bias, float slope, T* out, int32_t out_cstride, int32_t out_coff, hipStream_t st) {
-  if (!src || !wq || !out || src_cstride % 4 || C4P * 4 < ((Cin + 31) & ~31)) return VV_ERR_BAD_ARG;
+  // pixel strides are whole 16-byte groups in both types (4 floats / 8 halves), as the header states; vv_ld4<vv_h> itself loads 8 bytes
+  if (!src || !wq || !out || src_cstride % (sizeof(T) == 2 ? 8 : 4) || C4P * 4 < ((Cin + 31) & ~31)) return VV_ERR_BAD_ARG;
   // every form addresses the source through 64-bit pointers (vv_fetch4, vv_ld4 on src + (int64_t)pixel * cstride), so no byte limit
   // applies; the pixel index itself is formed in int, and the limit on elements is kept uniformly for all forms and both element types
   if ((int64_t)B * H * W * src_cstride >= (1ll << 31)) return VV_ERR_UNSUPPORTED;

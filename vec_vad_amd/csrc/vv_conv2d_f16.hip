@@ -66,7 +66,7 @@ conv2d_f16_kernel(const vv_conv2d_params p, const int tilesX, const int tilesY, 
 
   const vv_h* __restrict__ src = reinterpret_cast<const vv_h*>(p.src.ptr);
   const int cs = p.src.cstride, scoff = p.src.coff;
-  const int C8 = (p.Cin + 7) & ~7;                     // channels the source holds (pad channels up to ceil8 are zero)
+  const int C8 = (p.Cin + 7) & ~7;                     // channels read per pixel (pad channels up to ceil8 are finite; their panel rows are 0)
   const int CoutP = p.CoutP, KQ = p.CinP >> 3;
   const int co0 = nn * TN;
   const vv_h* __restrict__ wg = reinterpret_cast<const vv_h*>(p.w);
