@@ -613,6 +613,31 @@ int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32_t mcap, in
                     int32_t grid_h, int32_t grid_w, int32_t hb, int32_t wb, double h_step, double w_step, int32_t block_mode,
                     int32_t* n, int32_t* dropped, int32_t* crops, uint8_t* masks, int32_t* boxes_out, vv_stream stream);
 
+/* ---- several cameras in one scorer (vec_vad_amd/multistream.py): the two launches above over a camera dimension, ONE launch each for
+ * `cams` cameras.  All tables live in device memory; the values are those of the single-camera entry points called per camera (the
+ * same device functions).
+ * vv_stream_cut_multi: one workgroup per (camera, slot).
+ *   raw_ring  uint8 [cams*R][H][W][C], flow_ring float32 [cams*Rf][H][W][2]: camera k's frames and fields in slots k*R.. and k*Rf..
+ *   n         int32 [cams], each clamped to [0, cap]; crops int32 [cams][cap][4] (rows >= n[k] of camera k are not read)
+ *   raw_win   int32 [cams][T], flow_win int32 [cams][Tf]: ABSOLUTE ring slots, clamped into the whole rings
+ *   Box b < n[k] of camera k goes to store slot k*cap + b: raw_store uint8 [cams*cap][T][P][P][C], flow_store float32
+ *   [cams*cap][Tf][P][P][2], keep uint8 [cams*cap], energy double [cams*cap] or NULL.  Every other slot keeps what it holds.  A crop
+ *   outside the frame is dropped: keep 0, nothing read.  VV_ERR_BAD_ARG as vv_stream_cut, and for cams <= 0, cams > 65535 or
+ *   cams * R, cams * Rf, cams * cap > INT32_MAX.
+ * vv_stream_scores_multi: one workgroup per camera; one block's share of `cams` frame scores.
+ *   raw / of float32 [cams*cap], stats double [4] or NULL, keep and mask uint8 [cams*cap], n int32 [cams].  Box b of camera k counts
+ *   iff b < n[k], keep[k*cap+b] and mask[k*cap+b]; then box_scores[k*box_stride + b] = the score of vv_stream_scores (+big without
+ *   stats) and frame_score[k*frame_stride] is max-accumulated; a box below n[k] that does not count gets -big and its errors are not
+ *   read; slots >= n[k] are neither read nor written, and a camera with n[k] = 0 leaves its cell as it was.  Strides in elements,
+ *   box_stride >= cap and frame_stride >= 1 (the cameras' rows and cells must not overlap), cams >= 1, else VV_ERR_BAD_ARG. */
+int vv_stream_cut_multi(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
+                        int32_t cams, const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win,
+                        int32_t cap, int32_t T, int32_t Tf, int32_t P, double thr, uint8_t* raw_store, float* flow_store,
+                        uint8_t* keep, double* energy, vv_stream stream);
+int vv_stream_scores_multi(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
+                           const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cams, int32_t cap, double* box_scores,
+                           int64_t box_stride, double* frame_score, int64_t frame_stride, vv_stream stream);
+
 /* ---- a streamed frame's score mask, its trailing-window mean and the tables its picture needs (StreamScorer with masks / smooth /
  * render): what test.py's paint, smooth and render stages compute for a finished split, for ONE issued frame, with the box count and
  * the motion boxes still on the device.  VV_STREAM_UNPAINTED (-100000.0, = VV_SMOOTH_UNPAINTED = VV_RENDER_UNPAINTED) is the background.

@@ -24,6 +24,16 @@ taken one push after it was issued instead of at the end, so that its pinned buf
 ``[mi355x] stream_tracks`` also writes ``results/<ds>/stream_scores_track_<fg>_<method>.npy`` -- per frame the largest mean score of a
 track seen ``track_min_hits`` times or more (``StreamResult.track_score``) -- and, with frame labels, its ROC
 ``..._stream_track_results.npz`` and AUROC line; every other file is the one written without the key.
+
+``[mi355x] stream_cameras = N`` (default 1: exactly the run above).  With N > 1 the videos of the split (of each scene for
+ShanghaiTech, the scenes one after the other, one ``vec_vad_amd.multistream.MultiStreamScorer`` of N cameras each) are dealt to the
+cameras in split order, video ``v`` to camera ``v mod N``, and every camera plays its videos in order.  The cameras run in lockstep
+(``camera_ticks``): a tick pushes the next frame of every camera that still has one, in one ``push``; the cameras whose video ended
+with that frame are then ended together in one ``end_video([...])`` and start their next video at the next tick; a camera that has
+run out of videos passes ``None``.  The schedule depends on the split alone.  The files are those above (``stream_scores_*.npy`` and
+``*_stream_results.npz``); a score differs from the run at N = 1 only through the launch sizes.  ``stream_boxes = motion`` and the
+``stream_masks`` / ``stream_smooth`` / ``stream_render`` / ``stream_tracks`` switches are single-camera features: with N > 1 each is
+refused with a one-line ``ValueError`` before any GPU work.
 """
 import os
 import sys
@@ -80,8 +90,86 @@ def _detector_boxes(c, n):
     return [np.asarray(b)[:, :4] if np.asarray(b).ndim == 2 else np.zeros((0, 4), np.float32) for b in ap_all]
 
 
+def camera_ticks(videos, cameras):
+    """The schedule of ``[mi355x] stream_cameras = N``, pure: ``videos`` (a list of lists of frame indices, in split order) dealt to
+    ``cameras`` cameras, video ``v`` to camera ``v % cameras``, each camera playing its videos in order.  Yields the calls of the run in
+    order: ``('push', frames)`` with one frame index or None per camera, then, when the frame just pushed was the last of its video for
+    some cameras, ``('end', [those cameras])``; a camera that was ended starts its next video with the next push."""
+    queues = [videos[k::cameras] for k in range(cameras)]
+    vid, pos = [0] * cameras, [0] * cameras
+    while True:
+        frames = [queues[k][vid[k]][pos[k]] if vid[k] < len(queues[k]) else None for k in range(cameras)]
+        if all(f is None for f in frames):
+            return
+        yield 'push', frames
+        ends = []
+        for k in range(cameras):
+            if frames[k] is not None:
+                pos[k] += 1
+                if pos[k] == len(queues[k][vid[k]]):
+                    ends.append(k)
+                    vid[k], pos[k] = vid[k] + 1, 0
+        if ends:
+            yield 'end', ends
+
+
+def _main_cameras(c, flownet2):
+    """``main`` with ``[mi355x] stream_cameras = N > 1``: per scene one ``MultiStreamScorer`` of N cameras, driven by ``camera_ticks``."""
+    from vec_vad_amd.multistream import MultiStreamScorer, check_single_camera_keys
+    check_single_camera_keys(c)                       # motion boxes, masks, smoothing, overlays, tracks: refused before any GPU work
+    import foreground as FG
+    from test import BIG, load_artifacts
+    from vad_datasets import get_inputs
+    ds, cameras = c['dataset_name'], c['stream_cameras']
+    shanghai = ds == 'ShanghaiTech'
+    device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
+    torch.cuda.set_device(device)
+    base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
+    st = FG._stage(c, 'test', direct_flow=True)
+    scene_idx, labels = FG._write_frame_index(st, ds, 'test')
+    indexer, n = st.raw_ds, len(st.raw_ds)
+    net_set, st_r, st_o = load_artifacts(base, c['mode_fg'], c['method'], shanghai, lambda: build_network(c), device, c['h_block'],
+                                         c['w_block'])
+    if flownet2 is None:
+        from calc_optical_flow import load_flownet2
+        flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
+    scores = np.full(n, -float(BIG), np.float64)
+    scenes = {}                                       # scene -> its videos (lists of test frames), both in split order
+    for i in range(n):
+        if i == 0 or indexer.frame_video_idx[i] != indexer.frame_video_idx[i - 1]:
+            video = []
+            scenes.setdefault(int(scene_idx[i]) - 1 if shanghai else None, []).append(video)
+        video.append(i)
+    for key, videos in scenes.items():
+        scorer, pushed, results = None, [[] for _ in range(cameras)], []
+        for kind, arg in camera_ticks(videos, cameras):
+            if kind == 'end':
+                results += scorer.end_video(arg)
+                continue
+            frames = [get_inputs(indexer.all_frame_addr[i]) if i is not None else None for i in arg]
+            if scorer is None:
+                shape = next(f.shape for f in frames if f is not None)
+                scorer = MultiStreamScorer(c, net_set, st_r, st_o, shape, cameras, flownet2=flownet2, scene=key, device=device)
+            for k, i in enumerate(arg):
+                if i is not None:
+                    pushed[k].append(i)
+            results += scorer.push(frames, [st.boxes[i] if i is not None else None for i in arg])
+        for r in results:
+            scores[pushed[r.camera][r.frame]] = r.wait()[0]
+    os.makedirs(os.path.join('results', ds), exist_ok=True)
+    np.save(scores_path(c), scores)
+    if labels is None:
+        print('no frame labels for {} -> frame-level evaluation of the stream skipped'.format(ds))
+        return scores
+    print('Evaluating the stream of {} by frame-criterion:'.format(ds))
+    _evaluate(c, scores, labels, scene_idx, shanghai)
+    return scores
+
+
 def main(config_path='config.cfg', flownet2=None):
     c = read_config(config_path)                      # a bad [mi355x] stream_max_boxes / stream_boxes raises here, before any GPU work
+    if c['stream_cameras'] > 1:
+        return _main_cameras(c, flownet2)
     if c['stream_boxes'] == 'motion' and c['mode_fg'] != 'obj_det_with_motion':
         # the boxes would be obj_det_with_motion's while the models and statistics are loaded by mode_fg
         raise ValueError("[mi355x] stream_boxes = motion scores the boxes of mode obj_det_with_motion; the configured mode is "

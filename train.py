@@ -135,6 +135,7 @@ def read_config(path='config.cfg'):
              render_flow_max=cp.getfloat('mi355x', 'render_flow_max', fallback=0.0),
              stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip(),
              stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower(),
+             stream_cameras=cp.get('mi355x', 'stream_cameras', fallback='1').strip(),
              stream_masks=cp.getboolean('mi355x', 'stream_masks', fallback=False),
              stream_smooth=cp.getboolean('mi355x', 'stream_smooth', fallback=False),
              stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False),
@@ -191,6 +192,8 @@ def read_config(path='config.cfg'):
     from vec_vad_amd.stream import check_stream_boxes, check_track_settings
     c['stream_boxes'] = check_stream_boxes(c['stream_boxes'])
     check_track_settings(c, None)                      # the settings of a stream's tracks, checked whatever the switch says
+    from vec_vad_amd.multistream import check_cameras
+    c['stream_cameras'] = check_cameras(c['stream_cameras'])      # cameras per scorer of stream.py, checked whatever route runs
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT

@@ -63,9 +63,11 @@ It needs the descriptor's tail (the count and the host's rectangles) but no mask
 one copy behind the same event (``StreamResult.track_ids`` / ``.track_hits`` / ``.track_scores`` / ``.track_score`` /
 ``.tracks_dropped`` / ``.tracks``).  The defaults of its keys are untuned picks; no accuracy is claimed for them.
 
-What is not here: the mmdet detector (detector boxes are the caller's), decoding, several cameras per scorer, a centred (delayed)
-smoothing window, per-pixel error maps, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment
-by the Hungarian method, re-identification and ids drawn into the picture.
+What is not here: the mmdet detector (detector boxes are the caller's), decoding, a centred (delayed) smoothing window, per-pixel
+error maps, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment by the Hungarian method,
+re-identification and ids drawn into the picture.  Several cameras in one scorer are ``vec_vad_amd.multistream.MultiStreamScorer``
+(one frame shape and one model set, given boxes, scores only): the motion boxes, masks, smoothing, overlays and tracks described
+above stay features of this single-camera class.
 """
 import os
 
