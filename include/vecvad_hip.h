@@ -676,6 +676,30 @@ int64_t vv_stream_smooth_partials(int32_t h, int32_t w);
 int vv_stream_smooth(const double* ring, int32_t K, int32_t h, int32_t w, const int32_t* win, int32_t kt, int32_t ks, double* Bsum,
                      uint16_t* bcnt, double* out, double* partial, vv_stream stream);
 
+/* ---- a streamed frame's per-pixel error mask (StreamScorer with maps): where inside its boxes a frame is anomalous.  What
+ * vv_error_zmaps followed by vv_paint_zmaps compute on the batch route, fused, for boxes whose number lives on the device.
+ * vv_stream_zpaint: ONE block's share of ONE round of one frame, enqueued behind that block's vv_stream_scores over the same tables.
+ *   e_raw / e_of float32 [cap][32][32] = the per-pixel errors of the round's scoring launch (vv_error_maps; e_of == NULL drops the flow
+ *   term; both may be NULL with stats NULL); stats double [4] or NULL, w_raw, w_of, big as for vv_stream_scores; keep and mask uint8
+ *   [cap] = the round's keep flags and the block's mask row; n int32 [1] on the device, clamped to [0, cap].  Slot b counts iff b < n,
+ *   keep[b] and mask[b] (the rule of vv_stream_scores).  Its rectangle is row slot0 + b of the FRAME's table (slot0 = round * cap):
+ *   rects int32 [..][4] = (y0, y1, x0, x1) for rows below n_host -- resolved by the host as for vv_paint_masks, inside the h x w mask --
+ *   and else Python's slicing of boxes int32 [..][4] = (x1, y1, x2, y2) exactly as vv_stream_paint resolves it; boxes == NULL: every
+ *   rectangle is the host's.  rects is only read.  Pixel (y, x) inside the rectangle of a counted slot b is max-combined with
+ *     z = the score of vv_cube_scores' expression (the same device function) on 1024 * e_raw[b][q] (and 1024 * e_of[b][q]),
+ *     q = py * 32 + px, py = ((2 (y - y0) + 1) * 32) / (2 (y1 - y0)), px likewise (the source pixel of vv_paint_zmaps),
+ *   or with +big when stats is NULL -- the value vv_error_zmaps + vv_paint_zmaps give that pixel, bit for bit.
+ *   first != 0: out double [h][w] is written whole, -big where no counted rectangle reaches (no fill launch, out is not read);
+ *   first == 0: the launch max-accumulates into what out holds, so a frame is the maximum over its rounds and blocks in any order.
+ *   cap = 0 or n = 0 with first set leaves a mask of -big.  The errors of a slot that does not count are never read: NaN or Inf in the
+ *   padded slots of the scoring launch, in dropped boxes and in boxes of other blocks cannot reach the mask.  An empty rectangle paints
+ *   nothing.  Tables are staged through LDS VV_STREAM_PAINT_STAGE slots at a time; a thread owns two consecutive pixels (one 16-byte
+ *   store where aligned); no atomics.  VV_ERR_BAD_ARG without a launch: NULL out / n / rects, NULL keep / mask with cap > 0, e_raw
+ *   NULL with stats, cap < 0, slot0 < 0, n_host < 0, h <= 0 or w <= 0, h * w > (2^31 - 1) / 64 - 512. */
+int vv_stream_zpaint(const float* e_raw, const float* e_of, const double* stats, double w_raw, double w_of, double big,
+                     const uint8_t* keep, const uint8_t* mask, const int32_t* n, int32_t cap, int32_t slot0, const int32_t* rects,
+                     int32_t n_host, const int32_t* boxes, int32_t h, int32_t w, double* out, int32_t first, vv_stream stream);
+
 /* ---- a streamed frame's boxes linked into tracks (StreamScorer with tracks): one launch behind the frame's last vv_stream_scores,
  * over the tables vv_stream_paint reads.  All geometry is in integers and every sum is taken in one stated order, so the result is
  * exact.  The state belongs to the caller (one camera): t_meta int32 [max_tracks][8] = (id, age, hits, y0, y1, x0, x1, 0), t_hist

@@ -25,6 +25,11 @@ taken one push after it was issued instead of at the end, so that its pinned buf
 track seen ``track_min_hits`` times or more (``StreamResult.track_score``) -- and, with frame labels, its ROC
 ``..._stream_track_results.npz`` and AUROC line; every other file is the one written without the key.
 
+``[mi355x] stream_maps`` also writes ``results/<ds>/stream_scores_fine_<fg>_<method>.npy`` -- per frame the maximum of the frame's
+per-pixel error mask (``StreamResult.fine_score``) -- and, with frame labels, its ROC ``..._stream_fine_results.npz`` and AUROC line;
+every other file is the one written without the key, and no mask file is written.  Like the masks above it makes a frame's result
+be taken one push after it was issued.
+
 ``[mi355x] stream_cameras = N`` (default 1: exactly the run above).  With N > 1 the videos of the split (of each scene for
 ShanghaiTech, the scenes one after the other, one ``vec_vad_amd.multistream.MultiStreamScorer`` of N cameras each) are dealt to the
 cameras in split order, video ``v`` to camera ``v mod N``, and every camera plays its videos in order.  The cameras run in lockstep
@@ -32,7 +37,7 @@ cameras in split order, video ``v`` to camera ``v mod N``, and every camera play
 with that frame are then ended together in one ``end_video([...])`` and start their next video at the next tick; a camera that has
 run out of videos passes ``None``.  The schedule depends on the split alone.  The files are those above (``stream_scores_*.npy`` and
 ``*_stream_results.npz``); a score differs from the run at N = 1 only through the launch sizes.  ``stream_boxes = motion`` and the
-``stream_masks`` / ``stream_smooth`` / ``stream_render`` / ``stream_tracks`` switches are single-camera features: with N > 1 each is
+``stream_masks`` / ``stream_smooth`` / ``stream_render`` / ``stream_tracks`` / ``stream_maps`` switches are single-camera features: with N > 1 each is
 refused with a one-line ``ValueError`` before any GPU work.
 """
 import os
@@ -49,31 +54,31 @@ from train import read_config, build_network  # noqa: E402
 from utils import save_roc_pr_curve_data  # noqa: E402
 
 
-def results_path(c, scene=None, smooth=False, track=False):
+def results_path(c, scene=None, smooth=False, track=False, fine=False):
     return os.path.join('results', c['dataset_name'], '{}_{}_{}_stream{}_results{}.npz'.format(
-        c['modality'], c['mode_fg'], c['method'], '_smooth' if smooth else ('_track' if track else ''),
+        c['modality'], c['mode_fg'], c['method'], '_smooth' if smooth else ('_track' if track else ('_fine' if fine else '')),
         '' if scene is None else '_scene_{}'.format(scene)))
 
 
-def scores_path(c, smooth=False, track=False):
+def scores_path(c, smooth=False, track=False, fine=False):
     return os.path.join('results', c['dataset_name'], 'stream_scores{}_{}_{}.npy'.format(
-        '_smooth' if smooth else ('_track' if track else ''), c['mode_fg'], c['method']))
+        '_smooth' if smooth else ('_track' if track else ('_fine' if fine else '')), c['mode_fg'], c['method']))
 
 
 def render_dir(c):
     return os.path.join('results', c['dataset_name'], 'stream_render')
 
 
-def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False, track=False):
+def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False, track=False, fine=False):
     """The frame-level ROC of a score vector of the stream, written and printed as ``test.py`` does for its own."""
-    what = 'smoothed stream' if smooth else ("stream's tracks" if track else 'stream')
+    what = 'smoothed stream' if smooth else ("stream's tracks" if track else ("stream's error maps" if fine else 'stream'))
     if shanghai:
-        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si], results_path(c, si, smooth, track))
-                             for si in sorted(set(scene_idx))]))
+        auc = float(np.mean([save_roc_pr_curve_data(scores[scene_idx == si], labels[scene_idx == si],
+                                                    results_path(c, si, smooth, track, fine)) for si in sorted(set(scene_idx))]))
         print('Average frame-level AUC of the {} is {}'.format(what, auc))
     else:
-        print('Results written to {}:'.format(results_path(c, smooth=smooth, track=track)))
-        auc = save_roc_pr_curve_data(scores, labels, results_path(c, smooth=smooth, track=track))
+        print('Results written to {}:'.format(results_path(c, smooth=smooth, track=track, fine=fine)))
+        auc = save_roc_pr_curve_data(scores, labels, results_path(c, smooth=smooth, track=track, fine=fine))
         print('Frame-level AUC of the {} is {}'.format(what, auc))
 
 
@@ -115,8 +120,9 @@ def camera_ticks(videos, cameras):
 
 def _main_cameras(c, flownet2):
     """``main`` with ``[mi355x] stream_cameras = N > 1``: per scene one ``MultiStreamScorer`` of N cameras, driven by ``camera_ticks``."""
-    from vec_vad_amd.multistream import MultiStreamScorer, check_single_camera_keys
+    from vec_vad_amd.multistream import MultiStreamScorer, check_single_camera_keys, check_stream_maps
     check_single_camera_keys(c)                       # motion boxes, masks, smoothing, overlays, tracks: refused before any GPU work
+    check_stream_maps(c)                              # ... and the per-pixel error maps
     import foreground as FG
     from test import BIG, load_artifacts
     from vad_datasets import get_inputs
@@ -203,9 +209,10 @@ def main(config_path='config.cfg', flownet2=None):
         from calc_optical_flow import load_flownet2
         flownet2 = load_flownet2(c['flownet2_checkpoint'], device=device, fp16=c['direct_flow_fp16'])
     scores = np.full(n, -float(BIG), np.float64)
-    pixels = c['stream_masks'] or c['stream_smooth'] or c['stream_render']
+    pixels = c['stream_masks'] or c['stream_smooth'] or c['stream_render'] or c['stream_maps']
     smooth_scores = np.full(n, -float(BIG), np.float64) if c['stream_smooth'] else None
     track_scores = np.full(n, -float(BIG), np.float64) if c['stream_tracks'] else None
+    fine_scores = np.full(n, -float(BIG), np.float64) if c['stream_maps'] else None
     if c['stream_render']:
         from PIL import Image
         os.makedirs(render_dir(c), exist_ok=True)
@@ -223,6 +230,8 @@ def main(config_path='config.cfg', flownet2=None):
                 smooth_scores[f] = r.smooth_score
             if track_scores is not None:
                 track_scores[f] = r.track_score
+            if fine_scores is not None:
+                fine_scores[f] = r.fine_score
             if r.picture is not None:
                 Image.fromarray(r.picture).save(os.path.join(render_dir(c), '{}.png'.format(f)))
         del results[:upto]
@@ -253,6 +262,8 @@ def main(config_path='config.cfg', flownet2=None):
         np.save(scores_path(c, smooth=True), smooth_scores)
     if track_scores is not None:
         np.save(scores_path(c, track=True), track_scores)
+    if fine_scores is not None:
+        np.save(scores_path(c, fine=True), fine_scores)
     if labels is None:
         print('no frame labels for {} -> frame-level evaluation of the stream skipped'.format(ds))
         return scores
@@ -262,6 +273,8 @@ def main(config_path='config.cfg', flownet2=None):
         _evaluate(c, smooth_scores, labels, scene_idx, shanghai, smooth=True)
     if track_scores is not None:
         _evaluate(c, track_scores, labels, scene_idx, shanghai, track=True)
+    if fine_scores is not None:
+        _evaluate(c, fine_scores, labels, scene_idx, shanghai, fine=True)
     return scores
 
 

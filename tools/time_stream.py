@@ -32,12 +32,19 @@ With ``--tracks`` a further leg alternates with the others: the same stream thro
 timed like the pixel launches: ``--boxes`` rectangles that every launch finds where the launch before left them, so a launch is one
 matching round in a table of ``stream_max_tracks`` slots.
 
+With ``--maps`` a further leg alternates with the others: the same stream through ``StreamScorer(maps=True)``, reported as
+``stream_maps`` next to ``stream`` (the error mask of every frame is copied out in ``wait()``, inside the timed span).
+``maps_launches_us`` is the device time of what the switch adds per scored block and round, timed like the pixel launches: the scoring
+launch without and with the stored reconstructions and the error maps, ``vv_stream_zpaint`` over ``--boxes`` rectangles, and the copy
+of the mask to pinned memory.  ``--no-batch`` leaves the batch leg out (the stream legs do not depend on it).
+
 Prints one JSON line; needs the GPU.
 
     timeout 900 python tools/time_stream.py --frames 200 [--boxes 12] [--reps 2] [--no-flow-branch] [--out stream.json]
     timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --stream-boxes motion [--out stream_motion.json]
     timeout 900 python tools/time_stream.py --frames 200 --masks --smooth --render [--out stream_masks.json]
     timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --tracks [--out stream_tracks.json]
+    timeout 900 python tools/time_stream.py --frames 200 --boxes 12 --maps --no-batch [--out stream_maps.json]
 """
 import argparse
 import contextlib
@@ -139,9 +146,49 @@ def track_launch_us(sc, n_boxes, batch=50):
     return dict(vv_stream_tracks=1e3 * a.elapsed_time(b) / batch, live=int(counts[0]), next_id=int(counts[2]))
 
 
-def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tracks=False):
+def maps_launches_us(sc, n_boxes, batch=50):
+    """Device time of what ``maps`` adds to one scored block of one round of ``sc``, in microseconds, each timed with events around
+    ``batch`` back-to-back calls on the scorer's own store and buffers: the scoring launch without and with the stored reconstructions
+    and the error maps (``score_cubes`` / ``score_cubes_maps``: a graph replay plus the launches behind it), ``vv_stream_zpaint`` over
+    ``n_boxes`` rectangles of 36x30 pixels, and the copy of the error mask to pinned memory (once per frame)."""
+    import torch
+    from vec_vad_amd.stream import stream_zpaint
+    dev, gh, gw, cap = sc.device, sc.grid_h, sc.grid_w, sc.cap
+    rng = np.random.default_rng(1)
+    nb = min(n_boxes, cap)
+    y0, x0 = rng.integers(0, gh - 40, cap), rng.integers(0, gw - 40, cap)
+    rects = torch.from_numpy(np.stack([y0, y0 + 36, x0, x0 + 30], axis=1).astype(np.int32)).to(dev)
+    n = torch.tensor([nb], dtype=torch.int32, device=dev)
+    ones = torch.ones(cap, dtype=torch.uint8, device=dev)
+    tr, stats = next(ent for ent in sc.blocks.values() if ent is not None)
+    _, _, e_raw, e_of = tr.score_cubes(sc.store_raw, sc.store_flow, sc.idx, maps=True)
+    e_of = e_of if sc.use_flow else None
+    host = torch.empty(sc.zmask.shape, dtype=sc.zmask.dtype, pin_memory=True)
+    out = {}
+
+    def timed(name, launch):
+        for _ in range(3):                               # a graph not yet captured is captured here, outside the events
+            launch()
+        torch.cuda.synchronize(dev)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(batch):
+            launch()
+        b.record()
+        b.synchronize()
+        out[name] = 1e3 * a.elapsed_time(b) / batch
+
+    timed('score_cubes', lambda: tr.score_cubes(sc.store_raw, sc.store_flow, sc.idx))
+    timed('score_cubes_maps', lambda: tr.score_cubes(sc.store_raw, sc.store_flow, sc.idx, maps=True))
+    timed('vv_stream_zpaint', lambda: stream_zpaint(e_raw, e_of, stats, sc.w_raw, sc.w_of, ones, ones, n, 0, rects, nb, None, sc.zmask, True))
+    timed('error_mask_copy', lambda: host.copy_(sc.zmask, non_blocking=True))
+    return dict(out, boxes=nb, cubes_per_launch=cap)
+
+
+def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tracks=False, maps=False):
     """``frames`` / ``boxes`` None: the test split of the tree and its box file.  ``mode='motion'``: ``push`` gets the frames alone.
-    ``pixels``: the ``masks`` / ``smooth`` / ``render`` switches of the scorer (None: all off).  ``tracks``: its ``tracks`` switch."""
+    ``pixels``: the ``masks`` / ``smooth`` / ``render`` switches of the scorer (None: all off).  ``tracks``: its ``tracks`` switch.
+    ``maps``: its ``maps`` switch (the error mask is copied out in ``wait()``, inside the timed span)."""
     import torch
     import foreground as FG
     import test as S
@@ -160,10 +207,11 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tr
     t0 = time.perf_counter()
     arts = S.load_artifacts(os.path.join(c['data_root_dir'], c['modality'], 'UCSDped2_'), c['mode_fg'], c['method'], False,
                             lambda: T.build_network(c), torch.device('cuda'))
-    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode, tracks=tracks, **(pixels or {}))
+    sc = StreamScorer(c, *arts, frames[0].shape, flownet2=net, boxes=mode, tracks=tracks, maps=maps, **(pixels or {}))
     torch.cuda.synchronize()
     setup = time.perf_counter() - t0
     scores, lat, found, dropped = np.zeros(n), [], np.zeros(n, np.int64), 0
+    fine = np.zeros(n)
     trk = dict(live_max=0, next_id=1, dropped=0, frames_with_a_track_score=0)
 
     def take(results):
@@ -171,6 +219,8 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tr
         for r in results:
             scores[r.frame] = r.wait()[0]
             found[r.frame], dropped = len(r.boxes), dropped + r.dropped
+            if maps:
+                fine[r.frame] = r.fine_score
             if tracks:
                 trk['live_max'], trk['dropped'] = max(trk['live_max'], len(r.tracks)), trk['dropped'] + r.tracks_dropped
                 trk['next_id'] = max([trk['next_id']] + [int(i) + 1 for i in r.track_ids])
@@ -186,6 +236,9 @@ def stream_leg(net, warm, frames=None, boxes=None, mode='given', pixels=None, tr
     extra = dict(pixels, pixel_launches_us=pixel_launches_us(sc, max(1, int(found.max())))) if pixels else {}
     if tracks:
         extra.update(tracks=trk, track_launch_us=track_launch_us(sc, max(1, int(found.max()))))
+    if maps:
+        extra.update(maps_launches_us=maps_launches_us(sc, max(1, int(found.max()))), fine_above_score=int((fine > scores).sum()),
+                     fine_support_is_the_scores=bool(((fine > -1e5) == (scores > -1e5)).all()))
     return dict(extra, setup_s=setup, wall_s=wall, wall_ms_per_frame=1e3 * wall / n, push_to_wait_ms_median=float(np.median(steady)),
                 push_to_wait_ms_p95=float(np.percentile(steady, 95)), push_to_wait_ms_max=float(steady.max()),
                 frames_timed=int(len(steady)), look_ahead_frames=1, max_boxes=sc.cap, boxes_per_frame_mean=float(found.mean()),
@@ -282,12 +335,20 @@ def measure(a, use_flow):
             res['stream_pixels'] = []
         if a.tracks:
             res['stream_tracks'] = []
+        if a.maps:
+            res['stream_maps'] = []
         for _ in range(a.reps):
-            b, sb = batch_leg(net, a.frames)
+            if not a.no_batch:
+                b, sb = batch_leg(net, a.frames)
+                res['batch'].append(b)
             s, ss = stream_leg(net, a.warm)
-            res['batch'].append(b)
             res['stream'].append(s)
-            res['largest_score_difference'] = float(np.abs(sb - ss).max())
+            if not a.no_batch:
+                res['largest_score_difference'] = float(np.abs(sb - ss).max())
+            if a.maps:
+                m, sm = stream_leg(net, a.warm, maps=True)
+                res['stream_maps'].append(m)
+                res['maps_change_a_score'] = bool((sm != ss).any())
             if pixels:
                 p, sp = stream_leg(net, a.warm, pixels=pixels)
                 res['stream_pixels'].append(p)
@@ -314,6 +375,8 @@ def main():
     ap.add_argument('--smooth', action='store_true')
     ap.add_argument('--render', action='store_true')
     ap.add_argument('--tracks', action='store_true')
+    ap.add_argument('--maps', action='store_true')
+    ap.add_argument('--no-batch', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)

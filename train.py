@@ -140,6 +140,7 @@ def read_config(path='config.cfg'):
              stream_smooth=cp.getboolean('mi355x', 'stream_smooth', fallback=False),
              stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False),
              stream_tracks=cp.getboolean('mi355x', 'stream_tracks', fallback=False),
+             stream_maps=cp.getboolean('mi355x', 'stream_maps', fallback=False),
              track_iou_percent=cp.getint('mi355x', 'track_iou_percent', fallback=30),
              track_max_age=cp.getint('mi355x', 'track_max_age', fallback=5),
              track_window=cp.getint('mi355x', 'track_window', fallback=8),

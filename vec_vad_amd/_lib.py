@@ -179,6 +179,8 @@ _SIGS = {
     'vv_stream_boxes': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp]),
     'vv_stream_paint': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vv_stream_zpaint': (c_i32, [c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp,
+                                 c_i32, c_vp]),
     'vv_stream_tracks': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
                                  c_i32, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'vv_stream_smooth_partials': (c_i64, [c_i32, c_i32]),

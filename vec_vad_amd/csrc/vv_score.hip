@@ -251,9 +251,7 @@ __global__ void __launch_bounds__(256) auc_count_kernel(const double* __restrict
 // ---- per-pixel anomaly maps: the per-pixel errors of vv_error_maps -> z-maps -> fine masks -> the pixel criterion on a formed mask --
 // z[m][q] = cube_score with 1024 * e[m][q] in place of the cube's error (a 32x32 patch: the cube's error is the sum of its 1024 pixel
 // errors, so a cube whose error is spread evenly gets the constant map z = its cube score, to the bit; the scaling by 2^10 is exact).
-constexpr int ZMAP_PIX = 1024;               // pixels of a patch (32 x 32)
-constexpr int ZMAP_SIDE = 32;
-
+// ZMAP_PIX, ZMAP_SIDE and zmap_src (the nearest source pixel of a stretched patch) live in vv_score_fn.h, shared with vv_stream.hip.
 __global__ void __launch_bounds__(256) error_zmap_kernel(const float* __restrict__ e_raw, const float* __restrict__ e_of,
                                                          const int32_t* __restrict__ cube_stat, const double* __restrict__ stats,
                                                          double w_raw, double w_of, double big, int64_t total,
@@ -264,10 +262,6 @@ __global__ void __launch_bounds__(256) error_zmap_kernel(const float* __restrict
   const float o = e_of ? 1024.f * e_of[i] : 0.f;
   out[i] = cube_score(&r, e_of ? &o : nullptr, cube_stat + i / ZMAP_PIX, stats, w_raw, w_of, big, 0);
 }
-
-// nearest source row / column of a patch stretched over [lo, hi): ((2 (v - lo) + 1) * 32) / (2 (hi - lo)) in integers, 0..31 for
-// lo <= v < hi, the identity when hi - lo == 32
-__device__ __forceinline__ int zmap_src(int v, int lo, int hi) { return ((2 * (v - lo) + 1) * ZMAP_SIDE) / (2 * (hi - lo)); }
 
 // paint_mask_kernel with the value read from the cube's z-map instead of one score per box: same tiles, same pairs, same LDS passes
 // over the frame's rectangles (no limit on their number); z is read through L2 only where the pixel lies inside the rectangle.

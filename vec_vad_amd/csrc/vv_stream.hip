@@ -8,6 +8,8 @@
 // them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.  vv_stream_paint is
 // the fourth: the frame's box-score rows painted into its score mask, with the box count and the motion boxes still on the device.
 // vv_stream_tracks is the fifth: over the same tables, the frame's boxes linked to the tracks of the frames before, in one workgroup.
+// vv_stream_zpaint is the sixth: behind a block's vv_stream_scores, the per-pixel errors of that scoring launch painted into the frame's
+// error mask under the same keep flags and mask row -- vv_error_zmaps + vv_paint_zmaps of the batch route, the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -210,6 +212,93 @@ __global__ void __launch_bounds__(256) stream_paint_kernel(const double* __restr
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     frame_off[0] = 0;
     frame_off[1] = n;
+  }
+}
+
+// ---- the issued frame's per-pixel error mask (vv_stream_zpaint) --------------------------------------------------------------------------
+// stream_paint_kernel's layout with the value read from the box's error maps instead of one score per box: vv_error_zmaps and
+// vv_paint_zmaps of the batch route in one launch, for ONE block's share of ONE round.  Staging slot b of the round, a thread writes its
+// rectangle -- row slot0 + b of the frame's table, the host's below n_host, else Python's slicing of the device's box -- and one flag:
+// the slot counts (b < n, keep[b], mask[b]: the rule of stream_scores_kernel) and its rectangle holds a pixel.  Every lane reads the same
+// entry (broadcast); the maps of a slot whose flag is 0 are never read, and those of a counted slot only where a pixel lies in its
+// rectangle, through L2.  first: the mask is written whole from the background -big; else the launch max-accumulates into what it holds.
+// The value of pixel (y, x) inside the rectangle r = (y0, y1, x0, x1) of the slot whose maps start at m0: vv_error_zmaps' expression at
+// the patch pixel vv_paint_zmaps reads.  The index is clamped into the patch, so that a rectangle that is no row of scoring.box_rects
+// cannot make the kernel read outside the maps.
+__device__ __forceinline__ double zpaint_value(const float* __restrict__ e_raw, const float* __restrict__ e_of, const double* st,
+                                               const double w_raw, const double w_of, const int64_t m0, const int y, const int x,
+                                               const int4 r) {
+  const int qy = min(max(zmap_src(y, r.x, r.y), 0), ZMAP_SIDE - 1), qx = min(max(zmap_src(x, r.z, r.w), 0), ZMAP_SIDE - 1);
+  const int64_t q = m0 + qy * ZMAP_SIDE + qx;
+  const float er = 1024.f * e_raw[q];
+  if (!e_of) return cube_score_row(&er, nullptr, st, w_raw, w_of, 0);
+  const float eo = 1024.f * e_of[q];
+  return cube_score_row(&er, &eo, st, w_raw, w_of, 0);      // two calls, so that neither operand's address is a run-time choice: no scratch
+}
+
+__global__ void __launch_bounds__(256) stream_zpaint_kernel(const float* __restrict__ e_raw, const float* __restrict__ e_of,
+                                                            const double* __restrict__ stats, double w_raw, double w_of, double big,
+                                                            const uint8_t* __restrict__ keep, const uint8_t* __restrict__ mask,
+                                                            const int32_t* __restrict__ n_ptr, int cap, int slot0,
+                                                            const int32_t* __restrict__ rects, int n_host,
+                                                            const int32_t* __restrict__ boxes, int h, int w, double* __restrict__ out,
+                                                            int first) {
+  __shared__ int4 srect[SP_STAGE];
+  __shared__ int sflag[SP_STAGE];
+  const int n = min(max(n_ptr[0], 0), cap);
+  const int hw = h * w;
+  const int p0 = (blockIdx.x * 256 + (int)threadIdx.x) * SP_PIX;
+  const bool in0 = p0 < hw, in1 = p0 + 1 < hw;
+  const int ya = in0 ? p0 / w : -1, xa = in0 ? p0 - ya * w : -1;      // a pixel past the frame lies in no box
+  const int yb = in1 ? (p0 + 1) / w : -1, xb = in1 ? p0 + 1 - yb * w : -1;
+  const bool wide = in1 && (reinterpret_cast<uintptr_t>(out + p0) & 15) == 0;
+  double v0 = -big, v1 = -big;
+  if (!first) {
+    if (wide) {
+      const double2 v = *reinterpret_cast<const double2*>(out + p0);
+      v0 = v.x, v1 = v.y;
+    } else {
+      if (in0) v0 = out[p0];
+      if (in1) v1 = out[p0 + 1];
+    }
+  }
+  double st[4] = {0.0, 1.0, 0.0, 1.0};
+  if (stats) st[0] = stats[0], st[1] = stats[1], st[2] = stats[2], st[3] = stats[3];
+  for (int base = 0; base < n; base += SP_STAGE) {
+    const int cnt = min(SP_STAGE, n - base);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const int b = base + (int)threadIdx.x, g = slot0 + b;
+      int4 r = make_int4(0, 0, 0, 0);
+      int counts = 0;
+      if (keep[b] && mask[b]) {
+        if (!boxes || g < n_host) {
+          r = make_int4(rects[4 * g + 0], rects[4 * g + 1], rects[4 * g + 2], rects[4 * g + 3]);
+        } else {
+          const int x1 = boxes[4 * g + 0], y1 = boxes[4 * g + 1], x2 = boxes[4 * g + 2], y2 = boxes[4 * g + 3];
+          r = make_int4(slice_bound(y1, h), slice_bound(y2, h), slice_bound(x1, w), slice_bound(x2, w));
+        }
+        counts = r.y > r.x && r.w > r.z;
+      }
+      srect[threadIdx.x] = r;
+      sflag[threadIdx.x] = counts;
+    }
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      if (!sflag[k]) continue;                // the same for every lane
+      const int4 r = srect[k];                // y0, y1, x0, x1
+      const int64_t m0 = (int64_t)(base + k) * ZMAP_PIX;
+      const bool hit0 = ya >= r.x && ya < r.y && xa >= r.z && xa < r.w;
+      const bool hit1 = yb >= r.x && yb < r.y && xb >= r.z && xb < r.w;
+      if (hit0) v0 = fmax(v0, stats ? zpaint_value(e_raw, e_of, st, w_raw, w_of, m0, ya, xa, r) : big);
+      if (hit1) v1 = fmax(v1, stats ? zpaint_value(e_raw, e_of, st, w_raw, w_of, m0, yb, xb, r) : big);
+    }
+  }
+  if (wide) {
+    *reinterpret_cast<double2*>(out + p0) = make_double2(v0, v1);
+  } else {
+    if (in0) out[p0] = v0;
+    if (in1) out[p0 + 1] = v1;
   }
 }
 
@@ -499,6 +588,20 @@ extern "C" int vv_stream_paint(const double* scores, int32_t rows, int32_t width
   const int tiles = max(1, (h * w + SP_TILE - 1) / SP_TILE);      // a frame of no pixels still leaves box_max, rects and frame_off
   VV_LAUNCH(stream_paint_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, scores, (int)rows, (int)width, n, (int)n_host,
             reinterpret_cast<int4*>(rects), boxes, (int)h, (int)w, mask, box_max, frame_off);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_stream_zpaint(const float* e_raw, const float* e_of, const double* stats, double w_raw, double w_of, double big,
+                                const uint8_t* keep, const uint8_t* mask, const int32_t* n, int32_t cap, int32_t slot0,
+                                const int32_t* rects, int32_t n_host, const int32_t* boxes, int32_t h, int32_t w, double* out,
+                                int32_t first, vv_stream stream) {
+  if (!out || !n || !rects || cap < 0 || slot0 < 0 || n_host < 0 || h <= 0 || w <= 0 || (stats && !e_raw)) return VV_ERR_BAD_ARG;
+  if (cap > 0 && (!keep || !mask)) return VV_ERR_BAD_ARG;
+  if ((int64_t)h * w > INT32_MAX / 64 - SP_TILE || (int64_t)slot0 + cap > INT32_MAX / 4) return VV_ERR_BAD_ARG;      // zmap_src: 64 (v - lo) in int32
+  const int tiles = (h * w + SP_TILE - 1) / SP_TILE;
+  VV_LAUNCH(stream_zpaint_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, e_raw, stats ? e_of : nullptr, stats, w_raw,
+            w_of, big, keep, mask, n, (int)cap, (int)slot0, rects, (int)n_host, boxes, (int)h, (int)w, out, (int)first);
   VV_CHECK_LAUNCH();
   return VV_OK;
 }

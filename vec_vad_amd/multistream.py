@@ -22,8 +22,8 @@ launch, an error sum that of a scoring launch of ``cameras*max_boxes`` cubes; wi
 No camera's values depend on another camera's frames or boxes.
 
 Limits.  All cameras share one frame shape and one model set (for ShanghaiTech: one scene per scorer).  Boxes are given: the motion
-boxes, masks, smoothing, overlays and tracks of ``StreamScorer`` stay single-camera features and are refused here when switched on in
-the configuration.  Cameras that tick at different rates pass ``None`` for the ticks they miss.
+boxes, masks, smoothing, overlays, tracks and per-pixel error maps of ``StreamScorer`` stay single-camera features and are refused
+here when switched on in the configuration.  Cameras that tick at different rates pass ``None`` for the ticks they miss.
 """
 import os
 
@@ -57,6 +57,14 @@ def check_single_camera_keys(c):
         if on:
             raise ValueError('[mi355x] {} = {} is a single-camera feature: several cameras in one scorer take given boxes and deliver '
                              'scores only (use stream_cameras = 1)'.format(key, 'motion' if key == 'stream_boxes' else 'on'))
+
+
+def check_stream_maps(c):
+    """``stream_maps`` switched on in ``c`` is refused with a one-line ``ValueError``: the per-pixel error mask is a single-camera
+    feature like those of ``SINGLE_CAMERA_KEYS``; no GPU is touched."""
+    if bool(c.get('stream_maps', False)):
+        raise ValueError('[mi355x] stream_maps = on is a single-camera feature: several cameras in one scorer take given boxes and '
+                         'deliver scores only (use stream_cameras = 1)')
 
 
 def stream_cut_multi(raw_ring, flow_ring, cams, n, crops, raw_win, flow_win, thr, raw_store, flow_store, keep, energy=None):
@@ -281,6 +289,7 @@ class MultiStreamScorer:
         self.cameras = check_cameras(cameras)                                                                # all before any GPU work
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)
         check_single_camera_keys(c)
+        check_stream_maps(c)
         from vad_datasets import frame_size
         from vec_vad_amd.trainer import FusedTrainer
         cp, ds, method = c['cp'], c['dataset_name'], c['method']
@@ -352,6 +361,7 @@ class MultiStreamScorer:
         c = read_config(config_path)
         cameras = check_cameras(c['stream_cameras'] if cameras is None else cameras)
         check_single_camera_keys(c)
+        check_stream_maps(c)
         from test import load_artifacts
         from vad_datasets import frame_size
         ds = c['dataset_name']

@@ -63,11 +63,23 @@ It needs the descriptor's tail (the count and the host's rectangles) but no mask
 one copy behind the same event (``StreamResult.track_ids`` / ``.track_hits`` / ``.track_scores`` / ``.track_score`` /
 ``.tracks_dropped`` / ``.tracks``).  The defaults of its keys are untuned picks; no accuracy is claimed for them.
 
-What is not here: the mmdet detector (detector boxes are the caller's), decoding, a centred (delayed) smoothing window, per-pixel
-error maps, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment by the Hungarian method,
-re-identification and ids drawn into the picture.  Several cameras in one scorer are ``vec_vad_amd.multistream.MultiStreamScorer``
-(one frame shape and one model set, given boxes, scores only): the motion boxes, masks, smoothing, overlays and tracks described
-above stay features of this single-camera class.
+Where inside a box (``maps``; ``[mi355x] stream_maps``, off by default -- then nothing more is allocated, launched or copied).  A
+score mask is constant over every rectangle.  With ``maps`` every scoring launch is the one that also stores its reconstructions
+(``FusedTrainer.score_cubes(maps=True)``, a captured graph of its own, warmed at construction; its error sums are the bits of the
+plain launch, so score, box scores and keep flags do not change), and behind each block's ``vv_stream_scores`` one
+``vv_stream_zpaint`` paints that launch's per-pixel errors into the frame's error mask: for every box that counts -- the same count on
+the device, keep flags and mask row -- the 32 x 32 map of z-scores, stretched over the box's rectangle, max-combined over boxes,
+blocks and rounds.  It is ``scoring.error_zmaps`` + ``scoring.paint_error_masks`` of the batch route in one launch, bit for bit, for
+boxes the host may not even know: rectangles of motion boxes are resolved by the kernel.  The frame's first launch writes the mask
+whole (a frame without a box gets one background launch), so there is no fill.  ``StreamResult.error_mask`` arrives in a pooled
+pinned buffer behind the event ``wait()`` already waits on, ``StreamResult.fine_score`` is its maximum.  It needs the descriptor's
+tail but neither the score mask nor the tracks; smoothing and overlays keep working on the score mask, not on this one.
+
+What is not here: the mmdet detector (detector boxes are the caller's), decoding, a centred (delayed) smoothing window, smoothing or
+rendering of the error mask, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment by the
+Hungarian method, re-identification and ids drawn into the picture.  Several cameras in one scorer are
+``vec_vad_amd.multistream.MultiStreamScorer`` (one frame shape and one model set, given boxes, scores only): the motion boxes, masks,
+smoothing, overlays, tracks and error maps described above stay features of this single-camera class.
 """
 import os
 
@@ -215,6 +227,39 @@ def stream_paint(scores, n, n_host, rects, boxes, mask, box_max, frame_off):
                                           boxes.data_ptr() if boxes is not None else None, mask.shape[0], mask.shape[1], mask.data_ptr(),
                                           box_max.data_ptr(), frame_off.data_ptr(), torch.cuda.current_stream(mask.device).cuda_stream),
                'vv_stream_paint')
+
+
+def stream_zpaint(e_raw, e_of, stats, w_raw, w_of, keep, mask, n, slot0, rects, n_host, boxes, out, first):
+    """``vv_stream_zpaint``: one block's share of one round of a frame's per-pixel error mask.  e_raw / e_of: float32 ``[cap,32,32]``,
+    the per-pixel errors of a scoring launch over the store (``FusedTrainer.score_cubes(maps=True)``; ``e_of`` None drops the flow term;
+    both may be None with ``stats`` None); stats, w_raw, w_of, keep uint8 ``[cap]``, n int32 ``[1]`` and mask uint8 ``[cap]`` as for
+    ``stream_scores`` (``cap`` is ``keep``'s length); rects int32 ``[width,4]`` rows ``(y0, y1, x0, x1)`` of the FRAME, of which the
+    round's are rows ``slot0 .. slot0 + cap - 1``; rows below ``n_host`` are the host's (``scoring.box_rects``), the others are resolved
+    from boxes int32 ``[width,4]`` rows ``(x1, y1, x2, y2)`` as ``stream_paint`` resolves them (None: every rectangle is the host's).
+    out float64 ``[h,w]`` is written in place: pixel ``(y, x)`` of the rectangle of a slot ``b < n[0]`` with ``keep[b]`` and ``mask[b]``
+    is max-combined with the value ``scoring.error_zmaps`` + ``scoring.paint_error_masks`` give it (``+BIG`` without a model).
+    ``first``: the mask is written whole over a background of ``-BIG`` and what ``out`` held is not read; else the launch accumulates.
+    The maps of a slot that does not count are not read."""
+    _dev('out', out, torch.float64), _dev('keep', keep, torch.uint8), _dev('n', n, torch.int32, 1)
+    if out.dim() != 2:
+        raise ValueError('out must be an [h,w] tensor')
+    cap, slot0 = keep.numel(), int(slot0)
+    if slot0 < 0:
+        raise ValueError('slot0 must not be negative, got {}'.format(slot0))
+    _dev('mask', mask, torch.uint8, cap), _dev('rects', rects, torch.int32, 4 * (slot0 + cap))
+    if boxes is not None:
+        _dev('boxes', boxes, torch.int32, 4 * (slot0 + cap))
+    if stats is not None:
+        _dev('stats', stats, torch.float64, 4), _dev('e_raw', e_raw, torch.float32, 1024 * cap)
+        if e_of is not None:
+            _dev('e_of', e_of, torch.float32, 1024 * cap)
+    _lib.check(_lib.lib().vv_stream_zpaint(e_raw.data_ptr() if stats is not None else None,
+                                           e_of.data_ptr() if (stats is not None and e_of is not None) else None,
+                                           stats.data_ptr() if stats is not None else None, float(w_raw), float(w_of), float(BIG),
+                                           keep.data_ptr() if cap else None, mask.data_ptr() if cap else None, n.data_ptr(), cap, slot0,
+                                           rects.data_ptr(), int(n_host), boxes.data_ptr() if boxes is not None else None, out.shape[0],
+                                           out.shape[1], out.data_ptr(), int(bool(first)),
+                                           torch.cuda.current_stream(out.device).cuda_stream), 'vv_stream_zpaint')
 
 
 def stream_smooth(ring, win, kt, ks, Bsum, bcnt, out, partial):
@@ -379,7 +424,11 @@ class StreamResult:
     and the frames that track was matched in; ``track_scores``, float64 ``[n]``, the mean of the track's last ``track_window`` scores
     (``-BIG`` for id 0); ``track_score``, their maximum over tracks with ``track_min_hits`` matches or more (``-BIG`` without one);
     ``tracks_dropped``, the detections that found no free slot; ``tracks``, int32 ``[L,7]``, the live slots of the table in slot
-    order as ``(id, age, hits, y0, y1, x0, x1)``."""
+    order as ``(id, age, hits, y0, y1, x0, x1)``.
+
+    With the scorer's ``maps``, also after ``wait()`` (both None with the switch off): ``error_mask``, float64 ``[gh,gw]``, the
+    frame's per-pixel error mask -- inside the rectangle of every box that counts the box's map of z-scores, ``-BIG`` elsewhere (its
+    support is that of ``mask``) -- and ``fine_score``, a float, exactly ``error_mask.max()``."""
 
     def __init__(self, frame, n, rows, width, host, host_keep, event, boxes, host_found=None, pixels=None, tracks=None):
         self.frame, self._n, self._rows, self._width = frame, n, rows, width
@@ -387,7 +436,7 @@ class StreamResult:
         self._given, self._host_found = np.asarray(boxes, np.float64).reshape(-1, 4), host_found      # host_found: n, dropped, boxes_out
         self.boxes, self.dropped = (self._given, 0) if host_found is None else (None, None)
         self._pixels = pixels or {}          # name -> pooled pinned buffer, held until wait() has copied it out
-        self.mask = self.smooth_mask = self.smooth_score = self.picture = None
+        self.mask = self.smooth_mask = self.smooth_score = self.picture = self.error_mask = self.fine_score = None
         self._tracks = tracks                # (pinned copy of the scorer's track buffer, max_tracks, width) | None
         self.track_ids = self.track_hits = self.track_scores = self.track_score = self.tracks_dropped = self.tracks = None
 
@@ -412,6 +461,8 @@ class StreamResult:
                 self.smooth_score = float(a.max()) if a.size else -float(BIG)
             else:
                 setattr(self, name, a.copy())
+                if name == 'error_mask':      # a maximum does not round
+                    self.fine_score = float(self.error_mask.max())
             it[1] = None
 
     def __del__(self):                        # a result that was never waited for gives its buffers back once its copies have landed
@@ -472,7 +523,7 @@ _HELD = _Held()
 
 class StreamScorer:
     """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None,
-    masks=None, smooth=None, render=None, tracks=None)``.
+    masks=None, smooth=None, render=None, tracks=None, maps=None)``.
 
     ``c``: the dict of ``train.read_config``; ``net_set`` / ``stats_raw`` / ``stats_of``: what ``test.load_artifacts`` returns;
     ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3); ``flownet2``: the network (None loads
@@ -508,10 +559,15 @@ class StreamScorer:
     its score is the mean of its last ``track_window`` box scores, and the frame's track score the largest over tracks seen
     ``track_min_hits`` times or more (``StreamResult.track_ids`` / ``.track_hits`` / ``.track_scores`` / ``.track_score`` /
     ``.tracks_dropped`` / ``.tracks``).  The box scores are those of the frame's score mask: a box that paints no pixel of the
-    nominal frame or scored ``-BIG`` has no track.  Needs no mask: with ``masks`` off nothing of the mask ring exists."""
+    nominal frame or scored ``-BIG`` has no track.  Needs no mask: with ``masks`` off nothing of the mask ring exists.
+
+    ``maps`` (None reads ``[mi355x] stream_maps``; off by default, and then nothing of it is allocated, launched or copied): every
+    scoring launch also stores its reconstructions (the ``'eval_maps'`` graph of ``FusedTrainer``, warmed and captured here, so that a
+    ``push`` only replays), and one ``vv_stream_zpaint`` per scored block and round paints the per-pixel errors of the boxes that count
+    into the frame's error mask (``StreamResult.error_mask`` / ``.fine_score``).  Score, box scores and keep flags keep their bits."""
 
     def __init__(self, c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda',
-                 boxes=None, masks=None, smooth=None, render=None, tracks=None):
+                 boxes=None, masks=None, smooth=None, render=None, tracks=None, maps=None):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
         self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
         from vad_datasets import frame_size
@@ -530,7 +586,8 @@ class StreamScorer:
         (self.masks, self.smooth, self.render, self.kt, self.ks, self.render_source, self.render_boxes, self.render_lo, self.render_hi,
          self.render_alpha) = check_pixel_settings(c, masks, smooth, render, (H, W), frame_size[ds][:2])      # before any GPU work
         self.tracks, self.trk_iou, self.trk_age, self.trk_window, self.trk_hits, self.trk_max = check_track_settings(c, tracks)
-        self.tail = self.masks or self.tracks          # the stages that read the descriptor's tail
+        self.maps = bool(c.get('stream_maps', False) if maps is None else maps)
+        self.tail = self.masks or self.tracks or self.maps      # the stages that read the descriptor's tail
         self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion,
                                   mask_frames=self.kt if self.smooth else 1)
         self.P = cp.getint(ds, 'patch_size')
@@ -602,6 +659,9 @@ class StreamScorer:
             self._init_pixels()
         if self.tracks:
             self._init_tracks()
+        if self.maps:                         # the frame's error mask: every block's vv_stream_zpaint of every round accumulates into it
+            self.zmask = torch.empty((self.grid_h, self.grid_w), dtype=torch.float64, device=dev)
+            self.zfirst = True                # the frame being issued has had no vv_stream_zpaint launch yet
         self.staging = _Staging()
         self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
@@ -609,11 +669,11 @@ class StreamScorer:
         for ent in self.blocks.values():
             if ent is not None:
                 for _ in range(3):
-                    ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
+                    ent[0].score_cubes(self.store_raw, self.store_flow, self.idx, maps=self.maps)
         torch.cuda.synchronize(dev)
 
     def _init_tail(self):
-        """Behind the descriptor, for the stages behind a frame's last ``vv_stream_scores`` (pixels, tracks): the tail ``n, 3 unused |
+        """Behind the descriptor, for the stages that read the frame's box count and rectangles (pixels, tracks, maps): the tail ``n, 3 unused |
         window [1 + K], padded to 4 words | rects [width][4]``."""
         dev, K = self.device, self.sched.K
         self.t_win = 4
@@ -782,19 +842,39 @@ class StreamScorer:
         _lib.check(lib.vv_flow_resize_back(self.flow_out.data_ptr(), 1, self.flow_h, self.flow_w, base + 8, self.H, self.W,
                                            self.flow_ring.data_ptr(), sc.Rf, stream), 'vv_flow_resize_back')
 
-    def _score_block(self, cell, keep, n, masks, box_scores, frame_score):
+    def _score_block(self, cell, keep, n, masks, box_scores, frame_score, zp=None):
         """One block's share of a round: its model scores the whole store in its own fixed-size launch (no launch for a block without a
-        model), ``vv_stream_scores`` reduces under ``keep`` and the block's mask row."""
+        model), ``vv_stream_scores`` reduces under ``keep`` and the block's mask row.  With ``maps`` the launch is the one that stores
+        the reconstructions (same sums), and ``vv_stream_zpaint`` paints its per-pixel errors into the frame's error mask behind it;
+        ``zp = (slot0, rects, n_host, boxes_dev)``: the round's first row of the frame's rectangle table and who resolves which row."""
         hh, ww = cell
         ent = self.blocks[cell]
-        raw = of = stats = None
+        raw = of = stats = e_raw = e_of = None
         if ent is not None:
-            raw, of = ent[0].score_cubes(self.store_raw, self.store_flow, self.idx)
+            raw, of, *maps = ent[0].score_cubes(self.store_raw, self.store_flow, self.idx, maps=self.maps)
+            if self.maps:
+                e_raw, e_of = maps[0], (maps[1] if self.use_flow else None)
             raw = raw.to(torch.float32).contiguous()
             of = of.to(torch.float32).contiguous() if (of is not None and self.use_flow) else None
             stats = ent[1]
         m0 = (hh * self.wb + ww) * self.cap
         stream_scores(raw, of, stats, self.w_raw, self.w_of, keep, n, masks[m0:m0 + self.cap], box_scores, frame_score)
+        if self.maps:
+            slot0, rects, n_host, boxes_dev = zp
+            stream_zpaint(e_raw, e_of, stats, self.w_raw, self.w_of, keep, masks[m0:m0 + self.cap], n, slot0, rects, n_host, boxes_dev,
+                          self.zmask, self.zfirst)
+            self.zfirst = False
+
+    def _maps_out(self, n_dev, rects):
+        """The frame's error mask on its way to a pooled pinned buffer, on the current stream (the caller's event behind it covers the
+        copy).  A frame that had no ``vv_stream_zpaint`` launch -- no box, or no block with a box -- gets its one background launch."""
+        if self.zfirst:
+            none = self.idx[:0].to(torch.uint8)
+            stream_zpaint(None, None, None, self.w_raw, self.w_of, none, none, n_dev, 0, rects, 0, None, self.zmask, True)
+        self.zfirst = True                    # for the next frame
+        it = self.staging.hold('error_mask', self.zmask.shape, self.zmask.dtype)
+        it[0].copy_(self.zmask, non_blocking=True)
+        return {'error_mask': it}
 
     def _read_back(self, *tensors):
         """Non-blocking copies to fresh pinned memory and the event behind them."""
@@ -841,6 +921,8 @@ class StreamScorer:
         width = rounds * cap
         out = torch.full((1 + len(rows) * width,), -float(BIG), dtype=torch.float64, device=self.device)
         keep = torch.zeros(max(width, 1), dtype=torch.uint8, device=self.device)
+        tail = desc[t_base:words] if self.tail else None
+        zrects = tail[self.t_rects:self.t_rects + 4 * max(width, 1)] if self.maps else None
         for r in range(rounds):
             o = 4 + r * D
             rnd, k = desc[o:o + D], keep[r * cap:(r + 1) * cap]
@@ -848,14 +930,16 @@ class StreamScorer:
             stream_cut(self.raw_ring, self.flow_ring, rnd[0:1], rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
                        rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
             for i in used[r]:
-                self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1])
+                self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1],
+                                  (r * cap, zrects, n, None))
         pixels, trk = None, []
         if self.tail:
-            tail = desc[t_base:words]
             if self.tracks:
                 trk = [self._tracks(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)]
             if self.masks:
                 pixels = self._pixels(issue, tail, out[1:].view(len(rows), width), tail[0:1], n, None)
+            if self.maps:
+                pixels = dict(pixels or {}, **self._maps_out(tail[0:1], zrects))
         (host, host_keep, *host_trk), event = self._read_back(out, keep, *trk)
         return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes, pixels=pixels,
                             tracks=(host_trk[0], self.trk_max, width) if host_trk else None)
@@ -915,13 +999,16 @@ class StreamScorer:
                    rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, keep)
         cells = [(hh, ww) for hh in range(self.hb) for ww in range(self.wb)]
         out = torch.full((1 + len(cells) * cap,), -float(BIG), dtype=torch.float64, device=self.device)
+        zrects = desc[self.t_base + self.t_rects:self.t_base + self.t_rects + 4 * cap] if self.maps else None
         for i, cell in enumerate(cells):
-            self._score_block(cell, keep, n, masks, out[1 + i * cap:1 + (i + 1) * cap], out[0:1])
+            self._score_block(cell, keep, n, masks, out[1 + i * cap:1 + (i + 1) * cap], out[0:1], (0, zrects, k, found[2:]))
         pixels, trk = None, []
         if self.tracks:
             trk = [self._tracks(issue, desc[self.t_base:], out[1:].view(len(cells), cap), n, k, found[2:])]
         if self.masks:
             pixels = self._pixels(issue, desc[self.t_base:], out[1:].view(len(cells), cap), n, k, found[2:])
+        if self.maps:
+            pixels = dict(pixels or {}, **self._maps_out(n, zrects))
         (host, host_keep, host_found, *host_trk), event = self._read_back(out, keep, found, *trk)
         return StreamResult(self.frames - 1, None, len(cells), cap, host, host_keep, event, boxes, host_found, pixels=pixels,
                             tracks=(host_trk[0], self.trk_max, cap) if host_trk else None)
