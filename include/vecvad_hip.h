@@ -638,6 +638,34 @@ int vv_stream_scores_multi(const float* raw, const float* of, const double* stat
                            const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cams, int32_t cap, double* box_scores,
                            int64_t box_stride, double* frame_score, int64_t frame_stride, vv_stream stream);
 
+/* ---- training from pushed frames (vec_vad_amd/stream_train.py): the kept cubes of one vv_stream_cut round appended to ONE large
+ * training store, behind the round's cut on the same stream, with no word to the host.
+ * vv_stream_append: one workgroup per slot of the round.
+ *   raw_slots uint8 [cap][raw_cube_bytes], flow_slots float32 [cap][flow_cube_bytes / 4], keep uint8 [cap], n int32 [1]: the stores,
+ *             keep flags and box count of vv_stream_cut; n[0] is read on the device and clamped to [0, cap]
+ *   masks     uint8 [cells][cap]: the round's block rows (the descriptor's, or those of vv_stream_boxes); NULL only with cells == 0
+ *   boxes     int32 [cap][4] (the boxes_out of vv_stream_boxes) or NULL
+ *   frame     the running frame index; slot0: the box index of slot 0 (round * cap)
+ *   cursor_in, cursor_out int32 [1]: two DIFFERENT cells, which the host alternates per launch
+ *   raw_store uint8 [capacity][raw_cube_bytes], flow_store float32 [capacity][flow_cube_bytes / 4], meta int32 [capacity][2],
+ *             meta_boxes int32 [capacity][4], meta_cells uint8 [capacity][cells]
+ *   The kept slots are the b < n[0] with keep[b] != 0, in ascending b; the j-th of them goes to store cube d = cursor_in[0] + j.  If
+ *   0 <= d < capacity: its raw_cube_bytes and flow_cube_bytes are copied unchanged to cube d of the two stores, meta[d] = (frame,
+ *   slot0 + b), meta_boxes[d] = boxes[b] (four zeros when boxes == NULL) and meta_cells[d][k] = masks[k * cap + b] for k < cells.  A
+ *   cube with d >= capacity is not written anywhere.  cursor_out[0] = cursor_in[0] + (number of kept slots), NOT clamped, so that the
+ *   host can say how many cubes would have been needed.  Nothing else is written, whatever the slots >= n[0] and the unkept slots
+ *   hold (NaN and Inf included), and no store cube outside [cursor_in[0], cursor_in[0] + kept).
+ *   Every workgroup derives its slot's rank from keep[0..b) itself (a count in LDS); workgroup 0 alone writes cursor_out.  Ordinary
+ *   vector loads and stores only, no atomics, no workgroup waits for another; bit-identical run to run.  The copy uses 16-byte accesses
+ *   where source, destination and size allow (always for P = 32 on 16-byte aligned stores), else a byte path.  The entry point
+ *   allocates nothing and copies nothing.  VV_ERR_BAD_ARG without a launch: cap < 1, cells < 0, capacity < 0, a negative cube size; NULL
+ *   n, keep, cursor_in, cursor_out, raw_slots, flow_slots, raw_store, flow_store, meta, meta_boxes or meta_cells; NULL masks with
+ *   cells > 0; cursor_in == cursor_out. */
+int vv_stream_append(const uint8_t* raw_slots, const float* flow_slots, const uint8_t* keep, const int32_t* n, int32_t cap,
+                     int64_t raw_cube_bytes, int64_t flow_cube_bytes, const uint8_t* masks, int32_t cells, const int32_t* boxes,
+                     int32_t frame, int32_t slot0, const int32_t* cursor_in, int32_t* cursor_out, int64_t capacity, uint8_t* raw_store,
+                     float* flow_store, int32_t* meta, int32_t* meta_boxes, uint8_t* meta_cells, vv_stream stream);
+
 /* ---- a streamed frame's score mask, its trailing-window mean and the tables its picture needs (StreamScorer with masks / smooth /
  * render): what test.py's paint, smooth and render stages compute for a finished split, for ONE issued frame, with the box count and
  * the motion boxes still on the device.  VV_STREAM_UNPAINTED (-100000.0, = VV_SMOOTH_UNPAINTED = VV_RENDER_UNPAINTED) is the background.

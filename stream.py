@@ -82,10 +82,11 @@ def _evaluate(c, scores, labels, scene_idx, shanghai, smooth=False, track=False,
         print('Frame-level AUC of the {} is {}'.format(what, auc))
 
 
-def _detector_boxes(c, n):
+def _detector_boxes(c, n, mode='test'):
     """``[mi355x] stream_boxes = motion``: the appearance boxes of every test frame as ``foreground._motion_bboxes`` reads them -- the
-    first four columns of the rows of ``bboxes_test_obj_det.npy`` when that file exists (it must hold ``n`` frames), none otherwise."""
-    path = os.path.join(c['raw_dataset_dir'], c['dataset_name'], 'bboxes_test_obj_det.npy')
+    first four columns of the rows of ``bboxes_test_obj_det.npy`` when that file exists (it must hold ``n`` frames), none otherwise.
+    ``mode='train'``: those of the training split (``bboxes_train_obj_det.npy``; stream_train.py)."""
+    path = os.path.join(c['raw_dataset_dir'], c['dataset_name'], 'bboxes_{}_obj_det.npy'.format(mode))
     if not os.path.exists(path):
         print('no {}: motion boxes only (no appearance boxes)'.format(path))
         return [np.zeros((0, 4), np.float32) for _ in range(n)]

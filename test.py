@@ -107,7 +107,12 @@ def load_artifacts(base, fg, method, shanghai, build_net, device, h_block=1, w_b
     weights = torch.load(base + 'model_{}_{}.npy'.format(fg, method), map_location='cpu', weights_only=False)
     raw_tr = torch.load(base + 'raw_training_scores_{}_{}.npy'.format(fg, method), weights_only=False)
     of_tr = torch.load(base + 'of_training_scores_{}_{}.npy'.format(fg, method), weights_only=False)
+    return artifacts_from(weights, raw_tr, of_tr, shanghai, build_net, device)
 
+
+def artifacts_from(weights, raw_tr, of_tr, shanghai, build_net, device):
+    """What follows the file loads of ``load_artifacts``: the three nested lists the training stage saves (``train.train_store`` returns
+    them) -> (net_set, raw statistics, flow statistics)."""
     def build(wl):
         return [load_model(build_net(), wl[0], device)] if len(wl) > 0 else []
 

@@ -136,6 +136,7 @@ def read_config(path='config.cfg'):
              stream_max_boxes=cp.get('mi355x', 'stream_max_boxes', fallback='64').strip(),
              stream_boxes=cp.get('mi355x', 'stream_boxes', fallback='given').strip().lower(),
              stream_cameras=cp.get('mi355x', 'stream_cameras', fallback='1').strip(),
+             collect_max_cubes=cp.get('mi355x', 'collect_max_cubes', fallback='65536').strip(),
              stream_masks=cp.getboolean('mi355x', 'stream_masks', fallback=False),
              stream_smooth=cp.getboolean('mi355x', 'stream_smooth', fallback=False),
              stream_render=cp.getboolean('mi355x', 'stream_render', fallback=False),
@@ -195,6 +196,8 @@ def read_config(path='config.cfg'):
     check_track_settings(c, None)                      # the settings of a stream's tracks, checked whatever the switch says
     from vec_vad_amd.multistream import check_cameras
     c['stream_cameras'] = check_cameras(c['stream_cameras'])      # cameras per scorer of stream.py, checked whatever route runs
+    from vec_vad_amd.stream_train import check_max_cubes
+    c['collect_max_cubes'] = check_max_cubes(c['collect_max_cubes'])      # cubes a StreamCollector's store holds (stream_train.py)
     if c['flownet2_checkpoint'] is None:
         from calc_optical_flow import CHECKPOINT
         c['flownet2_checkpoint'] = CHECKPOINT
@@ -446,11 +449,50 @@ def _training_blocks(c, base, store=None):
     return None, [len(row) for row in fset], blocks()
 
 
+def _train_blocks(c, net, scenes, rows, blocks, device, dist=None, log=print):
+    """The block loop of ``main``: ``train_block`` on every ``((s, h, w), segments)`` of ``_training_blocks``, ``net`` carried from
+    block to block as the reference carries it.  Returns the three nested lists that are saved: ``(model_set, raw_scores_set,
+    of_scores_set)``, ``[h][w]`` (below ``[scene]`` for ShanghaiTech), empty lists where a block was left out."""
+    def nested():
+        def grid():
+            return [[[] for _ in range(n)] for n in rows]
+        return grid() if scenes is None else [grid() for _ in range(scenes)]
+
+    model_set, raw_scores_set, of_scores_set = nested(), nested(), nested()
+    for (s, h, w), segments in blocks:
+        sd, r, o = train_block(net, segments, c['epochs'], c['batch_size'], c['lambda_raw'], c['lambda_of'],
+                               c['shuffle_seed'], device, log=log, tag='({}, {})'.format(h, w), dist=dist, overlap=c['overlap_wgrad'])
+        models, raw_sc, of_sc = ((t if s is None else t[s])[h] for t in (model_set, raw_scores_set, of_scores_set))
+        models[w].append({k: v.cpu() for k, v in sd.items()})
+        raw_sc[w] = r
+        of_sc[w] = o
+    return model_set, raw_scores_set, of_scores_set
+
+
+def train_store(c, store, net, dist=None, log=print):
+    """Every (h, w) block trained from a device-resident store: ``store`` is the dict of ``foreground.extract_train_device`` (or of
+    ``vec_vad_amd.stream_train.StreamCollector.finish``), each block's cubes its index list ``store['groups'][(None, h, w)]``.
+    Returns ``(model_set, raw_scores_set, of_scores_set)``, the three nested lists ``main`` saves."""
+    scenes, rows, blocks = _training_blocks(c, None, store)
+    return _train_blocks(c, net, scenes, rows, blocks, store['raw'].device, dist, log)
+
+
+def save_outputs(c, model_set, raw_scores_set, of_scores_set, log=print):
+    """The three files of the training stage under ``<data_root_dir>/<modality>/``, written as the reference writes them."""
+    base = os.path.join(c['data_root_dir'], c['modality'], c['dataset_name'] + '_')
+    fg, method = c['mode_fg'], c['method']
+    torch.save(raw_scores_set, base + 'raw_training_scores_{}_{}.npy'.format(fg, method))
+    torch.save(of_scores_set, base + 'of_training_scores_{}_{}.npy'.format(fg, method))
+    log('training scores saved!')
+    torch.save(model_set, base + 'model_{}_{}.npy'.format(fg, method))
+    log('Training of {} for dataset: {} has completed!'.format(method, c['dataset_name']))
+
+
 def main(config_path='config.cfg', flownet2=None):
     """``flownet2``: the network ``[mi355x] direct_flow`` computes the training split's flow with (only with ``direct_train``);
     None loads ``[mi355x] flownet2_checkpoint``."""
     c = read_config(config_path)
-    cp, ds, fg, root, mod, method = c['cp'], c['dataset_name'], c['mode_fg'], c['data_root_dir'], c['modality'], c['method']
+    cp, ds, root, mod = c['cp'], c['dataset_name'], c['data_root_dir'], c['modality']
     direct = c['direct_train']
     if direct and ds == 'ShanghaiTech':                         # before any GPU work
         raise NotImplementedError(DIRECT_TRAIN_SHANGHAI)
@@ -466,27 +508,12 @@ def main(config_path='config.cfg', flownet2=None):
         # (after build_network: loading FlowNet2 must not move the random state the initial weights are drawn from)
         from foreground import extract_train_device
         store = extract_train_device(c, device, log=print if rank == 0 else (lambda *a: None), flownet2=flownet2)
-    scenes, rows, blocks = _training_blocks(c, base, store)
-
-    def nested():
-        def grid():
-            return [[[] for _ in range(n)] for n in rows]
-        return grid() if scenes is None else [grid() for _ in range(scenes)]
-
-    model_set, raw_scores_set, of_scores_set = nested(), nested(), nested()
-    for (s, h, w), segments in blocks:
-        sd, r, o = train_block(net, segments, c['epochs'], c['batch_size'], c['lambda_raw'], c['lambda_of'],
-                               c['shuffle_seed'], device, tag='({}, {})'.format(h, w), dist=dist, overlap=c['overlap_wgrad'])
-        models, raw_sc, of_sc = ((t if s is None else t[s])[h] for t in (model_set, raw_scores_set, of_scores_set))
-        models[w].append({k: v.cpu() for k, v in sd.items()})
-        raw_sc[w] = r
-        of_sc[w] = o
+    if store is not None:
+        model_set, raw_scores_set, of_scores_set = train_store(c, store, net, dist)
+    else:
+        model_set, raw_scores_set, of_scores_set = _train_blocks(c, net, *_training_blocks(c, base), device, dist)
     if rank == 0:
-        torch.save(raw_scores_set, base + 'raw_training_scores_{}_{}.npy'.format(fg, method))
-        torch.save(of_scores_set, base + 'of_training_scores_{}_{}.npy'.format(fg, method))
-        print('training scores saved!')
-        torch.save(model_set, base + 'model_{}_{}.npy'.format(fg, method))
-        print('Training of {} for dataset: {} has completed!'.format(method, ds))
+        save_outputs(c, model_set, raw_scores_set, of_scores_set)
     if dist is not None:
         dist.barrier()
 

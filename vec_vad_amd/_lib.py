@@ -176,6 +176,8 @@ _SIGS = {
                                     c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'vv_stream_scores_multi': (c_i32, [c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64,
                                        c_vp]),
+    'vv_stream_append': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp]),
     'vv_stream_boxes': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp]),
     'vv_stream_paint': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

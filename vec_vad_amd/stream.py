@@ -79,7 +79,9 @@ What is not here: the mmdet detector (detector boxes are the caller's), decoding
 rendering of the error mask, the pixel and region criteria of ``test.py``, and for the tracks motion prediction, assignment by the
 Hungarian method, re-identification and ids drawn into the picture.  Several cameras in one scorer are
 ``vec_vad_amd.multistream.MultiStreamScorer`` (one frame shape and one model set, given boxes, scores only): the motion boxes, masks,
-smoothing, overlays, tracks and error maps described above stay features of this single-camera class.
+smoothing, overlays, tracks and error maps described above stay features of this single-camera class.  The models and statistics a
+scorer is built from can come from pushed frames too: ``vec_vad_amd.stream_train.StreamCollector`` runs this front half (``check_frame``,
+``RingSchedule``, ``_flow``, ``_fill_round``, ``_motion_front``) in front of a training store.
 """
 import os
 
@@ -133,6 +135,19 @@ def _dev(name, t, dtype, numel=None):
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() < numel):
         raise ValueError('{} must be a contiguous CUDA {} tensor{}'.format(name, dtype, '' if numel is None else ' of at least %d elements' % numel))
     return t
+
+
+def check_frame(frame_u8, boxes, H, W, C):
+    """What ``push`` is handed, checked on the host: the frame as a uint8 ``[H,W,C]`` array (a ``[H,W]`` one passes for ``C`` = 1) and
+    the first four columns of its boxes as float64 ``[n,4]``; a frame of another type or shape is a one-line ``ValueError``."""
+    frame = np.asarray(frame_u8)
+    if frame.ndim == 2 and C == 1:
+        frame = frame[:, :, None]
+    if frame.dtype != np.uint8 or tuple(frame.shape) != (H, W, C):
+        raise ValueError('push takes uint8 frames of shape {}, got {} {}'.format((H, W, C), frame.dtype, tuple(frame.shape)))
+    boxes = np.asarray(boxes, np.float64)
+    boxes = boxes.reshape(-1, boxes.shape[-1])[:, :4] if boxes.ndim == 2 and boxes.shape[0] else np.zeros((0, 4), np.float64)
+    return frame, boxes
 
 
 def stream_cut(raw_ring, flow_ring, n, crops, raw_win, flow_win, thr, raw_store, flow_store, keep, energy=None):
@@ -787,13 +802,7 @@ class StreamScorer:
     # ---- host side of a frame: everything that can be refused is refused before a ring is touched
     def _prepare(self, frame_u8, boxes):
         from utils import calc_block_idx
-        frame = np.asarray(frame_u8)
-        if frame.ndim == 2 and self.C == 1:
-            frame = frame[:, :, None]
-        if frame.dtype != np.uint8 or tuple(frame.shape) != (self.H, self.W, self.C):
-            raise ValueError('push takes uint8 frames of shape {}, got {} {}'.format((self.H, self.W, self.C), frame.dtype, tuple(frame.shape)))
-        boxes = np.asarray(boxes, np.float64)
-        boxes = boxes.reshape(-1, boxes.shape[-1])[:, :4] if boxes.ndim == 2 and boxes.shape[0] else np.zeros((0, 4), np.float64)
+        frame, boxes = check_frame(frame_u8, boxes, self.H, self.W, self.C)
         ap = None
         if self.motion:                                   # the given boxes are the frame's appearance boxes: one round holds them all
             from .motion import _ap_table
@@ -960,10 +969,11 @@ class StreamScorer:
                 here.add((hh, ww))
         return here
 
-    def _issue_motion(self, issue, held):
-        """A frame whose motion boxes the device finds: ONE round, the appearance boxes in slots ``0..k-1`` as ``_issue`` files them, the
-        motion boxes behind them by ``vv_stream_boxes``, and every block of the grid scored, since the host does not know where a motion
-        box lands."""
+    def _motion_front(self, issue, held):
+        """The front half of a frame whose motion boxes the device finds, up to the tables ``vv_stream_cut`` reads: the descriptor of
+        the ONE round (the appearance boxes in slots ``0..k-1`` as ``_issue`` files them), the flow, and ``vv_motion_mask`` ->
+        ``vv_mask_boxes`` -> ``vv_stream_boxes``, which files the motion boxes behind them.  Returns ``(desc, rnd, n, masks)``: the
+        descriptor and its round on the device, the box count on the device and the ``[hb*wb][cap]`` mask rows."""
         boxes, crops, blocks, ap = held
         lib, cap, sc, D, k = _lib.lib(), self.cap, self.sched, self.D, len(held[1])
         st = self.staging.get('desc', (self.desc.numel(),), torch.int32)
@@ -994,6 +1004,14 @@ class StreamScorer:
         n, masks = found[0:1], rnd[self.w_mask:].view(torch.uint8)
         stream_boxes(self.mt_count, self.mt_boxes, k, self.H, self.W, self.grid_h, self.grid_w, self.hb, self.wb, self.h_step, self.w_step,
                      self.block_mode, n, found[1:2], rnd[self.w_crops:self.w_rwin].view(cap, 4), masks, found[2:])
+        return desc, rnd, n, masks
+
+    def _issue_motion(self, issue, held):
+        """A frame whose motion boxes the device finds: ONE round, the appearance boxes in slots ``0..k-1`` as ``_issue`` files them, the
+        motion boxes behind them by ``vv_stream_boxes``, and every block of the grid scored, since the host does not know where a motion
+        box lands."""
+        boxes, cap, sc, k, found = held[0], self.cap, self.sched, len(held[1]), self.found
+        desc, rnd, n, masks = self._motion_front(issue, held)
         keep = torch.zeros(cap, dtype=torch.uint8, device=self.device)
         stream_cut(self.raw_ring, self.flow_ring, n, rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
                    rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, keep)
