@@ -129,6 +129,41 @@ def test_tick_descriptor_on_a_hand_made_tick():
     for items in ([], [(2, i2, crops2, blocks2), (0, i0, crops0, blocks0)], [(3, i2, crops2, blocks2)]):
         with pytest.raises(ValueError, match='ascending camera order'):
             tick_descriptor(lay, items)
+    # one camera: every round is the single-camera round -- n, 3 unused | crops [cap][4] | raw_win [T] | flow_win [Tf], padded to 4 |
+    # masks [hb*wb][cap] bytes -- and the header's tables hold the issue's pair and row.  No round, one full round, two rounds.
+    from vec_vad_amd.stream import RingSchedule
+    cap, hb, wb = 2, 1, 2
+    rs = RingSchedule(CFN, 4)
+    for _ in range(8):
+        _, issue = rs.push()
+    T, Tf = rs.T, rs.Tf
+    lay1 = TickLayout(1, cap, T, Tf, hb, wb)
+    w_mask = (4 + 4 * cap + T + Tf + 3) // 4 * 4
+    assert lay1.D == w_mask + (hb * wb * cap + 3) // 4
+    all_crops = np.array([[1, 2, 30, 40], [5, 6, 70, 80], [9, 10, 110, 120]], np.int32)
+    all_blocks = [[(0, 0)], [(0, 0), (0, 1)], []]
+    for n in (0, 2, 3):
+        crops, blocks = all_crops[:n], all_blocks[:n]
+        d, rounds, rows, used = tick_descriptor(lay1, [(0, issue, crops, blocks)])
+        assert rounds == (n + cap - 1) // cap and len(d) == lay1.words(rounds) and len(used) == rounds
+        assert tuple(d[lay1.h_pairs:lay1.h_rows]) == issue['pair_slots'] and d[lay1.h_rows] == issue['flow_slot']
+        for r in range(max(rounds, 1)):                      # no box: the words of one round are laid out, n = 0 and the windows in them
+            m = min(n, (r + 1) * cap) - r * cap
+            want = np.zeros(lay1.D, np.int32)
+            want[0] = m
+            want[4:4 + 4 * m] = crops[r * cap:r * cap + m].reshape(-1)
+            want[4 + 4 * cap:4 + 4 * cap + T] = issue['raw_slots']
+            want[4 + 4 * cap + T:4 + 4 * cap + T + Tf] = issue['flow_slots']
+            masks = want[w_mask:].view(np.uint8)
+            for b, cells in enumerate(blocks[r * cap:r * cap + m]):
+                for hh, ww in cells:
+                    masks[(hh * wb + ww) * cap + b] = 1
+            assert np.array_equal(d[lay1.head + r * lay1.D:lay1.head + (r + 1) * lay1.D], want), (n, r)
+        # fill_tick on a caller's zeroed buffer, as StreamFront calls it: the same words and lists, the words behind them untouched
+        from vec_vad_amd.stream_front import fill_tick
+        buf = np.zeros(len(d) + 5, np.int32)
+        assert fill_tick(lay1, [(0, issue, crops, blocks)], lay1.rounds([(0, issue, crops, blocks)]), buf) == (rows, used)
+        assert np.array_equal(buf, np.concatenate([d, np.zeros(5, np.int32)]))
 
 
 def test_camera_ticks_deals_videos_round_robin_and_ends_cameras_together():

@@ -178,3 +178,32 @@ def test_an_all_masked_frame_scores_minus_big():
         box, fs = stream_scores(raw, raw, STATS, 1.0, 1.0, np.array(keep, np.uint8), n, np.array(mask, np.uint8), np.full(4, 7.0), -BIG)
         assert fs == -BIG
         assert box.tolist() == ([-BIG] * 4 if n else [7.0] * 4)
+
+
+# ---- the cells of a frame's boxes ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('block_mode', [1, 5, 9])
+def test_box_cells_under_the_test_rule_and_the_training_rule(block_mode):
+    """``box_cells`` on hand-made boxes of a 96 x 144 mask in 48 x 48 cells: under the test rule the bits ``stream_boxes_restatement``
+    sets for the same boxes, under the training rule every cell of ``calc_block_idx``; a box outside the grid is refused by both."""
+    import stream_boxes_restatement as R
+    from utils import calc_block_idx
+    from vec_vad_amd.stream_front import box_cells
+    grid = dict(grid_h=96, grid_w=144, hb=2, wb=3)
+    boxes = np.array([[10, 10, 30, 30],       # well inside cell (0, 0)
+                      [-3, 5, 40, 40],        # x1 < 0: the slice wraps to nothing, the box paints no pixel; its probes lie in the grid
+                      [40, 4, 70, 20],        # centre x = 55 in column 1, left corner probe (40 + 55) / 2 = 47.5 in column 0: two cells
+                      [24, 8, 72, 48]],       # centre (28, 48): x exactly on the boundary of columns 0 and 1
+                     np.float64)
+    h_step, w_step = grid['grid_h'] / grid['hb'], grid['grid_w'] / grid['wb']
+    masks = R.stream_boxes(len(boxes), boxes, 0, len(boxes), 48, 72, block_mode=block_mode, **grid)[3]
+    want = [[(r // grid['wb'], r % grid['wb']) for r in np.nonzero(masks[:, b])[0]] for b in range(len(boxes))]
+    got = box_cells(boxes, h_step=h_step, w_step=w_step, block_mode=block_mode, painted_only=True, **grid)
+    assert got == want and got[1] == [] and got[0] == [(0, 0)]
+    assert (len(got[2]) == 2) == (block_mode > 1) and (0, 1) in got[3]
+    train = box_cells(boxes, h_step=h_step, w_step=w_step, block_mode=block_mode, painted_only=False, **grid)
+    assert train == [sorted(set(calc_block_idx(b[0], b[2], b[1], b[3], h_step, w_step, mode=block_mode))) for b in boxes]
+    assert train[1] != [] and [train[i] for i in (0, 2, 3)] == [got[i] for i in (0, 2, 3)]
+    outside = np.array([[10, 10, 30, 30], [100, 10, 200, 40]], np.float64)      # centre x = 150: column 3 of 3
+    for painted_only in (True, False):
+        with pytest.raises(IndexError, match='box 1 falls outside the 2x3 block grid'):
+            box_cells(outside, h_step=h_step, w_step=w_step, block_mode=block_mode, painted_only=painted_only, **grid)

@@ -4,7 +4,10 @@
 // score under a validity mask.  Both read the number of boxes, the crops, the window slots and the masks from device memory, so their
 // launch arguments never change from frame to frame (they can sit in a captured graph).  Both are small and latency-bound (5-30 boxes a
 // frame): the point is one launch each.  The arithmetic is that of vv_cube_cut / vv_cube_energy / vv_cube_scores, through the shared
-// headers: the same bits.  vv_stream_boxes is the third: for a scorer that finds its own motion boxes (vv_motion_mask + vv_mask_boxes leave
+// headers: the same bits.  Both kernels have a camera dimension (vec_vad_amd/multistream.py: camera k's frames in slots k*R .. of one raw
+// ring, its fields in slots k*Rf .. of one flow ring, its boxes in store slots k*cap ..), so that a tick of `cams` cameras is ONE launch
+// of each (vv_stream_cut_multi, vv_stream_scores_multi); the single-camera entry points are that launch at cams = 1.
+// vv_stream_boxes is the third: for a scorer that finds its own motion boxes (vv_motion_mask + vv_mask_boxes leave
 // them on the device) it forms the crops, the box count and the per-block masks the host forms for boxes it is given.  vv_stream_paint is
 // the fourth: the frame's box-score rows painted into its score mask, with the box count and the motion boxes still on the device.
 // vv_stream_tracks is the fifth: over the same tables, the frame's boxes linked to the tracks of the frames before, in one workgroup.
@@ -24,62 +27,72 @@ namespace {
 using namespace vv_resize;
 using namespace vv_score_fn;
 
-// One workgroup per store slot b; slots >= n leave at once and write nothing.  The flow cube is stored by the loop that sums its
-// squares (box_energy: the order and the bits of vv_cube_energy), then the raw cube is cut, thread j taking pixels j, j + 256, ... of
-// the [T][P][P] patch.  All boxes share the frame's two windows.
-__global__ void __launch_bounds__(256) stream_cut_kernel(const uint8_t* __restrict__ raw_ring, int R, const float* __restrict__ flow_ring,
-                                                         int Rf, int H, int W, int C, const int32_t* __restrict__ n_ptr,
+// One workgroup per (camera k, slot b) = store slot k*cap + b; slots at or above n[k] leave at once and write nothing.  The flow cube is
+// stored by the loop that sums its squares (box_energy: the order and the bits of vv_cube_energy), then the raw cube is cut, thread j
+// taking pixels j, j + 256, ... of the [T][P][P] patch.  A camera's boxes share its two windows; the window tables hold absolute ring
+// slots, clamped into the whole ring.  One camera (vv_stream_cut) is the grid (cap, 1).
+__global__ void __launch_bounds__(256) stream_cut_kernel(const uint8_t* __restrict__ raw_ring, int R_all, const float* __restrict__ flow_ring,
+                                                         int Rf_all, int H, int W, int C, const int32_t* __restrict__ n_ptr,
                                                          const int32_t* __restrict__ crops, const int32_t* __restrict__ raw_win,
                                                          const int32_t* __restrict__ flow_win, int cap, int T, int Tf, int P, double thr,
                                                          uint8_t* __restrict__ raw_store, float* __restrict__ flow_store,
                                                          uint8_t* __restrict__ keep, double* __restrict__ energy) {
   __shared__ double part[256];
-  const int b = blockIdx.x;
-  const int n = min(max(n_ptr[0], 0), cap);
+  const int b = blockIdx.x, k = blockIdx.y;
+  const int n = min(max(n_ptr[k], 0), cap);
   if (b >= n) return;                                    // the same for every thread of the workgroup
-  const int x_min = crops[4 * b + 0], y_min = crops[4 * b + 1], x_max = crops[4 * b + 2], y_max = crops[4 * b + 3];
-  if (!crop_ok(x_min, y_min, x_max, y_max, H, W)) {      // a wrong table (the wrapper refuses it): the box is dropped, nothing is read
+  const int64_t s = (int64_t)k * cap + b;                // the store slot
+  const int32_t* crop = crops + 4 * s;
+  const int x_min = crop[0], y_min = crop[1], x_max = crop[2], y_max = crop[3];
+  if (!crop_ok(x_min, y_min, x_max, y_max, H, W)) {      // a wrong table: the box is dropped, nothing is read
     if (threadIdx.x == 0) {
-      keep[b] = 0;
-      if (energy) energy[b] = 0.0;
+      keep[s] = 0;
+      if (energy) energy[s] = 0.0;
     }
     return;
   }
   const int64_t per_f = (int64_t)Tf * P * P, per_r = (int64_t)T * P * P;
-  const double e = box_energy(flow_ring, Rf, H, W, 2, x_min, y_min, x_max, y_max, flow_win, Tf, P, part, flow_store + b * per_f * 2);
+  const double e = box_energy(flow_ring, Rf_all, H, W, 2, x_min, y_min, x_max, y_max, flow_win + (int64_t)k * Tf, Tf, P, part,
+                              flow_store + s * per_f * 2);
   if (threadIdx.x == 0) {
-    keep[b] = e > thr ? 1 : 0;
-    if (energy) energy[b] = e;
+    keep[s] = e > thr ? 1 : 0;
+    if (energy) energy[s] = e;
   }
+  const int32_t* win = raw_win + (int64_t)k * T;
   for (int j = threadIdx.x; j < (int)per_r; j += 256) {
     const int dx = j % P, dy = (j / P) % P, t = j / (P * P);
-    const int f = min(max(raw_win[t], 0), R - 1);
+    const int f = min(max(win[t], 0), R_all - 1);
     const uint8_t* src = raw_ring + (((int64_t)f * H + y_min) * W + x_min) * C;
-    uint8_t* dst = raw_store + (b * per_r + j) * C;
+    uint8_t* dst = raw_store + (s * per_r + j) * C;
     resize_pixel(src, (int64_t)W * C, C, x_max - x_min, y_max - y_min, P, P, dy, dx, [dst](int c, uint8_t v) { dst[c] = v; });
   }
 }
 
-// One workgroup.  Box b counts iff b < n, keep[b] and mask[b]: only then is its error read at all, so whatever the padded slots of the
-// scoring launch, a dropped box or a box of another block hold (NaN, Inf) cannot reach the maximum.  A counted box gets the score of
-// vv_cube_scores (stats == nullptr: the block has no model, +big), another box below n gets -big, slots >= n are not written.  The
-// maximum of the counted scores meets in an LDS tree and is max-accumulated into the frame's cell (launches on one stream are ordered,
-// a cell has one writer at a time).
+// One workgroup per camera k, over slots k*cap .. of the scoring launch.  Box b counts iff b < n[k], keep and mask: only then is its
+// error read at all, so whatever the padded slots of the scoring launch, a dropped box or a box of another block hold (NaN, Inf) cannot
+// reach the maximum.  A counted box gets the score of vv_cube_scores (stats == nullptr: the block has no model, +big), another box below
+// n[k] gets -big, slots >= n[k] are not written.  The maximum of the counted scores meets in an LDS tree and is max-accumulated into the
+// camera's cell (launches on one stream are ordered, a cell has one writer at a time).  A camera with n[k] = 0 reads and writes nothing:
+// its cell keeps its value, as under fmax with -inf.  Cameras write disjoint rows and cells: no atomics.
 __global__ void __launch_bounds__(256) stream_scores_kernel(const float* __restrict__ raw, const float* __restrict__ of,
                                                             const double* __restrict__ stats, double w_raw, double w_of, double big,
                                                             const uint8_t* __restrict__ keep, const int32_t* __restrict__ n_ptr,
                                                             const uint8_t* __restrict__ mask, int cap, double* __restrict__ box_scores,
-                                                            double* __restrict__ frame_score) {
+                                                            int64_t box_stride, double* __restrict__ frame_score, int64_t frame_stride) {
   __shared__ double part[256];
-  const int n = min(max(n_ptr[0], 0), cap);
+  const int k = blockIdx.x;
+  const int n = min(max(n_ptr[k], 0), cap);
+  if (n == 0) return;                                    // the same for every thread: the camera's cell stays as it was
+  const int base = k * cap;                              // fits: the entry point refuses cams * cap > INT32_MAX
+  double* row = box_scores + (int64_t)k * box_stride;
   double best = -INFINITY;
   for (int b = threadIdx.x; b < n; b += 256) {
     double s = -big;
-    if (keep[b] && mask[b]) {
-      s = stats ? cube_score_row(raw, of, stats, w_raw, w_of, b) : big;
+    if (keep[base + b] && mask[base + b]) {
+      s = stats ? cube_score_row(raw, of, stats, w_raw, w_of, base + b) : big;
       best = fmax(best, s);
     }
-    box_scores[b] = s;
+    row[b] = s;
   }
   part[threadIdx.x] = best;
   __syncthreads();
@@ -87,7 +100,10 @@ __global__ void __launch_bounds__(256) stream_scores_kernel(const float* __restr
     if ((int)threadIdx.x < s) part[threadIdx.x] = fmax(part[threadIdx.x], part[threadIdx.x + s]);
     __syncthreads();
   }
-  if (threadIdx.x == 0) frame_score[0] = fmax(frame_score[0], part[0]);
+  if (threadIdx.x == 0) {
+    double* cell = frame_score + (int64_t)k * frame_stride;
+    cell[0] = fmax(cell[0], part[0]);
+  }
 }
 
 // Python's slice(a, b).indices(len)[:2] for step 1: a negative bound counts from the end, then both clip to [0, len].
@@ -619,28 +635,48 @@ extern "C" int vv_stream_boxes(const int32_t* count, const int32_t* boxes, int32
   return VV_OK;
 }
 
+extern "C" int vv_stream_cut_multi(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W,
+                                   int32_t C, int32_t cams, const int32_t* n, const int32_t* crops, const int32_t* raw_win,
+                                   const int32_t* flow_win, int32_t cap, int32_t T, int32_t Tf, int32_t P, double thr,
+                                   uint8_t* raw_store, float* flow_store, uint8_t* keep, double* energy, vv_stream stream) {
+  if (cams <= 0 || cams > 65535) return VV_ERR_BAD_ARG;                                 // a camera is a row of the launch grid
+  if (R <= 0 || Rf <= 0 || H <= 0 || W <= 0 || C <= 0 || cap < 0 || T <= 0 || Tf <= 0 || P <= 0 || P > 1024) return VV_ERR_BAD_ARG;
+  if ((int64_t)T * P * P > 0x7fffffff || (int64_t)Tf * P * P > 0x7fffffff) return VV_ERR_BAD_ARG;      // a box's patch is indexed with an int
+  if ((int64_t)cams * R > 0x7fffffff || (int64_t)cams * Rf > 0x7fffffff || (int64_t)cams * cap > 0x7fffffff) return VV_ERR_BAD_ARG;
+  if (cap == 0) return VV_OK;
+  if (!raw_ring || !flow_ring || !n || !crops || !raw_win || !flow_win || !raw_store || !flow_store || !keep) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_cut_kernel, dim3((unsigned)cap, (unsigned)cams), dim3(256), 0, (hipStream_t)stream, raw_ring, cams * R,
+            flow_ring, cams * Rf, H, W, C, n, crops, raw_win, flow_win, cap, T, Tf, P, thr, raw_store, flow_store, keep, energy);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+extern "C" int vv_stream_scores_multi(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
+                                      const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cams, int32_t cap,
+                                      double* box_scores, int64_t box_stride, double* frame_score, int64_t frame_stride,
+                                      vv_stream stream) {
+  if (cams <= 0 || cap < 0 || (int64_t)cams * cap > 0x7fffffff) return VV_ERR_BAD_ARG;
+  if (cap == 0) return VV_OK;
+  if (box_stride < cap || frame_stride < 1) return VV_ERR_BAD_ARG;                      // the cameras' rows and cells must not overlap
+  if (!keep || !n || !mask || !box_scores || !frame_score || (stats && !raw)) return VV_ERR_BAD_ARG;
+  VV_LAUNCH(stream_scores_kernel, dim3((unsigned)cams), dim3(256), 0, (hipStream_t)stream, raw, of, stats, w_raw, w_of, big, keep,
+            n, mask, cap, box_scores, box_stride, frame_score, frame_stride);
+  VV_CHECK_LAUNCH();
+  return VV_OK;
+}
+
+// One camera is the launch above at cams = 1, with the row and the cell of camera 0; no refusal of the multi entries can fire at
+// cams = 1 that is not one of these entries' own.
 extern "C" int vv_stream_cut(const uint8_t* raw_ring, int32_t R, const float* flow_ring, int32_t Rf, int32_t H, int32_t W, int32_t C,
                              const int32_t* n, const int32_t* crops, const int32_t* raw_win, const int32_t* flow_win, int32_t cap,
                              int32_t T, int32_t Tf, int32_t P, double thr, uint8_t* raw_store, float* flow_store, uint8_t* keep,
                              double* energy, vv_stream stream) {
-  if (R <= 0 || Rf <= 0 || H <= 0 || W <= 0 || C <= 0 || cap < 0 || T <= 0 || Tf <= 0 || P <= 0 || P > 1024) return VV_ERR_BAD_ARG;
-  if ((int64_t)T * P * P > 0x7fffffff || (int64_t)Tf * P * P > 0x7fffffff) return VV_ERR_BAD_ARG;      // a box's patch is indexed with an int
-  if (cap == 0) return VV_OK;
-  if (!raw_ring || !flow_ring || !n || !crops || !raw_win || !flow_win || !raw_store || !flow_store || !keep) return VV_ERR_BAD_ARG;
-  VV_LAUNCH(stream_cut_kernel, dim3((unsigned)cap), dim3(256), 0, (hipStream_t)stream, raw_ring, R, flow_ring, Rf, H, W, C, n, crops,
-            raw_win, flow_win, cap, T, Tf, P, thr, raw_store, flow_store, keep, energy);
-  VV_CHECK_LAUNCH();
-  return VV_OK;
+  return vv_stream_cut_multi(raw_ring, R, flow_ring, Rf, H, W, C, 1, n, crops, raw_win, flow_win, cap, T, Tf, P, thr, raw_store, flow_store,
+                             keep, energy, stream);
 }
 
 extern "C" int vv_stream_scores(const float* raw, const float* of, const double* stats, double w_raw, double w_of, double big,
                                 const uint8_t* keep, const int32_t* n, const uint8_t* mask, int32_t cap, double* box_scores,
                                 double* frame_score, vv_stream stream) {
-  if (cap < 0) return VV_ERR_BAD_ARG;
-  if (cap == 0) return VV_OK;
-  if (!keep || !n || !mask || !box_scores || !frame_score || (stats && !raw)) return VV_ERR_BAD_ARG;
-  VV_LAUNCH(stream_scores_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, raw, of, stats, w_raw, w_of, big, keep, n, mask, cap,
-            box_scores, frame_score);
-  VV_CHECK_LAUNCH();
-  return VV_OK;
+  return vv_stream_scores_multi(raw, of, stats, w_raw, w_of, big, keep, n, mask, 1, cap, box_scores, cap, frame_score, 1, stream);
 }

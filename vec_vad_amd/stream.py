@@ -80,103 +80,19 @@ rendering of the error mask, the pixel and region criteria of ``test.py``, and f
 Hungarian method, re-identification and ids drawn into the picture.  Several cameras in one scorer are
 ``vec_vad_amd.multistream.MultiStreamScorer`` (one frame shape and one model set, given boxes, scores only): the motion boxes, masks,
 smoothing, overlays, tracks and error maps described above stay features of this single-camera class.  The models and statistics a
-scorer is built from can come from pushed frames too: ``vec_vad_amd.stream_train.StreamCollector`` runs this front half (``check_frame``,
-``RingSchedule``, ``_flow``, ``_fill_round``, ``_motion_front``) in front of a training store.
+scorer is built from can come from pushed frames too (``vec_vad_amd.stream_train.StreamCollector``).  All three classes derive from
+``vec_vad_amd.stream_front.StreamFront``, which owns everything up to and including ``vv_stream_cut`` -- the refusals, rings and
+stores, ``RingSchedule``, the host side of a frame, the descriptor (``tick_descriptor`` at one camera, with the motion tables and this
+class's tail behind its first round), the flow and the motion front; the names that used to be defined here are re-imported from
+there.  This module holds what stands behind the cut: the score, paint, smooth, track and map stages and ``StreamResult``.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
-from .extract import boxes_to_crops
-from .scoring import BIG, box_paints
-
-
-def ring_frames(context_frame_num):
-    """Frames the raw ring holds: the ``context_frame_num + 1`` frames of the 'predict' window of the frame being issued, plus the
-    frame pushed behind it (the second frame of its flow pair)."""
-    return int(context_frame_num) + 2
-
-
-def motion_ring_frames(context_frame_num):
-    """Frames the raw ring holds when the scorer finds its own motion boxes: the motion window of the frame being issued is the frame
-    before it, the frame and the look-ahead frame, so never fewer than 3."""
-    return max(ring_frames(context_frame_num), 3)
-
-
-def flow_ring_frames(context_of_num):
-    """Flow fields the flow ring holds: the ``context_of_num + 1`` fields of the flow window of the frame being issued (its own field
-    is computed when it is issued, into the slot of the field that left the window)."""
-    return int(context_of_num) + 1
-
-
-def check_max_boxes(v):
-    """``stream_max_boxes`` as an integer >= 1, else a one-line ``ValueError``; no GPU is touched."""
-    if isinstance(v, str):
-        try:
-            v = int(v.strip())
-        except ValueError:
-            pass
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-        raise ValueError('[mi355x] stream_max_boxes must be an integer >= 1, got {!r}'.format(v))
-    return int(v)
-
-
-def check_stream_boxes(v):
-    """``stream_boxes`` as ``'given'`` or ``'motion'``, else a one-line ``ValueError``; no GPU is touched."""
-    w = v.strip().lower() if isinstance(v, str) else v
-    if w not in ('given', 'motion'):
-        raise ValueError("[mi355x] stream_boxes must be 'given' or 'motion', got {!r}".format(v))
-    return w
-
-
-def _dev(name, t, dtype, numel=None):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() < numel):
-        raise ValueError('{} must be a contiguous CUDA {} tensor{}'.format(name, dtype, '' if numel is None else ' of at least %d elements' % numel))
-    return t
-
-
-def check_frame(frame_u8, boxes, H, W, C):
-    """What ``push`` is handed, checked on the host: the frame as a uint8 ``[H,W,C]`` array (a ``[H,W]`` one passes for ``C`` = 1) and
-    the first four columns of its boxes as float64 ``[n,4]``; a frame of another type or shape is a one-line ``ValueError``."""
-    frame = np.asarray(frame_u8)
-    if frame.ndim == 2 and C == 1:
-        frame = frame[:, :, None]
-    if frame.dtype != np.uint8 or tuple(frame.shape) != (H, W, C):
-        raise ValueError('push takes uint8 frames of shape {}, got {} {}'.format((H, W, C), frame.dtype, tuple(frame.shape)))
-    boxes = np.asarray(boxes, np.float64)
-    boxes = boxes.reshape(-1, boxes.shape[-1])[:, :4] if boxes.ndim == 2 and boxes.shape[0] else np.zeros((0, 4), np.float64)
-    return frame, boxes
-
-
-def stream_cut(raw_ring, flow_ring, n, crops, raw_win, flow_win, thr, raw_store, flow_store, keep, energy=None):
-    """``vv_stream_cut``: the cubes of the ``n[0]`` boxes of one frame from the two rings into slots ``0..n-1`` of a fixed store, and the
-    motion test.  raw_ring uint8 ``[R,H,W,C]``, flow_ring float32 ``[Rf,H,W,2]``; the tables are DEVICE tensors that the kernel reads
-    (int32: ``n`` ``[1]``, ``crops`` ``[cap,4]`` as ``boxes_to_crops`` forms them, ``raw_win`` ``[T]`` and ``flow_win`` ``[Tf]`` ring
-    slots), so nothing here looks at their values; raw_store uint8 ``[cap,T,P,P,C]``, flow_store float32 ``[cap,Tf,P,P,2]``, keep uint8
-    ``[cap]``, energy float64 ``[cap]`` or None.  Written: slots below ``n[0]`` -- the bytes of ``extract.cube_cut`` and the values of
-    ``extract.cube_energy`` for the same frames, crops and windows; everything else keeps what it holds."""
-    _dev('raw_ring', raw_ring, torch.uint8), _dev('flow_ring', flow_ring, torch.float32)
-    if raw_ring.dim() != 4 or flow_ring.dim() != 4 or tuple(flow_ring.shape[1:]) != tuple(raw_ring.shape[1:3]) + (2,):
-        raise ValueError('the rings must be [R,H,W,C] frames and [Rf,H,W,2] flow fields of one frame size')
-    R, H, W, C = raw_ring.shape
-    _dev('raw_store', raw_store, torch.uint8), _dev('flow_store', flow_store, torch.float32)
-    if raw_store.dim() != 5 or flow_store.dim() != 5:
-        raise ValueError('the stores must be [cap,T,P,P,C] and [cap,Tf,P,P,2] tensors')
-    cap, T, P = raw_store.shape[0], raw_store.shape[1], raw_store.shape[2]
-    Tf = flow_store.shape[1]
-    if tuple(raw_store.shape) != (cap, T, P, P, C) or tuple(flow_store.shape) != (cap, Tf, P, P, 2):
-        raise ValueError('the stores must be [cap,T,P,P,%d] and [cap,Tf,P,P,2] tensors of one cap and P' % C)
-    _dev('n', n, torch.int32, 1), _dev('crops', crops, torch.int32, 4 * cap)
-    _dev('raw_win', raw_win, torch.int32, T), _dev('flow_win', flow_win, torch.int32, Tf), _dev('keep', keep, torch.uint8, cap)
-    if energy is not None:
-        _dev('energy', energy, torch.float64, cap)
-    _lib.check(_lib.lib().vv_stream_cut(raw_ring.data_ptr(), R, flow_ring.data_ptr(), flow_ring.shape[0], H, W, C, n.data_ptr(),
-                                        crops.data_ptr(), raw_win.data_ptr(), flow_win.data_ptr(), cap, T, Tf, P, float(thr),
-                                        raw_store.data_ptr(), flow_store.data_ptr(), keep.data_ptr(),
-                                        energy.data_ptr() if energy is not None else None,
-                                        torch.cuda.current_stream(raw_ring.device).cuda_stream), 'vv_stream_cut')
+from .scoring import BIG
+from .stream_front import (RingSchedule, StreamFront, _Staging, _dev, check_frame, check_max_boxes, check_stream_boxes,  # noqa: F401
+                           flow_ring_frames, motion_ring_frames, ring_frames, stream_boxes, stream_cut)
 
 
 def stream_scores(raw, of, stats, w_raw, w_of, keep, n, mask, box_scores, frame_score):
@@ -199,25 +115,6 @@ def stream_scores(raw, of, stats, w_raw, w_of, keep, n, mask, box_scores, frame_
                                            keep.data_ptr(), n.data_ptr(), mask.data_ptr(), cap, box_scores.data_ptr(),
                                            frame_score.data_ptr(), torch.cuda.current_stream(box_scores.device).cuda_stream),
                'vv_stream_scores')
-
-
-def stream_boxes(count, boxes, n_ap, H, W, grid_h, grid_w, hb, wb, h_step, w_step, block_mode, n, dropped, crops, masks, boxes_out):
-    """``vv_stream_boxes``: what ``StreamScorer._prepare`` forms on the host, for motion boxes that exist only on the device.  count
-    int32 ``[1]`` and boxes int32 ``[mcap,4]`` as ``vv_mask_boxes`` leaves them for one window; ``n_ap``: slots ``0..n_ap-1`` of the
-    tables hold the host's appearance boxes and are not touched.  Written in place, all on the device: n int32 ``[1]`` = ``n_ap + m``
-    with ``m = min(count, mcap, cap - n_ap)``; dropped int32 ``[1]`` = ``count - m``; crops int32 ``[cap,4]`` (``boxes_to_crops``) and
-    boxes_out int32 ``[cap,4]`` in slots ``n_ap..n-1``; masks uint8 ``[hb*wb,cap]``: columns ``n_ap..cap-1`` get 1 in the cells of
-    ``utils.calc_block_idx`` of a box that paints a pixel of the ``grid_h x grid_w`` mask (``scoring.box_paints``), else 0."""
-    _dev('count', count, torch.int32, 1), _dev('boxes', boxes, torch.int32)
-    if boxes.dim() != 2 or boxes.shape[1] != 4 or crops.dim() != 2 or crops.shape[1] != 4:
-        raise ValueError('boxes and crops must be [mcap,4] and [cap,4] tensors')
-    cap = crops.shape[0]
-    _dev('crops', crops, torch.int32), _dev('boxes_out', boxes_out, torch.int32, 4 * cap), _dev('n', n, torch.int32, 1)
-    _dev('dropped', dropped, torch.int32, 1), _dev('masks', masks, torch.uint8, int(hb) * int(wb) * cap)
-    _lib.check(_lib.lib().vv_stream_boxes(count.data_ptr(), boxes.data_ptr(), boxes.shape[0], int(n_ap), cap, int(H), int(W), int(grid_h),
-                                          int(grid_w), int(hb), int(wb), float(h_step), float(w_step), int(block_mode), n.data_ptr(),
-                                          dropped.data_ptr(), crops.data_ptr(), masks.data_ptr(), boxes_out.data_ptr(),
-                                          torch.cuda.current_stream(crops.device).cuda_stream), 'vv_stream_boxes')
 
 
 PAINT_STAGE = 256      # boxes ``vv_stream_paint`` stages in LDS per pass (VV_STREAM_PAINT_STAGE)
@@ -375,52 +272,6 @@ def check_pixel_settings(c, masks, smooth, render, frame_hw, grid_hw):
     return masks, smooth, render, int(kt), int(ks), source, bool(c.get('render_boxes', True)), lo, hi, alpha
 
 
-class RingSchedule:
-    """The ring bookkeeping of one camera, pure (no GPU).  ``push()`` -> ``(slot, issue | None)``: the raw ring slot the new frame goes
-    into, and the frame that can now be issued (the previous frame of the video).  ``end_video()`` -> the issue of the video's last
-    frame (None for a video without frames; ``ValueError`` for a video of one frame), after which the next push starts a video.
-
-    An issue is a dict with video-local frame numbers and ring slots: ``frame``; ``raw_frames`` / ``raw_slots`` (the raw window);
-    ``flow_frames`` / ``flow_slots`` (the flow window); ``pair_frames`` / ``pair_slots`` (the two frames FlowNet2 sees for the flow of
-    ``frame``) and ``flow_slot`` (where that flow is written before the window is read); ``motion_frames`` / ``motion_slots`` (the
-    three-frame window of the motion stage, ``context_range(i, 'hard', 1)``: the frame between its two neighbours, itself in place of
-    a neighbour the video does not have).  Frame ``k`` of a video lives in raw slot ``k % R``, its flow in flow slot ``k % Rf``.
-    ``motion``: the raw ring holds ``motion_ring_frames`` frames, never fewer than the three of the motion window; without it the
-    motion slots mean something only where ``ring_frames`` is 3 or more already.  ``mask_frames`` = K, the slots of the score-mask ring
-    (the trailing smoothing window in frames; 1 without smoothing): ``mask_slot`` = ``frame % K`` is where the issued frame's mask
-    goes, ``mask_frames`` / ``mask_slots`` the frames ``max(0, frame - K + 1) .. frame`` of the video and their slots, ascending.
-    ``reset``: the issue is the first of its video (what a tracker frees its table for)."""
-
-    def __init__(self, context_frame_num=4, context_of_num=0, motion=False, mask_frames=1):
-        self.T, self.Tf, self.K = int(context_frame_num) + 1, int(context_of_num) + 1, int(mask_frames)
-        self.R = motion_ring_frames(context_frame_num) if motion else ring_frames(context_frame_num)
-        self.Rf = flow_ring_frames(context_of_num)
-        self.count = 0            # frames of the current video pushed so far
-
-    def _issue(self, t, last):
-        raw = [max(t - self.T + 1 + i, 0) for i in range(self.T)]            # 'predict': up to and including t, first frame repeated
-        flow = [max(t - self.Tf + 1 + i, 0) for i in range(self.Tf)]
-        pair = (t - 1, t) if last else ((t, t) if t == 0 else (t, t + 1))     # calc_optical_flow.flow_pairs
-        motion = (max(t - 1, 0), t, t if last else t + 1)                     # 'hard' at one frame of context: clipped to the video
-        trail = list(range(max(0, t - self.K + 1), t + 1))                    # the trailing window of the mask smoothing
-        return dict(frame=t, reset=t == 0, mask_slot=t % self.K, mask_frames=trail, mask_slots=[f % self.K for f in trail], raw_frames=raw, raw_slots=[f % self.R for f in raw], flow_frames=flow,
-                    flow_slots=[f % self.Rf for f in flow], pair_frames=pair, pair_slots=(pair[0] % self.R, pair[1] % self.R),
-                    flow_slot=t % self.Rf, motion_frames=motion, motion_slots=tuple(f % self.R for f in motion))
-
-    def push(self):
-        k = self.count
-        self.count += 1
-        return k % self.R, (self._issue(k - 1, False) if k >= 1 else None)
-
-    def end_video(self):
-        k, self.count = self.count, 0
-        if k == 0:
-            return None
-        if k == 1:
-            raise ValueError('a video that ends after one frame cannot be scored: the flow of a frame needs a second frame of its video')
-        return self._issue(k - 1, True)
-
-
 class StreamResult:
     """The scores of one frame, on their way to the host.  ``frame``: the running index of the frame (pushes are counted from 0 across
     videos).  ``wait()`` blocks until the frame's copy has landed and returns ``(score, box_scores, kept)``: the frame score (float64;
@@ -501,42 +352,7 @@ class StreamResult:
         return float(a[0]), box.copy(), self._host_keep.numpy()[:n].astype(bool)
 
 
-class _Staging:
-    """Pinned host buffers for uploads that are still in flight when the host moves on: a buffer is handed out again only once the
-    event recorded behind its last copy has completed (asked, never waited for); otherwise a new one is made."""
-
-    def __init__(self):
-        self.items = {}
-
-    def get(self, key, shape, dtype):
-        pool = self.items.setdefault((key, tuple(shape), dtype), [])
-        for it in pool:
-            if it[1] is None or it[1].query():
-                it[1] = None
-                return it
-        it = [torch.empty(tuple(shape), dtype=dtype, pin_memory=True), None]
-        pool.append(it)
-        return it
-
-    def hold(self, key, shape, dtype):
-        """A buffer for a read-back: it stays out of the pool until its reader (``StreamResult``) hands it back."""
-        it = self.get(key, shape, dtype)
-        it[1] = _HELD
-        return it
-
-
-class _Held:
-    """In place of an event on a pooled buffer that a ``StreamResult`` still has to read: never 'completed'."""
-
-    @staticmethod
-    def query():
-        return False
-
-
-_HELD = _Held()
-
-
-class StreamScorer:
+class StreamScorer(StreamFront):
     """``StreamScorer(c, net_set, stats_raw, stats_of, frame_shape, flownet2=None, scene=None, max_boxes=None, device='cuda', boxes=None,
     masks=None, smooth=None, render=None, tracks=None, maps=None)``.
 
@@ -585,89 +401,18 @@ class StreamScorer:
                  boxes=None, masks=None, smooth=None, render=None, tracks=None, maps=None):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
         self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
+        self._refuse(c, frame_shape)
         from vad_datasets import frame_size
-        from vec_vad_amd.motion import CONSTANTS
-        from vec_vad_amd.trainer import FusedTrainer
         cp, ds, method = c['cp'], c['dataset_name'], c['method']
-        if self.motion and ds not in CONSTANTS:
-            raise ValueError("stream_boxes = motion: the motion stage has no constants for dataset {!r}".format(ds))
-        if cp.get(method, 'border_mode') != 'predict':
-            raise ValueError("a stream scores with border_mode = predict only (a centred window needs frames that have not arrived), got "
-                             "{!r}".format(cp.get(method, 'border_mode')))
-        H, W, C = (int(v) for v in frame_shape)
-        if C not in (1, 3):
-            raise ValueError('frames must have 1 or 3 channels, got frame_shape {!r}'.format(tuple(frame_shape)))
-        self.H, self.W, self.C = H, W, C
         (self.masks, self.smooth, self.render, self.kt, self.ks, self.render_source, self.render_boxes, self.render_lo, self.render_hi,
-         self.render_alpha) = check_pixel_settings(c, masks, smooth, render, (H, W), frame_size[ds][:2])      # before any GPU work
+         self.render_alpha) = check_pixel_settings(c, masks, smooth, render, (self.H, self.W), frame_size[ds][:2])      # before any GPU work
         self.tracks, self.trk_iou, self.trk_age, self.trk_window, self.trk_hits, self.trk_max = check_track_settings(c, tracks)
         self.maps = bool(c.get('stream_maps', False) if maps is None else maps)
         self.tail = self.masks or self.tracks or self.maps      # the stages that read the descriptor's tail
-        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion,
-                                  mask_frames=self.kt if self.smooth else 1)
-        self.P = cp.getint(ds, 'patch_size')
-        self.thr = cp.getfloat(ds, 'motionThr')
-        self.hb, self.wb = c['h_block'], c['w_block']
-        self.grid_h, self.grid_w = frame_size[ds][0], frame_size[ds][1]
-        if self.motion and (H > self.grid_h or W > self.grid_w):
-            raise ValueError('stream_boxes = motion: {}x{} frames are larger than the nominal {}x{} frame of {}, so a motion box could '
-                             'fall outside the block grid'.format(H, W, self.grid_h, self.grid_w, ds))
-        self.h_step, self.w_step = self.grid_h / self.hb, self.grid_w / self.wb
-        self.block_mode = cp.getint(ds, 'test_block_mode')
-        self.w_raw, self.w_of, self.use_flow = float(c['w_raw']), float(c['w_of']), bool(c['useFlow'])
-        dev = torch.device(device)
-        self.device = dev = dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
-        if flownet2 is None:
-            from calc_optical_flow import load_flownet2
-            flownet2 = load_flownet2(c['flownet2_checkpoint'], device=dev, fp16=c['direct_flow_fp16'])
-        from calc_optical_flow import FLOW_H, FLOW_W
-        self.flow_h, self.flow_w = FLOW_H, FLOW_W
-        self.flow_in, self.flow_out, self.flow_graph = flownet2.graph_entry((1, 3, 2, FLOW_H, FLOW_W))
-        self.flownet2 = flownet2
-        sc, cap, P = self.sched, self.cap, self.P
-        self.raw_ring = torch.zeros((sc.R, H, W, C), dtype=torch.uint8, device=dev)
-        self.flow_ring = torch.zeros((sc.Rf, H, W, 2), dtype=torch.float32, device=dev)
-        self.store_raw = torch.zeros((cap, sc.T, P, P, C), dtype=torch.uint8, device=dev)
-        self.store_flow = torch.zeros((cap, sc.Tf, P, P, 2), dtype=torch.float32, device=dev)
-        self.idx = torch.arange(cap, dtype=torch.long, device=dev)
-        # per block of the grid: (trainer, device statistics) or None for a block without a model -- built as test._group_scorer does
-        nets = net_set[scene] if scene is not None else net_set
-        s_raw = stats_raw[scene] if scene is not None else stats_raw
-        s_of = stats_of[scene] if scene is not None else stats_of
-        trainers, self.blocks = {}, {}
-        for hh in range(self.hb):
-            for ww in range(self.wb):
-                models = nets[hh][ww]
-                if len(models) == 0:
-                    self.blocks[(hh, ww)] = None
-                    continue
-                net = models[0]
-                if id(net) not in trainers:
-                    trainers[id(net)] = FusedTrainer(net)
-                st_r = s_raw[hh][ww]
-                st_o = s_of[hh][ww] if self.use_flow else (0.0, 1.0)
-                stats = torch.from_numpy(np.array([st_r[0], st_r[1], st_o[0], st_o[1]], np.float64)).to(dev)
-                self.blocks[(hh, ww)] = (trainers[id(net)], stats)
-        # descriptor of one round, in int32 words: n, 3 unused | crops [cap][4] | raw window [T] | flow window [Tf] | masks [hb*wb][cap] bytes
-        self.w_crops = 4
-        self.w_rwin = self.w_crops + 4 * cap
-        self.w_fwin = self.w_rwin + sc.T
-        self.w_mask = (self.w_fwin + sc.Tf + 3) // 4 * 4
-        self.D = self.w_mask + (self.hb * self.wb * cap + 3) // 4
-        self.desc = torch.zeros(4 + self.D, dtype=torch.int32, device=dev)      # header: pair (2), flow row, rounds; grows with the rounds
-        if self.motion:
-            # behind the one round of a frame: motion window [3], 1 unused | appearance table [cap][5] = window 0, x1, y1, x2, y2
-            self.w_mwin = 4 + self.D
-            self.w_ap = self.w_mwin + 4
-            self.words_motion = self.w_ap + 5 * cap
-            self.desc = torch.zeros(self.words_motion, dtype=torch.int32, device=dev)
-            self.mt = CONSTANTS[ds]
-            lib = _lib.lib()
-            self.mt_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
-            self.mt_work = torch.empty((lib.vv_mask_boxes_workspace_bytes(1, H, W),), dtype=torch.uint8, device=dev)
-            self.mt_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.mt_boxes = torch.zeros((cap, 4), dtype=torch.int32, device=dev)                          # mcap = cap
-            self.found = torch.zeros((2 + 4 * cap,), dtype=torch.int32, device=dev)                       # n, dropped, boxes_out [cap][4]
+        super().__init__(c, RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion,
+                                         mask_frames=self.kt if self.smooth else 1), flownet2, device)
+        self._block_table(c, net_set, stats_raw, stats_of, scene)
+        dev = self.device
         if self.tail:
             self._init_tail()
         if self.masks:
@@ -677,15 +422,9 @@ class StreamScorer:
         if self.maps:                         # the frame's error mask: every block's vv_stream_zpaint of every round accumulates into it
             self.zmask = torch.empty((self.grid_h, self.grid_w), dtype=torch.float64, device=dev)
             self.zfirst = True                # the frame being issued has had no vv_stream_zpaint launch yet
-        self.staging = _Staging()
         self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
-        # warm-up: every engine runs its eager launches and captures its graph here, so that push only replays
-        for ent in self.blocks.values():
-            if ent is not None:
-                for _ in range(3):
-                    ent[0].score_cubes(self.store_raw, self.store_flow, self.idx, maps=self.maps)
-        torch.cuda.synchronize(dev)
+        self._warm_blocks(self.maps)
 
     def _init_tail(self):
         """Behind the descriptor, for the stages that read the frame's box count and rectangles (pixels, tracks, maps): the tail ``n, 3 unused |
@@ -697,7 +436,7 @@ class StreamScorer:
             self.t_base = (self.words_motion + 3) // 4 * 4
             self.desc = torch.zeros(self.t_base + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
         else:                                 # room for one round and its tail from the start; more rounds grow it as before
-            self.desc = torch.zeros((4 + self.D + 3) // 4 * 4 + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
+            self.desc = torch.zeros((self.lay.words(1) + 3) // 4 * 4 + self.t_rects + 4 * self.cap, dtype=torch.int32, device=dev)
 
     def _init_pixels(self):
         """The device state of the pixel-level stages, allocated once: the mask ring (``smooth_frames`` slots, 1 without smoothing),
@@ -786,52 +525,11 @@ class StreamScorer:
         """The scorer of a configuration: the artifacts ``train.py`` wrote under ``<data_root_dir>/<modality>/`` are loaded as ``test.py``
         loads them.  ``frame_shape`` None: the dataset's nominal frame size with 3 channels.  A bad ``stream_max_boxes`` raises before
         any GPU work."""
-        from train import build_network, read_config
-        c = read_config(config_path)
-        from test import load_artifacts
-        from vad_datasets import frame_size
-        ds = c['dataset_name']
-        device = torch.device('cuda', torch.cuda.current_device())
-        base = os.path.join(c['data_root_dir'], c['modality'], ds + '_')
-        net_set, st_r, st_o = load_artifacts(base, c['mode_fg'], c['method'], ds == 'ShanghaiTech', lambda: build_network(c), device,
-                                             c['h_block'], c['w_block'])
-        if frame_shape is None:
-            frame_shape = (frame_size[ds][0], frame_size[ds][1], 3)
+        c, net_set, st_r, st_o, frame_shape, device = cls.load(config_path, frame_shape)
         return cls(c, net_set, st_r, st_o, frame_shape, flownet2=flownet2, scene=scene, device=device)
 
-    # ---- host side of a frame: everything that can be refused is refused before a ring is touched
-    def _prepare(self, frame_u8, boxes):
-        from utils import calc_block_idx
-        frame, boxes = check_frame(frame_u8, boxes, self.H, self.W, self.C)
-        ap = None
-        if self.motion:                                   # the given boxes are the frame's appearance boxes: one round holds them all
-            from .motion import _ap_table
-            if len(boxes) > self.cap:
-                raise ValueError('{} appearance boxes, stream_max_boxes holds {} (with stream_boxes = motion a frame is one '
-                                 'round)'.format(len(boxes), self.cap))
-            ap = _ap_table([boxes], 1)                    # what vv_motion_mask erases: truncated to int32, x2 < 0 refused
-        crops = boxes_to_crops(boxes, self.H, self.W)
-        paints = box_paints(boxes, self.grid_h, self.grid_w)
-        blocks = []
-        for b, bb in enumerate(boxes):
-            cells = calc_block_idx(bb[0], bb[2], bb[1], bb[3], self.h_step, self.w_step, mode=self.block_mode)
-            if any(not (0 <= hi < self.hb and 0 <= wi < self.wb) for hi, wi in cells):
-                raise IndexError('box {} falls outside the {}x{} block grid'.format(b, self.hb, self.wb))
-            blocks.append(sorted(cells) if paints[b] else [])
-        return frame, (boxes, crops, blocks, ap)
-
     def push(self, frame_u8, boxes=None, ap_boxes=None):
-        if self.motion:
-            boxes = ap_boxes if ap_boxes is not None else (boxes if boxes is not None else np.zeros((0, 4), np.float64))
-        elif boxes is None or ap_boxes is not None:
-            raise ValueError('push takes the frame and its boxes; ap_boxes and a push without boxes belong to stream_boxes = motion')
-        frame, held = self._prepare(frame_u8, boxes)
-        slot, issue = self.sched.push()
-        st = self.staging.get('frame', frame.shape, torch.uint8)
-        st[0].numpy()[...] = frame
-        self.raw_ring[slot].copy_(st[0], non_blocking=True)
-        st[1] = torch.cuda.Event()
-        st[1].record()
+        issue, held = self._take(frame_u8, boxes, ap_boxes)
         out = [self._issue(issue, self.held)] if issue is not None else []
         self.held = held
         self.frames += 1
@@ -841,15 +539,6 @@ class StreamScorer:
         held, self.held = self.held, None
         issue = self.sched.end_video()
         return [self._issue(issue, held)] if issue is not None else []
-
-    def _flow(self, base, stream):
-        """The flow field of the issued frame, in place in the flow ring: the launches of ``calc_optical_flow.chunk_flows`` at one pair."""
-        lib, sc = _lib.lib(), self.sched
-        _lib.check(lib.vv_flow_pairs_prep(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base, 1, self.flow_h, self.flow_w,
-                                          self.flow_in.data_ptr(), stream), 'vv_flow_pairs_prep')
-        self.flow_graph.replay()
-        _lib.check(lib.vv_flow_resize_back(self.flow_out.data_ptr(), 1, self.flow_h, self.flow_w, base + 8, self.H, self.W,
-                                           self.flow_ring.data_ptr(), sc.Rf, stream), 'vv_flow_resize_back')
 
     def _score_block(self, cell, keep, n, masks, box_scores, frame_score, zp=None):
         """One block's share of a round: its model scores the whole store in its own fixed-size launch (no launch for a block without a
@@ -898,48 +587,28 @@ class StreamScorer:
         if self.motion:
             return self._issue_motion(issue, held)
         boxes, crops, blocks, _ = held
-        cap, sc, D = self.cap, self.sched, self.D
+        cap, lay = self.cap, self.lay
         n = len(crops)
         rounds = (n + cap - 1) // cap
-        words = 4 + max(rounds, 1) * D
+        width = rounds * cap
+        words = lay.words(rounds)
         t_base = (words + 3) // 4 * 4                                          # the tail of the pixel-level stages, 16-byte aligned
         if self.tail:
-            words = t_base + self.t_rects + 4 * max(rounds * cap, 1)
-        if self.desc.numel() < words:
-            self.desc = torch.zeros(words, dtype=torch.int32, device=self.device)
-        st = self.staging.get('desc', (words,), torch.int32)
-        d = st[0].numpy()
-        d[:] = 0
-        d[0:2] = issue['pair_slots']
-        d[2] = issue['flow_slot']
-        d[3] = rounds
-        rows = sorted({cell for cells in blocks for cell in cells})          # the blocks this frame's boxes belong to
-        used = []                                                              # per round: the rows with a box of that round
-        for r in range(rounds):
-            o = 4 + r * D
-            lo, hi = r * cap, min(n, (r + 1) * cap)
-            here = self._fill_round(d[o:o + D], issue, crops[lo:hi], blocks[lo:hi])
-            used.append([i for i, cell in enumerate(rows) if cell in here])
+            words = t_base + self.t_rects + 4 * max(width, 1)
+        st, d, _, rows, used = self._describe([(0, issue, crops, blocks)], words - lay.words(rounds))  # rows: the blocks of the frame's boxes
         if self.tail:
             self._fill_tail(d[t_base:], issue, n, boxes)
-        desc = self.desc
-        desc[:words].copy_(st[0], non_blocking=True)
-        st[1] = torch.cuda.Event()
-        st[1].record()
-        self._flow(desc.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        width = rounds * cap
+        desc = self._start(st)
         out = torch.full((1 + len(rows) * width,), -float(BIG), dtype=torch.float64, device=self.device)
         keep = torch.zeros(max(width, 1), dtype=torch.uint8, device=self.device)
         tail = desc[t_base:words] if self.tail else None
         zrects = tail[self.t_rects:self.t_rects + 4 * max(width, 1)] if self.maps else None
         for r in range(rounds):
-            o = 4 + r * D
-            rnd, k = desc[o:o + D], keep[r * cap:(r + 1) * cap]
-            masks = rnd[self.w_mask:].view(torch.uint8)
-            stream_cut(self.raw_ring, self.flow_ring, rnd[0:1], rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
-                       rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, k)
+            rnd, n_dev, masks = self._round(desc, r)
+            k = keep[r * cap:(r + 1) * cap]
+            self._cut(rnd, n_dev, k)
             for i in used[r]:
-                self._score_block(rows[i], k, rnd[0:1], masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1],
+                self._score_block(rows[i], k, n_dev, masks, out[1 + i * width + r * cap:1 + i * width + (r + 1) * cap], out[0:1],
                                   (r * cap, zrects, n, None))
         pixels, trk = None, []
         if self.tail:
@@ -953,68 +622,14 @@ class StreamScorer:
         return StreamResult(self.frames - 1, n, len(rows), width, host, host_keep, event, boxes, pixels=pixels,
                             tracks=(host_trk[0], self.trk_max, width) if host_trk else None)
 
-    def _fill_round(self, d, issue, crops, blocks):
-        """One round of the descriptor on the host: the number of boxes, their crops, the two windows and the mask rows.  Returns the set
-        of blocks with a box of the round."""
-        sc, cap = self.sched, self.cap
-        d[0] = len(crops)
-        d[self.w_crops:self.w_crops + 4 * len(crops)] = crops.reshape(-1)
-        d[self.w_rwin:self.w_rwin + sc.T] = issue['raw_slots']
-        d[self.w_fwin:self.w_fwin + sc.Tf] = issue['flow_slots']
-        masks = d[self.w_mask:self.D].view(np.uint8)
-        here = set()
-        for b, cells in enumerate(blocks):
-            for (hh, ww) in cells:
-                masks[(hh * self.wb + ww) * cap + b] = 1
-                here.add((hh, ww))
-        return here
-
-    def _motion_front(self, issue, held):
-        """The front half of a frame whose motion boxes the device finds, up to the tables ``vv_stream_cut`` reads: the descriptor of
-        the ONE round (the appearance boxes in slots ``0..k-1`` as ``_issue`` files them), the flow, and ``vv_motion_mask`` ->
-        ``vv_mask_boxes`` -> ``vv_stream_boxes``, which files the motion boxes behind them.  Returns ``(desc, rnd, n, masks)``: the
-        descriptor and its round on the device, the box count on the device and the ``[hb*wb][cap]`` mask rows."""
-        boxes, crops, blocks, ap = held
-        lib, cap, sc, D, k = _lib.lib(), self.cap, self.sched, self.D, len(held[1])
-        st = self.staging.get('desc', (self.desc.numel(),), torch.int32)
-        d = st[0].numpy()
-        d[:] = 0
-        d[0:2] = issue['pair_slots']
-        d[2] = issue['flow_slot']
-        d[3] = 1
-        self._fill_round(d[4:4 + D], issue, crops, blocks)
-        d[self.w_mwin:self.w_mwin + 3] = issue['motion_slots']
-        d[self.w_ap:self.w_ap + 5 * len(ap)] = ap.reshape(-1)
-        if self.tail:                         # the count is the device's (found[0]); the appearance boxes' rectangles are the host's
-            self._fill_tail(d[self.t_base:], issue, k, boxes)
-        desc = self.desc
-        desc.copy_(st[0], non_blocking=True)
-        st[1] = torch.cuda.Event()
-        st[1].record()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        base = desc.data_ptr()
-        self._flow(base, stream)
-        c = self.mt
-        _lib.check(lib.vv_motion_mask(self.raw_ring.data_ptr(), sc.R, self.H, self.W, self.C, base + 4 * self.w_mwin, 1, c['ksize'],
-                                      c['binary_thr'], base + 4 * self.w_ap if len(ap) else None, len(ap), c['extend'],
-                                      self.mt_mask.data_ptr(), stream), 'vv_motion_mask')
-        _lib.check(lib.vv_mask_boxes(self.mt_mask.data_ptr(), 1, self.H, self.W, c['area_thr'], c['extend'], cap, self.mt_work.data_ptr(),
-                                     self.mt_work.numel(), self.mt_count.data_ptr(), self.mt_boxes.data_ptr(), stream), 'vv_mask_boxes')
-        rnd, found = desc[4:4 + D], self.found
-        n, masks = found[0:1], rnd[self.w_mask:].view(torch.uint8)
-        stream_boxes(self.mt_count, self.mt_boxes, k, self.H, self.W, self.grid_h, self.grid_w, self.hb, self.wb, self.h_step, self.w_step,
-                     self.block_mode, n, found[1:2], rnd[self.w_crops:self.w_rwin].view(cap, 4), masks, found[2:])
-        return desc, rnd, n, masks
-
     def _issue_motion(self, issue, held):
         """A frame whose motion boxes the device finds: ONE round, the appearance boxes in slots ``0..k-1`` as ``_issue`` files them, the
         motion boxes behind them by ``vv_stream_boxes``, and every block of the grid scored, since the host does not know where a motion
         box lands."""
-        boxes, cap, sc, k, found = held[0], self.cap, self.sched, len(held[1]), self.found
+        boxes, cap, k, found = held[0], self.cap, len(held[1]), self.found
         desc, rnd, n, masks = self._motion_front(issue, held)
         keep = torch.zeros(cap, dtype=torch.uint8, device=self.device)
-        stream_cut(self.raw_ring, self.flow_ring, n, rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
-                   rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, keep)
+        self._cut(rnd, n, keep)
         cells = [(hh, ww) for hh in range(self.hb) for ww in range(self.wb)]
         out = torch.full((1 + len(cells) * cap,), -float(BIG), dtype=torch.float64, device=self.device)
         zrects = desc[self.t_base + self.t_rects:self.t_base + self.t_rects + 4 * cap] if self.maps else None

@@ -1,10 +1,11 @@
 """Training from pushed frames: a camera's normal footage in, models and training-score statistics out (``StreamCollector``).
 
 ``vec_vad_amd.stream.StreamScorer`` scores a camera frame by frame, but the models and statistics it is built from could only come
-from ``train.py`` on a dataset tree.  A ``StreamCollector`` is the scorer's front half with no model behind it: the same frame checks
-and refusals before any state is touched, the same ``RingSchedule`` with its one frame of look-ahead, the same descriptor through a
-pinned staging buffer, the flow at one pair per launch and ``vv_stream_cut`` per round into ``max_boxes`` fixed slots
-(``boxes='motion'``: ``vv_motion_mask`` -> ``vv_mask_boxes`` -> ``vv_stream_boxes`` in front of the one round of a frame).  Behind
+from ``train.py`` on a dataset tree.  A ``StreamCollector`` is the scorer's front half with no model behind it
+(``vec_vad_amd.stream_front.StreamFront``, the base class of both): the same frame checks and refusals before any state is touched, the
+same ``RingSchedule`` with its one frame of look-ahead, the same descriptor through a pinned staging buffer, the flow at one pair per
+launch and the cut of every round into ``max_boxes`` fixed slots (``boxes='motion'``: ``vv_motion_mask`` -> ``vv_mask_boxes`` ->
+``vv_stream_boxes`` in front of the one round of a frame).  Behind
 every cut ONE ``vv_stream_append`` packs the round's kept cubes behind those of the rounds before into a training store of
 ``[mi355x] collect_max_cubes`` cubes, with the frame, the box index, the box and the block cells of every cube in three small tables
 next to it.  The cursor lives on the device (two cells, alternated per launch): neither ``push`` nor ``end_video`` synchronises.
@@ -27,22 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .extract import boxes_to_crops
-from .stream import RingSchedule, StreamScorer, _Staging, _dev, check_frame, check_max_boxes, check_stream_boxes, stream_cut
+from .stream_front import RingSchedule, StreamFront, _dev, check_max_boxes, check_max_cubes, check_stream_boxes  # noqa: F401
 
 COLLECT_MAX_CUBES = 65536      # [mi355x] collect_max_cubes default: 65536 x 56 320 B (5 raw uint8 + 5 flow float32 patches) = 3.7 GB
-
-
-def check_max_cubes(v):
-    """``collect_max_cubes`` as an integer >= 1, else a one-line ``ValueError``; no GPU is touched."""
-    if isinstance(v, str):
-        try:
-            v = int(v.strip())
-        except ValueError:
-            pass
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-        raise ValueError('[mi355x] collect_max_cubes must be an integer >= 1, got {!r}'.format(v))
-    return int(v)
 
 
 def stream_append(raw_slots, flow_slots, keep, n, masks, boxes, frame, slot0, cursor_in, cursor_out, raw_store, flow_store, meta,
@@ -94,7 +82,7 @@ def meta_groups(meta, meta_cells, n_frames, wb):
     return block_groups([int(f) for f in meta[:, 0]], cube_blocks, n_frames)
 
 
-class StreamCollector:
+class StreamCollector(StreamFront):
     """``StreamCollector(c, frame_shape, flownet2=None, max_boxes=None, max_cubes=None, boxes=None, device='cuda')``.
 
     ``c``: the dict of ``train.read_config``; ``frame_shape``: ``(H, W, C)`` of the uint8 frames that will be pushed (C = 1 or 3);
@@ -115,73 +103,24 @@ class StreamCollector:
     ``train(net=None, save=False)`` -> ``(net_set, stats_raw, stats_of)`` as ``test.load_artifacts`` returns them: ``finish()`` if
     needed, then ``train.train_store``; ``save`` also writes the three files where ``train.py`` writes them."""
 
-    # the scorer's own code for the launches of the front half: neither holds a model
-    _flow = StreamScorer._flow
-    _fill_round = StreamScorer._fill_round
-    _motion_front = StreamScorer._motion_front
-    tail = False               # no stage reads a descriptor tail here
+    verb = 'collects'
+    block_mode_key = 'train_block_mode'      # the training rules: every cell of calc_block_idx, no painted-rectangle test
+    painted_only = False
 
     def __init__(self, c, frame_shape, flownet2=None, max_boxes=None, max_cubes=None, boxes=None, device='cuda'):
         self.cap = check_max_boxes(c.get('stream_max_boxes', 64) if max_boxes is None else max_boxes)      # before any GPU work
         self.capacity = check_max_cubes(c.get('collect_max_cubes', COLLECT_MAX_CUBES) if max_cubes is None else max_cubes)
         self.motion = check_stream_boxes(c.get('stream_boxes', 'given') if boxes is None else boxes) == 'motion'
-        from vad_datasets import frame_size
-        from vec_vad_amd.motion import CONSTANTS
-        cp, ds, method = c['cp'], c['dataset_name'], c['method']
-        if ds == 'ShanghaiTech':
+        cp, method = c['cp'], c['method']
+        if c['dataset_name'] == 'ShanghaiTech':
             from train import DIRECT_TRAIN_SHANGHAI
             raise NotImplementedError(DIRECT_TRAIN_SHANGHAI)
-        if self.motion and ds not in CONSTANTS:
-            raise ValueError("stream_boxes = motion: the motion stage has no constants for dataset {!r}".format(ds))
-        if cp.get(method, 'border_mode') != 'predict':
-            raise ValueError("a stream collects with border_mode = predict only (a centred window needs frames that have not arrived), "
-                             "got {!r}".format(cp.get(method, 'border_mode')))
-        H, W, C = (int(v) for v in frame_shape)
-        if C not in (1, 3):
-            raise ValueError('frames must have 1 or 3 channels, got frame_shape {!r}'.format(tuple(frame_shape)))
-        self.c, self.H, self.W, self.C = c, H, W, C
-        self.sched = RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion)
-        self.P = cp.getint(ds, 'patch_size')
-        self.thr = cp.getfloat(ds, 'motionThr')
-        self.hb, self.wb = c['h_block'], c['w_block']
-        self.grid_h, self.grid_w = frame_size[ds][0], frame_size[ds][1]
-        if self.motion and (H > self.grid_h or W > self.grid_w):
-            raise ValueError('stream_boxes = motion: {}x{} frames are larger than the nominal {}x{} frame of {}, so a motion box could '
-                             'fall outside the block grid'.format(H, W, self.grid_h, self.grid_w, ds))
-        self.h_step, self.w_step = self.grid_h / self.hb, self.grid_w / self.wb
-        self.block_mode = cp.getint(ds, 'train_block_mode')
-        dev = torch.device(device)
-        self.device = dev = dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
-        if flownet2 is None:
-            from calc_optical_flow import load_flownet2
-            flownet2 = load_flownet2(c['flownet2_checkpoint'], device=dev, fp16=c['direct_flow_fp16'])
-        from calc_optical_flow import FLOW_H, FLOW_W
-        self.flow_h, self.flow_w = FLOW_H, FLOW_W
-        self.flow_in, self.flow_out, self.flow_graph = flownet2.graph_entry((1, 3, 2, FLOW_H, FLOW_W))
-        self.flownet2 = flownet2
-        sc, cap, P, cells = self.sched, self.cap, self.P, self.hb * self.wb
-        self.raw_ring = torch.zeros((sc.R, H, W, C), dtype=torch.uint8, device=dev)
-        self.flow_ring = torch.zeros((sc.Rf, H, W, 2), dtype=torch.float32, device=dev)
-        self.store_raw = torch.zeros((cap, sc.T, P, P, C), dtype=torch.uint8, device=dev)
-        self.store_flow = torch.zeros((cap, sc.Tf, P, P, 2), dtype=torch.float32, device=dev)
-        self.keep = torch.zeros(cap, dtype=torch.uint8, device=dev)
-        # the descriptor of one round, as the scorer lays it out: n, 3 unused | crops | raw window | flow window | masks [hb*wb][cap] bytes
-        self.w_crops = 4
-        self.w_rwin = self.w_crops + 4 * cap
-        self.w_fwin = self.w_rwin + sc.T
-        self.w_mask = (self.w_fwin + sc.Tf + 3) // 4 * 4
-        self.D = self.w_mask + (cells * cap + 3) // 4
-        self.desc = torch.zeros(4 + self.D, dtype=torch.int32, device=dev)
-        if self.motion:
-            self.w_mwin = 4 + self.D
-            self.w_ap = self.w_mwin + 4
-            self.desc = torch.zeros(self.w_ap + 5 * cap, dtype=torch.int32, device=dev)
-            self.mt = CONSTANTS[ds]
-            self.mt_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
-            self.mt_work = torch.empty((_lib.lib().vv_mask_boxes_workspace_bytes(1, H, W),), dtype=torch.uint8, device=dev)
-            self.mt_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.mt_boxes = torch.zeros((cap, 4), dtype=torch.int32, device=dev)
-            self.found = torch.zeros((2 + 4 * cap,), dtype=torch.int32, device=dev)                       # n, dropped, boxes_out [cap][4]
+        self._refuse(c, frame_shape)
+        self.c = c
+        super().__init__(c, RingSchedule(cp.getint(method, 'context_frame_num'), cp.getint(method, 'context_of_num'), motion=self.motion),
+                         flownet2, device)
+        sc, P, C, cells, dev = self.sched, self.P, self.C, self.hb * self.wb, self.device
+        self.keep = torch.zeros(self.cap, dtype=torch.uint8, device=dev)
         # the training store and its tables; state: cursor cells [2] (launch i reads cell i % 2 and writes the other), dropped boxes
         self.train_raw = torch.empty((self.capacity, sc.T, P, P, C), dtype=torch.uint8, device=dev)
         self.train_flow = torch.empty((self.capacity, sc.Tf, P, P, 2), dtype=torch.float32, device=dev)
@@ -190,7 +129,6 @@ class StreamCollector:
         self.meta_cells = torch.zeros((self.capacity, cells), dtype=torch.uint8, device=dev)
         self.state = torch.zeros(3, dtype=torch.int32, device=dev)
         self.launches = 0         # vv_stream_append launches so far: the current cursor is cell launches % 2
-        self.staging = _Staging()
         self.held = None          # (boxes, crops, blocks, appearance table | None) of the frame that waits for its look-ahead
         self.frames = 0           # frames pushed so far, across videos
         self.given = []           # per pushed frame: the boxes the host knows (given boxes, or the appearance boxes in motion mode)
@@ -199,40 +137,10 @@ class StreamCollector:
         self.finished = False
         torch.cuda.synchronize(dev)
 
-    # ---- host side of a frame: everything that can be refused is refused before a ring is touched
-    def _prepare(self, frame_u8, boxes):
-        from utils import calc_block_idx
-        frame, boxes = check_frame(frame_u8, boxes, self.H, self.W, self.C)
-        ap = None
-        if self.motion:                                   # the given boxes are the frame's appearance boxes: one round holds them all
-            from .motion import _ap_table
-            if len(boxes) > self.cap:
-                raise ValueError('{} appearance boxes, stream_max_boxes holds {} (with stream_boxes = motion a frame is one '
-                                 'round)'.format(len(boxes), self.cap))
-            ap = _ap_table([boxes], 1)
-        crops = boxes_to_crops(boxes, self.H, self.W)
-        blocks = []
-        for b, bb in enumerate(boxes):                    # the training rule: every cell of calc_block_idx, no painted-rectangle test
-            cells = calc_block_idx(bb[0], bb[2], bb[1], bb[3], self.h_step, self.w_step, mode=self.block_mode)
-            if any(not (0 <= hi < self.hb and 0 <= wi < self.wb) for hi, wi in cells):
-                raise IndexError('box {} falls outside the {}x{} block grid'.format(b, self.hb, self.wb))
-            blocks.append(sorted(set(cells)))
-        return frame, (boxes, crops, blocks, ap)
-
     def push(self, frame_u8, boxes=None, ap_boxes=None):
         if self.finished:
             raise ValueError('this collector has finished: its store is handed over, start a new one for more frames')
-        if self.motion:
-            boxes = ap_boxes if ap_boxes is not None else (boxes if boxes is not None else np.zeros((0, 4), np.float64))
-        elif boxes is None or ap_boxes is not None:
-            raise ValueError('push takes the frame and its boxes; ap_boxes and a push without boxes belong to stream_boxes = motion')
-        frame, held = self._prepare(frame_u8, boxes)
-        slot, issue = self.sched.push()
-        st = self.staging.get('frame', frame.shape, torch.uint8)
-        st[0].numpy()[...] = frame
-        self.raw_ring[slot].copy_(st[0], non_blocking=True)
-        st[1] = torch.cuda.Event()
-        st[1].record()
+        issue, held = self._take(frame_u8, boxes, ap_boxes)
         if issue is not None:
             self._issue(issue, self.held)
         self.held = held
@@ -255,49 +163,25 @@ class StreamCollector:
                       self.meta_cells)
         self.launches += 1
 
-    def _cut(self, rnd, n):
-        sc = self.sched
-        stream_cut(self.raw_ring, self.flow_ring, n, rnd[self.w_crops:self.w_rwin], rnd[self.w_rwin:self.w_fwin],
-                   rnd[self.w_fwin:self.w_fwin + sc.Tf], self.thr, self.store_raw, self.store_flow, self.keep)
-
     def _issue(self, issue, held):
         """The launches of one issued frame (the frame pushed before the newest, or a video's last): the descriptor, the flow, and per
         round of ``max_boxes`` boxes ``vv_stream_cut`` and ``vv_stream_append``.  A frame without boxes still gets its flow: later
         frames' flow windows name it."""
         if self.motion:
             desc, rnd, n, masks = self._motion_front(issue, held)
-            self._cut(rnd, n)
+            self._cut(rnd, n, self.keep)
             self._append(n, masks[:self.hb * self.wb * self.cap], self.found[2:], 0)
             self.state[2:3].add_(self.found[1:2])         # the dropped boxes, accumulated where they are counted
             self.slots += self.cap
             return
         boxes, crops, blocks, _ = held
-        cap, D = self.cap, self.D
-        n = len(crops)
-        rounds = (n + cap - 1) // cap
-        words = 4 + max(rounds, 1) * D
-        if self.desc.numel() < words:
-            self.desc = torch.zeros(words, dtype=torch.int32, device=self.device)
-        st = self.staging.get('desc', (words,), torch.int32)
-        d = st[0].numpy()
-        d[:] = 0
-        d[0:2] = issue['pair_slots']
-        d[2] = issue['flow_slot']
-        d[3] = rounds
+        st, _, rounds, _, _ = self._describe([(0, issue, crops, blocks)])
+        desc = self._start(st)
         for r in range(rounds):
-            o = 4 + r * D
-            self._fill_round(d[o:o + D], issue, crops[r * cap:(r + 1) * cap], blocks[r * cap:(r + 1) * cap])
-        desc = self.desc
-        desc[:words].copy_(st[0], non_blocking=True)
-        st[1] = torch.cuda.Event()
-        st[1].record()
-        self._flow(desc.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-        for r in range(rounds):
-            o = 4 + r * D
-            rnd = desc[o:o + D]
-            self._cut(rnd, rnd[0:1])
-            self._append(rnd[0:1], rnd[self.w_mask:].view(torch.uint8)[:self.hb * self.wb * cap], None, r * cap)
-        self.slots += n
+            rnd, n, masks = self._round(desc, r)
+            self._cut(rnd, n, self.keep)
+            self._append(n, masks[:self.hb * self.wb * self.cap], None, r * self.cap)
+        self.slots += len(crops)
 
     def finish(self):
         """The one host synchronisation: the cursor, the dropped-box count and the meta rows come to the host (one event behind
